@@ -19,13 +19,19 @@ with fewer than N GPUs the ranks share device 0 over gloo: a rehearsal of the la
       `volume.segment_volume` on all N ranks (slice-sharded image encoder + conditioning pass, one RCCL exchange of memories / features,
       the propagation chain with the memory cross-attention's key range split over the ranks).  A step = one whole volume;
       scaling = "strong"; the per-phase seconds of the last volume are on the line.
-The 2d line also carries that volume pass as the side object `volume_3d` (after the timed region; guarded by a watchdog: if the exchange
-hangs, rank 0 still prints the line with the error recorded in it).
+A plain run sets up, warms up, times `--steps` steps and prints the line; `ms_per_step` is the wall time of one timed step.
+`--dump-outputs DIR` then writes what the last timed step returned on rank 0 (2d: low_res_masks, iou_predictions, maskmem_features;
+volume: every slice's low-res mask logits) as float32 .npy files, a fixed strided sample of an array past the 60 MB budget; the inputs
+and weights are seeded, so two builds can be compared output for output.  Everything below -- the side objects of the 2d line -- runs only with `--full` (each `--no-*` flag still skips its
+part there).
+
+With `--full` the 2d line also carries that volume pass as the side object `volume_3d` (after the timed region; guarded by a watchdog:
+if the exchange hangs, rank 0 still prints the line with the error recorded in it).
 
 Extra objects on the JSON line: "roofline" (dominant kernel = the memory cross-attention, attn_kv64x2_kernel, MFMA-bound; timed with
 HIP events on the launch stream), "roofline_gemm" (the GEMM family of the step: every distinct shape the step launches, timed the same
 way; flop-weighted fraction of the MFMA peak), "roofline_hiera_attention" and "cpu_baseline" (the CPU oracle on a bounded sample,
-rank 0, N=1 only).
+rank 0, N=1 only), and the other operand type's library on the same step (a child process, N=1 only).
 
 `cpu_baseline.parity_slice0`: the oracle sample IS slice 0 of the timed step (same image, click and memory bank), so its mask is compared
 with the HIP path's -- mask IoU and max / mean |delta logit| at the full 1024^2 size.
@@ -460,7 +466,8 @@ LIVE_VOLUME_STATS: dict = {}       # the running pass's `stats` (phases done so 
 
 def run_volume(m, device, T, world, sync_dev, steps, warmup):
     """`steps` timed passes of the whole T-slice volume through segment_volume (all ranks, strong scaling).  Returns (seconds for all
-    steps = max over ranks, phase seconds of the last pass on this rank, how the chain used the ranks, foreground fraction)."""
+    steps = max over ranks, phase seconds of the last pass on this rank, how the chain used the ranks, foreground fraction, slices,
+    the last pass's masks {slice: low-res logits})."""
     import medical_sam2_amd.parallel as par
     import medical_sam2_amd.volume as vol
     volume, prompts = volume_workload(device, T)
@@ -484,7 +491,7 @@ def run_volume(m, device, T, world, sync_dev, steps, warmup):
     dt = par.max_over_ranks(time.perf_counter() - t0, sync_dev)
     fg = sum(float((v > 0).float().mean()) for v in masks.values()) / len(masks)
     chain = "single rank" if world == 1 else "memory cross-attention key range split over the ranks (1 object < ranks), rest of the chain replicated"
-    return dt, st.get("phase_s"), chain, fg, len(masks)
+    return dt, st.get("phase_s"), chain, fg, len(masks), masks
 
 
 VOLUME_WORKLOAD = ("configs[3]: sam2_hiera_s 3D, ONE {T}-slice 1024x1024 synthetic volume, bbox prompt on every 2nd slice ({C} conditioning "
@@ -493,7 +500,7 @@ VOLUME_WORKLOAD = ("configs[3]: sam2_hiera_s 3D, ONE {T}-slice 1024x1024 synthet
 
 
 def volume_side_object(m, device, T, world, sync_dev):
-    dt, phases, chain, fg, n = run_volume(m, device, T, world, sync_dev, steps=1, warmup=0)
+    dt, phases, chain, fg, n, _ = run_volume(m, device, T, world, sync_dev, steps=1, warmup=0)
     return {"workload": VOLUME_WORKLOAD.format(T=T, C=T // 2, K=(T // 2 + 3) * 4096), "scaling": "strong", "n_gpus": world, "slices": n,
             "seconds_per_volume": dt, "slices_per_s": T / dt, "phase_s_rank0": phases, "chain": chain, "mean_foreground_fraction": fg}
 
@@ -531,6 +538,24 @@ def other_dtype_side_object(other, steps, warmup, oracle_low):
                                     "max_abs_dlogit": (low - oracle_low).abs().max().item(),
                                     "mean_abs_dlogit": (low - oracle_low).abs().mean().item()}
         return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000     # all arrays of one --dump-outputs together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: {name: tensor} -> DIR/<name>.npy in float32.  An array larger than its even share of DUMP_BUDGET_BYTES is
+    replaced by a fixed strided sample of its flattened elements (the same indices whenever the arguments are the same), written as
+    DIR/<name>_sample.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            a, name = a.reshape(-1)[np.linspace(0, a.size - 1, share // a.itemsize).astype(np.int64)], f"{name}_sample"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -610,11 +635,20 @@ def main():
                     help="skip the side object that runs the same step on the OTHER operand type's library (N=1 only)")
     ap.add_argument("--no-rooflines", action="store_true", help="skip the per-kernel roofline legs (used by the bf16 child run)")
     ap.add_argument("--dump-slice0", default=None, help="write the low-res mask logits of slice 0 to this file (bf16 child run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures of the 2d line: rooflines, CPU baseline with the slice-0 parity, training iteration, "
+                         "the other operand type, volume_3d (each --no-* flag still skips its part).  Without it a run only times the step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (rank 0) as DIR/<name>.npy in float32, 60 MB at most")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.mode == "2d" else 3
     if args.warmup is None:
         args.warmup = 3 if args.mode == "2d" else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_rooflines = args.no_cpu_baseline = args.no_train = args.no_bf16 = args.no_volume = True
 
     # the operand type is a property of the loaded library: choose it before the package is imported (and before ranks are launched:
     # the children inherit the environment)
@@ -650,7 +684,10 @@ def main():
 
     if args.mode == "volume":
         T = args.slices
-        dt, phases, chain, fg, n = run_volume(m, device, T, world, sync_dev, args.steps, args.warmup)
+        dt, phases, chain, fg, n, masks = run_volume(m, device, T, world, sync_dev, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"low_res_masks": torch.stack([masks[t].float().cpu() for t in sorted(masks)])})
+        del masks
         if rank == 0:
             line = {"metric": "slices/sec @1024^2 (Hiera-S)", "value": T * args.steps / dt, "unit": "slices/s", "n_gpus": world,
                     "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -712,14 +749,20 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     torch.cuda.synchronize()
     par.barrier(sync_dev)
     torch.cuda.synchronize()
     dt = par.max_over_ranks(time.perf_counter() - t0, sync_dev)
+    if graph is None:
+        out = last                     # eager: the last step's own outputs (a replay refills the captured `out` in place)
     low0 = (out[0][0] if isinstance(out, list) else out[0])[:1]
     if args.dump_slice0 and rank == 0:
         torch.save(low0.detach().float().cpu(), args.dump_slice0)
+    if args.dump_outputs and rank == 0:
+        parts_out = out if isinstance(out, list) else [out]      # --streams: one (low_res, iou, maskmem) per sub-batch
+        dump_outputs(args.dump_outputs, {name: torch.cat([p[i] for p in parts_out])
+                                         for i, name in enumerate(("low_res_masks", "iou_predictions", "maskmem_features"))})
 
     line = None
     if rank == 0:

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -38,7 +39,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_header_matches_sources():
     before = open(os.path.join(ROOT, "include", "msam2_hip.h")).read()
-    subprocess.check_call(["python", os.path.join(ROOT, "tools", "gen_header.py")], stdout=subprocess.DEVNULL)
+    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "gen_header.py")], stdout=subprocess.DEVNULL)
     assert open(os.path.join(ROOT, "include", "msam2_hip.h")).read() == before, "include/msam2_hip.h is stale: run tools/gen_header.py"
 
 

@@ -5,7 +5,7 @@ tag=${1:-r02}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-train > $out/bench_line.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-train > $out/bench_line.json 2> $out/bench.err
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $out/pmc_$c -- python3 tools/one_attn.py 4 1 4096 16384 kv64 4 > /dev/null 2> $out/pmc_$c.err
   rocprofv3 --pmc $c --output-format csv -d $out/win_pmc_$c -- python3 tools/one_win.py stage3 > /dev/null 2> $out/win_pmc_$c.err

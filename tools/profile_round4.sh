@@ -10,8 +10,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 export MSAM2_LIB_PATH=$PWD/medical-sam2_amd/libmsam2_hip_bf16.so
 export MSAM2_BENCH_GEMM_TABLE=$out/gemm_table.json
-python3 bench.py --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-volume --no-bf16 > $out/bench_line_under_profiler.json 2> $out/bench_prof.err
+python3 bench.py --full --steps 20 --warmup 3 > $out/bench_line.json 2> $out/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-train --no-volume --no-bf16 > $out/bench_line_under_profiler.json 2> $out/bench_prof.err
 rocprofv3 --kernel-trace --output-format csv -d $out/trace -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-train --no-volume --no-bf16 --no-rooflines > /dev/null 2> $out/trace.err
 python3 tools/trace_step.py $out/trace 5 > $out/step_breakdown.txt 2>&1
 rm -rf $out/trace
