@@ -109,6 +109,13 @@ SIGNATURES = {
     "msam2_select_mask": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_i, c_f, c_f, c_p]),
     "msam2_gather_rows": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_obj_ptr_mix": (c_i, [c_p, c_p, c_p, c_l, c_l, c_p]),
+    "msam2_convt2x2_shuffle_shared": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p]),
+    "msam2_mask_stats_workspace_bytes": (c_z, [c_l]),
+    "msam2_mask_stats": (c_i, [c_p, c_l, c_l, c_l, c_l, c_l, c_f, c_f, c_f, c_p, c_p, c_p, c_z, c_p]),
+    "msam2_mask_rle_runs": (c_i, [c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_p]),
+    "msam2_mask_rle": (c_i, [c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_p, c_p]),
+    "msam2_box_nms_workspace_bytes": (c_z, [c_l]),
+    "msam2_box_nms": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_z, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

@@ -445,7 +445,7 @@ __global__ void pixel_shuffle_kernel(const op16* __restrict__ g, const float* __
 // Eight channels per lane (16-byte loads / stores), C / 8 lanes per output pixel, 512 / C pixels per wave: the one-channel-per-lane form
 // above moves 128 bytes per wave instruction (32 us per call at the decoder's shapes); LayerNorm statistics are reduced over the
 // pixel's C / 8 lanes with xor-shuffles.  C in {32, 64}.
-template <int C, typename TS>
+template <int C, typename TS, bool SHARED_SKIP = false>
 __global__ void pixel_shuffle8_kernel(const op16* __restrict__ g, const float* __restrict__ bias, const TS* __restrict__ skip,
                                       const float* __restrict__ ln_w, const float* __restrict__ ln_b, op16* __restrict__ y, int B, int h,
                                       int w) {
@@ -462,13 +462,15 @@ __global__ void pixel_shuffle8_kernel(const op16* __restrict__ g, const float* _
   const int64_t tok = ((int64_t)b * h + Y / 2) * w + X / 2;
   const int sub = (Y & 1) * 2 + (X & 1);
   const op16x8 gv = *reinterpret_cast<const op16x8*>(g + tok * 4 * C + sub * C + c0);
+  // SHARED_SKIP: one skip map serves every batch element (N prompt sets on one image: batch stride 0)
+  const int64_t sp = SHARED_SKIP ? pp - (int64_t)b * H * W : pp;
   float sk[8];
   if constexpr (sizeof(TS) == 4) {                            // fp32 skip (the FPN's own output type): no 16-bit copy pass in front of this kernel
-    const f32x4 s0 = *reinterpret_cast<const f32x4*>(skip + pp * C + c0), s1 = *reinterpret_cast<const f32x4*>(skip + pp * C + c0 + 4);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(skip + sp * C + c0), s1 = *reinterpret_cast<const f32x4*>(skip + sp * C + c0 + 4);
 #pragma unroll
     for (int e = 0; e < 8; ++e) sk[e] = e < 4 ? s0[e] : s1[e - 4];
   } else {
-    const op16x8 sv = *reinterpret_cast<const op16x8*>(skip + pp * C + c0);
+    const op16x8 sv = *reinterpret_cast<const op16x8*>(skip + sp * C + c0);
 #pragma unroll
     for (int e = 0; e < 8; ++e) sk[e] = op2f(sv[e]);
   }
@@ -537,6 +539,36 @@ extern "C" int msam2_convt2x2_shuffle(const void* gemm_out, const float* bias, c
 extern "C" int msam2_convt2x2_shuffle_f32skip(const void* gemm_out, const float* bias, const float* skip, const float* ln_w,
                                               const float* ln_b, void* y, int64_t B, int64_t h, int64_t w, int64_t C, void* stream) {
   return convt2x2_shuffle_launch<float>(gemm_out, bias, skip, ln_w, ln_b, y, B, h, w, C, stream);
+}
+
+// msam2_convt2x2_shuffle / _f32skip with the skip features read at a batch stride of skip_batch_stride elements: 0 = one [4hw, C] map shared
+// by all B batch elements (N prompt sets on one image, mask_decoder.py:215-231 with repeat_image, without materialising N copies), or
+// 4*h*w*C = one map per element (the plain entries).  Same per-pixel arithmetic as the plain entries: bit-identical results.
+// C = 32 / 64, 16-byte aligned tensors (the decoder's shapes).
+extern "C" int msam2_convt2x2_shuffle_shared(const void* gemm_out, const float* bias, const void* skip, int skip_is_16bit, const float* ln_w,
+                                             const float* ln_b, void* y, int64_t B, int64_t h, int64_t w, int64_t C, int64_t skip_batch_stride,
+                                             void* stream) {
+  MSAM2_REQUIRE(gemm_out && bias && skip && y, "convt2x2_shuffle_shared: null tensor");
+  MSAM2_REQUIRE(B > 0 && h > 0 && w > 0 && (C == 32 || C == 64), "convt2x2_shuffle_shared: C must be 32 or 64");
+  MSAM2_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "convt2x2_shuffle_shared: ln_w and ln_b go together");
+  MSAM2_REQUIRE(skip_batch_stride == 0 || skip_batch_stride == 4 * h * w * C, "convt2x2_shuffle_shared: skip_batch_stride must be 0 or 4*h*w*C");
+  const bool al = (((uintptr_t)gemm_out | (uintptr_t)skip | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)ln_w | (uintptr_t)ln_b) & 15) == 0;
+  MSAM2_REQUIRE(al, "convt2x2_shuffle_shared: tensors must be 16-byte aligned");
+  if (skip_batch_stride != 0)
+    return skip_is_16bit ? msam2_convt2x2_shuffle(gemm_out, bias, skip, ln_w, ln_b, y, B, h, w, C, stream)
+                         : msam2_convt2x2_shuffle_f32skip(gemm_out, bias, (const float*)skip, ln_w, ln_b, y, B, h, w, C, stream);
+  const int64_t threads = B * 4 * h * w * (C / 8);
+  const dim3 grid(cdiv(threads, 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+#define PS8(CC, TS) hipLaunchKernelGGL((pixel_shuffle8_kernel<CC, TS, true>), grid, block, 0, s, (const op16*)gemm_out, bias, (const TS*)skip, ln_w, \
+                                       ln_b, (op16*)y, (int)B, (int)h, (int)w)
+  if (C == 64) {
+    if (skip_is_16bit) PS8(64, op16); else PS8(64, float);
+  } else {
+    if (skip_is_16bit) PS8(32, op16); else PS8(32, float);
+  }
+#undef PS8
+  return msam2_check_launch("convt2x2_shuffle_shared");
 }
 
 // masks[n, k, p] = sum_c hyper[n, k, c] * up[n, p, c]   (mask_decoder.py:249-256), C = 32, K mask tokens; fp32 out

@@ -312,10 +312,10 @@ class MaskDecoder(nn.Module):
         return ops.gemm(tokens_bf16, w_bf16(self._wc, f"cs{which}w", c.weight), v_f32(self._wc, f"cs{which}b", c.bias), out_dtype=out_dtype)
 
     def predict_masks_tokens(self, src_tokens: torch.Tensor, pe_tokens: torch.Tensor, sparse: torch.Tensor, feat_s0: torch.Tensor,
-                             feat_s1: torch.Tensor, B: int, h: int, w: int):
+                             feat_s1: torch.Tensor, B: int, h: int, w: int, shared_skips: bool = False):
         """src_tokens fp32 [B*h*w, C] (= image embedding + dense prompt); pe_tokens fp32 [h*w, C]; sparse fp32 [B,P,C];
-        feat_s0 [B*16hw, C/8], feat_s1 [B*4hw, C/4] token-major, 16-bit or fp32.  Returns (masks [B,4,4h,4w] fp32, iou [B,4],
-        mask_tokens_out [B,4,C], object_score_logits [B,1])."""
+        feat_s0 [B*16hw, C/8], feat_s1 [B*4hw, C/4] token-major, 16-bit or fp32 (shared_skips: ONE image's [16hw, C/8] / [4hw, C/4],
+        read for all B prompt sets).  Returns (masks [B,4,4h,4w] fp32, iou [B,4], mask_tokens_out [B,4,C], object_score_logits [B,1])."""
         wc = self._wc
         C = self.transformer_dim
         out_tok = wc.get("otok", [self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight],
@@ -331,10 +331,11 @@ class MaskDecoder(nn.Module):
             keys16 = to_bf16(keys)
         self.transformer._keys16 = None
         g = ops.gemm(keys16, dc1_w)
-        u = ops.convt2x2_shuffle(g, v_f32(wc, "dc1b", up[0].bias), feat_s1, v_f32(wc, "lnw", up[1].weight), v_f32(wc, "lnb", up[1].bias), B, h, w)
+        shuffle = ops.convt2x2_shuffle_shared if shared_skips else ops.convt2x2_shuffle
+        u = shuffle(g, v_f32(wc, "dc1b", up[0].bias), feat_s1, v_f32(wc, "lnw", up[1].weight), v_f32(wc, "lnb", up[1].bias), B, h, w)
         dc2_w = wc.get("dc2", [up[3].weight], lambda: up[3].weight.detach().permute(2, 3, 1, 0).reshape(-1, C // 4).to(OP16).contiguous())
         g = ops.gemm(u, dc2_w)
-        u = ops.convt2x2_shuffle(g, v_f32(wc, "dc2b", up[3].bias), feat_s0, None, None, B, 2 * h, 2 * w)  # [B*16hw, C/8] bf16
+        u = shuffle(g, v_f32(wc, "dc2b", up[3].bias), feat_s0, None, None, B, 2 * h, 2 * w)  # [B*16hw, C/8] bf16
         heads = list(self.output_hypernetworks_mlps) + [self.iou_prediction_head, self.pred_obj_score_head]
         fusable = C == 256 and self.pred_obj_scores and all(
             m.num_layers == 3 and m._act_code == ops.ACT_RELU and m.layers[0].in_features == C and m.layers[0].out_features == C
@@ -394,6 +395,27 @@ class MaskDecoder(nn.Module):
         # (torch.repeat_interleave of the embedding; the position encoding and the dense embedding broadcast).  The high-res skips are
         # added un-repeated in the reference (244-247), which only broadcasts for ONE image: mirrored, anything else raises like torch.
         n_sets = sparse_prompt_embeddings.shape[0]
+        from .. import autograd as ag
+        # N prompt sets on ONE image (SAM2ImagePredictor._predict with repeat_image): the embedding and both skip maps are read at a
+        # batch stride of 0 -- no N copies of them (at N = 64 and 1024^2 the skips alone would be 805 MB of fp32).  Bit-identical to
+        # the materialised path below.
+        shared = (n_sets > 1 and image_embeddings.shape[0] == 1 and high_res_features is not None
+                  and all(f.shape[0] == 1 for f in high_res_features) and self.transformer_dim // 8 in (32, 64)
+                  and (cell_nums is None or torch.as_tensor(cell_nums).reshape(-1).tolist() == [n_sets]) and not ag.active(self))
+        if shared:
+            _, C, h, w = image_embeddings.shape
+            B = n_sets
+            e3 = tokens_of(image_embeddings.to(F32)).view(1, h * w, C).expand(B, h * w, C)        # stride 0 over the prompt sets
+            dense = dense_prompt_embeddings.to(F32).expand(B, C, h, w)
+            if dense.stride(2) == 0 and dense.stride(3) == 0:
+                d3 = dense[:, :, 0, 0].unsqueeze(1).expand(B, h * w, C)
+            else:
+                d3 = tokens_of(dense).view(B, h * w, C)
+            src = ops.add_cast(e3, d3, 1.0, F32).view(B * h * w, C)
+            pe = tokens_of(image_pe.to(F32))[: h * w]
+            f0, f1 = high_res_features
+            skip = lambda f: tokens_of(f) if (f.dtype == F32 and f.shape[1] in (32, 64)) else to_bf16(tokens_of(f))
+            return self.predict_masks_tokens(src, pe, sparse_prompt_embeddings.to(F32), skip(f0), skip(f1), B, h, w, shared_skips=True)
         if image_embeddings.shape[0] != n_sets:
             if cell_nums is not None:
                 cn = torch.as_tensor(cell_nums, device=image_embeddings.device).reshape(-1).long()
@@ -414,7 +436,6 @@ class MaskDecoder(nn.Module):
             high_res_features = hr
         B, C, h, w = image_embeddings.shape
         assert sparse_prompt_embeddings.shape[0] == B, "one prompt set per (repeated) image embedding"
-        from .. import autograd as ag
         if ag.active(self):
             # train() + grad mode (func_2d/function.py:140-170 calls this module directly): differentiable glue + the decoder's Function
             src = tokens_of(image_embeddings.to(F32)).view(B, h * w, C) + tokens_of(dense_prompt_embeddings.to(F32).expand(B, C, h, w)).view(B, h * w, C)

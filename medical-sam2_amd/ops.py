@@ -542,6 +542,17 @@ def convt2x2_shuffle(g: torch.Tensor, bias, skip: torch.Tensor, ln_w, ln_b, B: i
     return y
 
 
+def convt2x2_shuffle_shared(g: torch.Tensor, bias, skip: torch.Tensor, ln_w, ln_b, B: int, h: int, w: int) -> torch.Tensor:
+    """convt2x2_shuffle with ONE skip map [4hw, C] (16-bit or fp32) read for all B batch elements (batch stride 0): N prompt sets on
+    one image without N copies of the high-resolution features.  Bit-identical to convt2x2_shuffle on the repeated map."""
+    C = g.shape[1] // 4
+    _req(g.dtype == OP16 and skip.dtype in (OP16, F32) and g.is_contiguous() and skip.is_contiguous(), "convt2x2_shuffle_shared: contiguous 16-bit g, 16-bit / fp32 skip")
+    _req(skip.numel() == 4 * h * w * C, "convt2x2_shuffle_shared: skip must be one [4hw, C] map")
+    y = torch.empty(B * 4 * h * w, C, dtype=OP16, device=g.device)
+    check(lib().msam2_convt2x2_shuffle_shared(_p(g), _p(bias), _p(skip), _is_bf16(skip), _p(ln_w), _p(ln_b), _p(y), B, h, w, C, 0, _stream()))
+    return y
+
+
 def hyper_masks(hyper: torch.Tensor, up: torch.Tensor, n: int, P: int) -> torch.Tensor:
     K, C = hyper.shape[1], hyper.shape[2]
     masks = torch.empty(n, K, P, dtype=F32, device=up.device)
@@ -714,3 +725,74 @@ def token_mlp3(hs: torch.Tensor, tok: torch.Tensor, w1, b1, w2, b2, w3, b3, out_
     check(lib().msam2_token_mlp3(_p(hs), hs.stride(0), hs.stride(1), _p(tok), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3),
                                  _p(out_dim), _p(sigmoid), _p(out), G, B, C, _stream()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# automatic mask generation: post-processing on low-res logits (csrc/amg.hip)
+def _f32(x: float) -> float:
+    """A Python threshold as torch compares an fp32 tensor with it (rounded to fp32)."""
+    return float(torch.tensor(x, dtype=F32))
+
+
+def mask_stats(logits: torch.Tensor, h: int, w: int, thr: float, offset: float):
+    """fp32 [M, lh, lw] low-res logits -> (counts int32 [M, 3], boxes int32 [M, 4]) of their (h, w) bilinear up-sampling:
+    counts = (#v > thr + offset, #v > thr - offset, #v > thr), boxes = inclusive xyxy of v > thr ([0,0,0,0] if empty)."""
+    _req(logits.dtype == F32 and logits.is_contiguous() and logits.dim() == 3, "mask_stats: fp32 contiguous [M, lh, lw]")
+    M, lh, lw = logits.shape
+    counts = torch.empty(M, 3, dtype=torch.int32, device=logits.device)
+    boxes = torch.empty(M, 4, dtype=torch.int32, device=logits.device)
+    nb = lib().msam2_mask_stats_workspace_bytes(M)
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=logits.device)
+    check(lib().msam2_mask_stats(_p(logits), M, lh, lw, int(h), int(w), _f32(thr), _f32(thr + offset), _f32(thr - offset), _p(counts), _p(boxes),
+                                 _p(ws), nb, _stream()))
+    return counts, boxes
+
+
+def mask_rle(logits: torch.Tensor, h: int, w: int, crop_xy: Tuple[int, int], orig_hw: Tuple[int, int], thr: float):
+    """Uncompressed RLEs ({"size": [H, W], "counts": [...]}, utils/amg.py format) of (bilinear (h, w) up-sampling of fp32 [M, lh, lw] > thr)
+    pasted at crop_xy = (x0, y0) into an orig_hw = (H, W) frame of zeros.  One small copy (run counts) and one copy of all counts to the host."""
+    _req(logits.dtype == F32 and logits.is_contiguous() and logits.dim() == 3, "mask_rle: fp32 contiguous [M, lh, lw]")
+    M, lh, lw = logits.shape
+    H, W = int(orig_hw[0]), int(orig_hw[1])
+    x0, y0 = int(crop_xy[0]), int(crop_xy[1])
+    t = _f32(thr)
+    if M == 0:
+        return []
+    runs = torch.empty(M, dtype=torch.int32, device=logits.device)
+    check(lib().msam2_mask_rle_runs(_p(logits), M, lh, lw, int(h), int(w), x0, y0, H, W, t, _p(runs), _stream()))
+    off = torch.zeros(M + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(runs.cpu().to(torch.int64), 0)
+    total = int(off[-1])
+    counts = torch.empty(total, dtype=torch.int32, device=logits.device)
+    off_d = off.to(logits.device)
+    check(lib().msam2_mask_rle(_p(logits), M, lh, lw, int(h), int(w), x0, y0, H, W, t, _p(off_d), _p(counts), _stream()))
+    flat = counts.cpu().tolist()
+    o = off.tolist()
+    return [{"size": [H, W], "counts": flat[o[i]:o[i + 1]]} for i in range(M)]
+
+
+def _f32_below(x: float) -> float:
+    """The largest fp32 t <= x: for every fp32 v, v > t exactly when v > x in double precision (torchvision compares its fp32 IoU with
+    the double threshold)."""
+    t = torch.tensor(x, dtype=F32)
+    if float(t) > x:
+        t = torch.nextafter(t, torch.tensor(-math.inf, dtype=F32))
+    return float(t)
+
+
+def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    """torchvision.ops.nms semantics (stable descending score order, IoU > threshold suppresses): int64 indices of the kept boxes,
+    in rank order."""
+    _req(boxes.dim() == 2 and boxes.shape[1] == 4 and scores.dim() == 1 and scores.shape[0] == boxes.shape[0], "box_nms: boxes [K, 4], scores [K]")
+    K = boxes.shape[0]
+    dev = boxes.device
+    if K == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    b = boxes.to(F32).contiguous()
+    s = scores.to(F32).contiguous()
+    keep = torch.empty(K, dtype=torch.int64, device=dev)
+    n_keep = torch.empty(1, dtype=torch.int32, device=dev)
+    nb = lib().msam2_box_nms_workspace_bytes(K)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    check(lib().msam2_box_nms(_p(b), _p(s), K, _f32_below(iou_threshold), _p(keep), _p(n_keep), _p(ws), nb, _stream()))
+    return keep[: int(n_keep.item())]

@@ -95,6 +95,13 @@ DOC = {
     "msam2_gather_rows": "Pick the SAM output token of the selected mask (sam2_base.py:375-383).",
     "msam2_obj_ptr_mix": "obj_ptr = lam*obj_ptr + (1-lam)*no_obj_ptr with the hard lam of fixed_no_obj_ptr (sam2_base.py:389-400).",
     "msam2_space_to_depth": "Non-overlapping k x k patches for the k2/s2 mask_downscaling convs (prompt_encoder.py:58-66) and the k4/s4\nmask_downsample conv (sam2_base.py:108,439).",
+    "msam2_convt2x2_shuffle_shared": "msam2_convt2x2_shuffle / msam2_convt2x2_shuffle_f32skip (skip_is_16bit selects) with the skip features read at a batch stride of\nskip_batch_stride elements: 0 = one [4hw, C] map serves all B batch elements (N prompt sets on one image, mask_decoder.py:215-231 with\nrepeat_image, sam2_image_predictor.py:317-418) instead of N materialised copies; 4*h*w*C = the plain entries.  Bit-identical to them.\nC = 32 / 64, 16-byte aligned tensors.",
+    "msam2_mask_stats_workspace_bytes": "Scratch (box accumulators, 16 bytes per mask) for msam2_mask_stats.",
+    "msam2_mask_stats": "One pass over the (h, w) bilinear up-sampling of low-res logits [M, lh, lw] fp32, re-evaluated per pixel with the expression of\nmsam2_bilinear_upsample (bit-identical, no high-res logits written): counts int32 [M, 3] = (#v > thr_hi, #v > thr_lo, #v > thr) --\nthe stability score's intersection / union (utils/amg.py:158-178) and the area -- and boxes int32 [M, 4] = the inclusive xyxy box of\nv > thr, [0,0,0,0] when empty (batched_mask_to_box, amg.py:305-348).  Thresholds are passed already rounded to fp32.",
+    "msam2_mask_rle_runs": "Pass 1 of msam2_mask_rle: runs int32 [M] = the length of each mask's uncompressed-RLE counts list (amg.py:109-137) over the\n(H, W) original-image frame with the (h, w) crop at (x0, y0) pasted in and 0 outside it (uncrop_masks).",
+    "msam2_mask_rle": "Pass 2: uncompressed RLE of (up-sampled logits > thr) in the reference's format -- column-major over the (H, W) frame, counts\nstarting with a 0 when the first pixel is set -- written as int32 at counts[offsets[m] .. offsets[m+1]) (offsets int64 [M + 1], the\nexclusive scan of msam2_mask_rle_runs); one workgroup per mask, ballot-ordered compaction, deterministic.",
+    "msam2_box_nms_workspace_bytes": "Scratch (rank order + K x ceil(K/64) IoU bitmask) for msam2_box_nms.",
+    "msam2_box_nms": "Greedy NMS with torchvision.ops.nms semantics (automatic_mask_generator.py's batched_nms with one category): boxes fp32 [K, 4] xyxy\n(16-byte aligned), scores fp32 [K]; ranks by score descending, ties to the lower input index (stable); IoU = inter / (area_a + area_b -\ninter) in fp32; a box is suppressed by a kept higher-ranked box with IoU > iou_thr.  keep int64 [K]: input indices of the kept boxes in\nrank order, n_keep int32 [1] their number.  K <= 65536 (the workspace is then 512 MiB).",
     "msam2_cc_workspace_bytes": "Scratch (union-find parents + area histogram) for msam2_cc_label.",
     "msam2_cc_label": "Drop-in for the reference's only native op, `_C.get_connected_componnets` (sam2_train/csrc/connected_components.cu:\n213-282; Python wrapper utils/misc.py:47-63): 8-connected labels (1 + smallest 2x2-block corner index of the component)\nand per-pixel component areas for uint8 masks [N,1,H,W], H and W even.  The caller allocates labels/counts/workspace.",
     "msam2_fill_holes_workspace_bytes": "Scratch for msam2_fill_holes.",
@@ -112,7 +119,7 @@ DOC = {
 
 def main():
     decls = []
-    for f in ["api.hip", "gemm.hip", "attention.hip", "attention_bwd.hip", "elementwise.hip", "conv.hip", "cc.hip", "backward.hip", "mlp_fused.hip"]:
+    for f in ["api.hip", "gemm.hip", "attention.hip", "attention_bwd.hip", "elementwise.hip", "conv.hip", "cc.hip", "backward.hip", "mlp_fused.hip", "amg.hip"]:
         s = open(os.path.join(CSRC, f)).read()
         for m in re.finditer(r'extern "C" ([^{;]+?)\s*\{', s, re.S):
             decls.append(" ".join(m.group(1).split()))
