@@ -392,11 +392,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
   // by every XCD.  Pure speed: any placement is correct.
   const int gx = gridDim.x, gy = gridDim.y;
   const int nwg = gx * gy * gridDim.z;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
   const int qtile = lid % gx;
   const int head = (lid / gx) % gy;
   const int zz = lid / (gx * gy);
@@ -433,8 +429,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
 
   // DMA sources: buffer descriptors (SGPRs) + loop-invariant 32-bit per-lane byte offsets + a scalar tile offset
   // (buffer_load_dwordx4 ... offen lds); piece j of this wave covers flat chunks (wave*PW + j)*64 + lane of the [32][CPR] image
-  const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kb, 0, 0x7fffffff, 0x00020000);
-  const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 0x7fffffff, 0x00020000);
+  const auto k_rsrc = raw_rsrc(kb);
+  const auto v_rsrc = raw_rsrc(vb);
   const int k_rb = (int)p.k_ts * 2, v_rb = (int)p.v_ts * 2;   // global row pitch in bytes
   unsigned koff[PW], voff[PW];
 #pragma unroll
@@ -615,7 +611,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
   for (int tile = t_begin; tile < t_full_end; ++tile) {
     const int st_i = (tile - t_begin) & 1;
     STAMP(t0_);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (tile + 1 < t_full_end) issue(tile + 1, st_i ^ 1);
     STAMP(t1_);
@@ -648,7 +644,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
       glds16(k_rsrc, base + j * 1024, ko, 0);
       glds16(v_rsrc, base + TILE + j * 1024, vo, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     compute(0, key0, true);
   }
@@ -721,11 +717,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   // XCD-aware work mapping (see attn_glds_kernel): the query tiles of one (batch, head, split) share an XCD's L2
   const int gx = gridDim.x, gy = gridDim.y;
   const int nwg = gx * gy * gridDim.z;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
   const int qtile = lid % gx;
   const int head = (lid / gx) % gy;
   const int zz = lid / (gx * gy);
@@ -751,8 +743,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   const int t_end = min(tiles_total, t_begin + tiles_per);
   const int t_full_end = min(t_end, Lk / BK);
 
-  const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kb, 0, 0x7fffffff, 0x00020000);
-  const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 0x7fffffff, 0x00020000);
+  const auto k_rsrc = raw_rsrc(kb);
+  const auto v_rsrc = raw_rsrc(vb);
   const int k_rb = (int)p.k_ts * 2, v_rb = (int)p.v_ts * 2;   // global row pitch in bytes
   unsigned koff[PWK], voff[PWV];
 #pragma unroll
@@ -880,7 +872,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   for (int tile = t_begin; tile < t_full_end; ++tile) {
     const int st_i = (tile - t_begin) & 1;
     STAMP(t0_);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (tile + 1 < t_full_end) issue(tile + 1, st_i ^ 1);
     STAMP(t1_);
@@ -919,7 +911,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
       const unsigned vo = (unsigned)((key0 + rr) * v_rb + ((c ^ (((row >> 1) & 1) << 2)) << 4));
       glds16(v_rsrc, smem + TILE_K + (wave * PWV + j) * 1024, vo, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     compute(0, key0, true);
   }
@@ -958,7 +950,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
     const int wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     if (wg < 4096) {
       g_wgtime[wg][0] = wg_t0_; g_wgtime[wg][1] = rt0_; g_wgtime[wg][2] = wg_t2_;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       g_wgtime[wg][3] = __builtin_amdgcn_s_memrealtime();
     }
   }
@@ -1008,11 +1000,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
   const int r = lane & 31, h = lane >> 5;
   const int gx = gridDim.x, gy = gridDim.y;
   const int nwg = gx * gy * gridDim.z;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
   const int qtile = lid % gx;
   const int head = (lid / gx) % gy;
   const int zz = lid / (gx * gy);
@@ -1044,8 +1032,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
   const int t_full_end = min(t_end, Lk / BK);
   const int nt = t_end - t_begin;
 
-  const auto k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kb, 0, 0x7fffffff, 0x00020000);
-  const auto v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vb, 0, 0x7fffffff, 0x00020000);
+  const auto k_rsrc = raw_rsrc(kb);
+  const auto v_rsrc = raw_rsrc(vb);
   const int k_rb = (int)p.k_ts * 2, v_rb = (int)p.v_ts * 2;
   // DMA piece j of this wave: LDS row / swizzled chunk it fills (fixed), global offset of that row in a full tile
   int krow[PWK], kchunk[PWK], vrow[PWV], vchunk[PWV];
@@ -1219,9 +1207,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
     issue(t_begin, 0);
     if (nt > 1) {
       issue(t_begin + 1, 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PWK + PWV) : "memory");   // tile 0 landed, tile 1 may still be in flight
+      wait_vmcnt<PWK + PWV>();   // tile 0 landed, tile 1 may still be in flight
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
     // two score buffers used alternately (the loop is unrolled by two): no copy between iterations, the AGPR -> VGPR reads of the
@@ -1231,7 +1219,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
     float mx[QB];
     int st_cur = 0, st_nxt = 1, st_ld = 2;
     auto iteration = [&](int i, f32x16 (&s_cur)[QB], f32x16 (&s_nxt)[QB]) __attribute__((always_inline)) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();   // tile i+1 has landed for every wave; every wave is done with iteration i-1 => stage st_ld is free
       if (i + 2 < nt) issue(t_begin + i + 2, st_ld);
       // block A: V fragments of tile i, 32 MFMAs of S(i+1), the exponentials of tile i (independent of the MFMAs)
@@ -1370,11 +1358,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
   const int r = lane & 31, h = lane >> 5;
   const int gx = gridDim.x, gy = gridDim.y;
   const int nwg = gx * gy * gridDim.z;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;   // query tiles of one (batch, head, split) share an XCD's L2 (see attn_glds_kernel)
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
   const int qtile = lid % gx;
   const int head = (lid / gx) % gy;
   const int zz = lid / (gx * gy);
@@ -1427,7 +1411,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
   static_assert(PIECES % PW == 0, "a wave's pieces must not straddle the K / V boundary");
   const bool isv = wave * PW >= PIECES;                               // wave-uniform
   const int d_rb = (int)(isv ? p.v_ts : p.k_ts) * 2;                  // global row pitch in bytes
-  const auto d_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(isv ? vb : kb), 0, 0x7fffffff, 0x00020000);
+  const auto d_rsrc = raw_rsrc(isv ? vb : kb);
   int drow[PW];
   unsigned dchunk[PW], doff[PW];
 #pragma unroll
@@ -1608,9 +1592,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
     issue(s_begin, 0);
     if (ns > 1) {
       issue(s_begin + 1, 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW) : "memory");   // stage 0 landed, stage 1 may still be in flight
+      wait_vmcnt<PW>();   // stage 0 landed, stage 1 may still be in flight
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
     f32x16 s0[QB], s1[QB];
@@ -1625,7 +1609,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
     // sub-tile 2T of stage T (slot sl0): opens the stage -- the only barrier of the stage
     auto even = [&](f32x16 (&s_cur)[QB], f32x16 (&s_nxt)[QB]) __attribute__((always_inline)) {
       if constexpr (PROBE < 4) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();   // stage T+1 has landed for every wave; every wave is done with stage T-1 => slot sl2 is free
         if (T + 2 < ns) issue(s_begin + T + 2, sl2);
       }
@@ -1728,13 +1712,9 @@ static int launch_attn_glds(const AttnParams& p, int Bz, hipStream_t s) {
   } else if constexpr (D == 96) {
     if (g96x2_applies(p)) {
       constexpr int LDS = 3 * 2 * 64 * 192;
-      static bool attr_set = false;
       static const bool x2 = getenv("MSAM2_G96_X2") != nullptr;   // 4 waves x 64 queries instead of 8 waves x 32
-      if (!attr_set) {
-        hipFuncSetAttribute((const void*)attn_g96x2_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        hipFuncSetAttribute((const void*)attn_g96x2_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-      }
+      ensure_dyn_lds<attn_g96x2_kernel<2, 4>>(LDS);
+      ensure_dyn_lds<attn_g96x2_kernel<1, 8>>(LDS);
       const dim3 g2(cdiv(p.Lq, 256), p.H, Bz * p.splits);
       if (x2) hipLaunchKernelGGL((attn_g96x2_kernel<2, 4>), g2, dim3(256), LDS, s, p);
       else hipLaunchKernelGGL((attn_g96x2_kernel<1, 8>), g2, dim3(512), LDS, s, p);
@@ -1752,11 +1732,7 @@ static int launch_attn_glds(const AttnParams& p, int Bz, hipStream_t s) {
 template <int D, int NW, bool WIN>
 static int launch_attn(const AttnParams& p, int Bz, hipStream_t s) {
   using C = AttnCfg<D>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)attn_fwd_kernel<D, NW, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    attr_set = true;
-  }
+  ensure_dyn_lds<attn_fwd_kernel<D, NW, WIN>>(C::LDS_BYTES);
   dim3 grid(cdiv(p.Lq, NW * 32), p.H, Bz * p.splits);
   // a single key tile per workgroup (the 4 x 4 windows of Hiera blocks 2 / 3: 16 keys) never touches the second stage: half the LDS
   // doubles the workgroups a CU holds, and these launches are bound by how many loads are in flight
@@ -2092,7 +2068,7 @@ __global__ __launch_bounds__(512) void attn_win_kernel(AttnParams p) {
     }
   }
 #ifdef MSAM2_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   ws3_ = __builtin_amdgcn_s_memrealtime();
   if (tid == 0) {
     const int wg = blockIdx.x + gridDim.x * blockIdx.y;
@@ -2119,11 +2095,7 @@ static bool attn_win_applies(const AttnParams& p) {
 
 static int launch_attn_win(const AttnParams& p, int Bz, hipStream_t s) {
   const int lds = (p.Lk + ((p.Lk + 7) & ~7)) * 192;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)attn_win_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr_set = true;
-  }
+  ensure_dyn_lds<attn_win_kernel<96>>(80 * 1024);
   // one wave per 32 queries; windows with few queries and many keys (q-pool blocks) get extra gather-only waves so that every thread
   // still moves its share of the K / V rows in one batch (they leave after the barrier)
   const int waves = min(8, max(cdiv(p.Lq, 32), cdiv((int64_t)p.Lk * 12, 6 * 64)));

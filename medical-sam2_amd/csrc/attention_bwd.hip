@@ -98,12 +98,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
   // XCD-aware placement (as in the forward): workgroups are dealt round-robin over the 8 XCDs, each with a private L2; all owner
   // blocks of one (batch, head) stream the SAME rows, so they go to one XCD (a contiguous slice of the remapped id space).
   const int gx = gridDim.x, gy = gridDim.y;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int nwg = gx * gy * gridDim.z;
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
   const int bx = lid % gx, head = (lid / gx) % gy, b = lid / (gx * gy);
   const int64_t bh = (int64_t)b * p.H + head;
 
@@ -329,12 +324,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int gx = gridDim.x, gy = gridDim.y;
-  int lid = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  {
-    const int nwg = gx * gy * gridDim.z;
-    const int q8 = nwg / 8, rem = nwg % 8, xcd = lid % 8;
-    lid = (xcd < rem ? xcd * (q8 + 1) : rem * (q8 + 1) + (xcd - rem) * q8) + lid / 8;
-  }
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
   const int bx = lid % gx, head = (lid / gx) % gy, b = lid / (gx * gy);
   const int64_t bh = (int64_t)b * p.H + head;
 
@@ -387,8 +377,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
   if (t_begin >= t_end) return;
   const int t_full_end = min(t_end, n_str / BK);
 
-  const auto rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)str1, 0, 0x7fffffff, 0x00020000);
-  const auto rsrc2 = __builtin_amdgcn_make_buffer_rsrc((void*)str2, 0, 0x7fffffff, 0x00020000);
+  const auto rsrc1 = raw_rsrc(str1);
+  const auto rsrc2 = raw_rsrc(str2);
   // per-lane source offsets: LDS slot f = (wave*PW + j)*64 + lane of an image holds global chunk swz(c) of row f / CPR
   auto src_off = [&](int j, int row_bytes, bool tr_image, int clamp_last) -> unsigned {
     const int f = (wave * PW + j) * 64 + lane;
@@ -408,15 +398,15 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
     const unsigned s1 = (unsigned)(tile * BK) * (unsigned)str1_rb, s2 = (unsigned)(tile * BK) * (unsigned)str2_rb;
 #pragma unroll
     for (int j = 0; j < PW; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (__attribute__((address_space(3))) void*)(base + j * 1024), 16, o1r[j], s1, 0, 0);
+      glds16(rsrc1, base + j * 1024, o1r[j], s1);
     if constexpr (ROLE != ROLE_DV) {
 #pragma unroll
       for (int j = 0; j < PW; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (__attribute__((address_space(3))) void*)(base + IMG + j * 1024), 16, o1t[j], s1, 0, 0);
+        glds16(rsrc1, base + IMG + j * 1024, o1t[j], s1);
     }
 #pragma unroll
     for (int j = 0; j < PW; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc2, (__attribute__((address_space(3))) void*)(base + (NIMG - 1) * IMG + j * 1024), 16, o2[j], s2, 0, 0);
+      glds16(rsrc2, base + (NIMG - 1) * IMG + j * 1024, o2[j], s2);
   };
   // statistics of the streamed rows (DK / DV): loaded by 32 lanes, parked in LDS next to the stage they belong to
   float rs_lse = 0.f, rs_del = 0.f;
@@ -524,7 +514,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
   }
   for (int tile = t_begin; tile < t_full_end; ++tile) {
     const int st_i = (tile - t_begin) & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (tile + 1 < t_full_end) {
       issue(tile + 1, st_i ^ 1);
@@ -542,17 +532,14 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
     const unsigned s1 = (unsigned)row0 * (unsigned)str1_rb, s2 = (unsigned)row0 * (unsigned)str2_rb;
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (__attribute__((address_space(3))) void*)(base + j * 1024), 16,
-                                               src_off(j, str1_rb, false, last), s1, 0, 0);
+      glds16(rsrc1, base + j * 1024, src_off(j, str1_rb, false, last), s1);
       if constexpr (ROLE != ROLE_DV)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc1, (__attribute__((address_space(3))) void*)(base + IMG + j * 1024), 16,
-                                                 src_off(j, str1_rb, true, last), s1, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc2, (__attribute__((address_space(3))) void*)(base + (NIMG - 1) * IMG + j * 1024), 16,
-                                               src_off(j, str2_rb, ROLE == ROLE_DV, last), s2, 0, 0);
+        glds16(rsrc1, base + IMG + j * 1024, src_off(j, str1_rb, true, last), s1);
+      glds16(rsrc2, base + (NIMG - 1) * IMG + j * 1024, src_off(j, str2_rb, ROLE == ROLE_DV, last), s2);
     }
     stat_load(t_full_end);
     stat_store(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     compute(0, row0, true);
   }
@@ -613,11 +600,7 @@ void launch_role_t(const AttnBwdParams& p, hipStream_t s) {
       return;
     }
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)attn_bwd_kernel<D, NW, ROLE, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-    attr_set = true;
-  }
+  ensure_dyn_lds<attn_bwd_kernel<D, NW, ROLE, DROP>>(C::LDS_BYTES);
   hipLaunchKernelGGL((attn_bwd_kernel<D, NW, ROLE, DROP>), grid, dim3(NW * 64), C::LDS_BYTES, s, p);
 }
 

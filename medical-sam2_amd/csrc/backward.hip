@@ -95,12 +95,7 @@ __global__ __launch_bounds__(256) void gemm_tt_kernel(GemmTTParams p) {
     }
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
   // transposed-read lane offsets (same pattern as the attention kernels' V^T fragments): rows = k, columns = m / n
   const int tr_off = (4 * h + (li >> 2)) * TT_PITCH + (16 * ((lane >> 4) & 1) + 4 * (li & 3)) * 2;
   auto frag = [&](const unsigned char* slab, int st, int col0) -> op16x8 {
@@ -175,6 +170,7 @@ __global__ __launch_bounds__(256) void gemm_tt_kernel(GemmTTParams p) {
 // read in one burst (transposed reads, the V^T pattern of attn_glds_kernel<128>: 16-byte chunk c of row k sits at c ^ ((k & 3) << 2),
 // applied on the DMA's source address) and the 16 MFMAs run with the next tile's DMA pieces issued in their shadow.
 // K % 64 == 0 (rows past K cannot be zero-filled by a DMA); columns past M / N re-read chunk 0 of their row (results not stored).
+// (Not one of common.h's DmaImage images: 256-byte k-major rows, swizzled by k & 3 for the TRANSPOSED reads.)
 __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   constexpr int BK = 64, RB = 256, SLAB = BK * RB, STAGE = 2 * SLAB;   // 32 KiB per stage
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE];
@@ -188,8 +184,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   if (kt0 >= kt1) return;
   const bool want_cs = p.a_colsum != nullptr && blockIdx.x == 0;      // (workgroup-uniform)
 
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, 0x7fffffff, 0x00020000);
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto b_rsrc = raw_rsrc(p.B);
   // piece i of this wave: k-rows 4 (4 wave + i) .. +3 of the slab; lane -> (row, LDS chunk slot), source chunk = slot ^ ((row & 3) << 2)
   unsigned offA[4], offB[4];
 #pragma unroll
@@ -202,20 +198,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   auto issue_piece = [&](int kt, int stage, int i) {
     unsigned char* base = lds + stage * STAGE + (4 * wave) * 1024;
     if (i < 4)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offA[i],
-                                               (unsigned)kt * BK * (unsigned)p.lda * 2u, 0, 0);
+      glds16(a_rsrc, base + i * 1024, offA[i], (unsigned)kt * BK * (unsigned)p.lda * 2u);
     else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rsrc, (__attribute__((address_space(3))) void*)(base + SLAB + (i - 4) * 1024), 16, offB[i - 4],
-                                               (unsigned)kt * BK * (unsigned)p.ldb * 2u, 0, 0);
+      glds16(b_rsrc, base + SLAB + (i - 4) * 1024, offB[i - 4], (unsigned)kt * BK * (unsigned)p.ldb * 2u);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
   float cs[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) cs[e] = 0.f;
@@ -239,7 +228,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   for (int i = 0; i < 8; ++i) issue_piece(kt0, 0, i);
   for (int kt = kt0; kt < kt1; ++kt) {
     const int st = (kt - kt0) & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA pieces of tile kt have landed
+    wait_vmcnt<0>();     // this wave's DMA pieces of tile kt have landed
     __builtin_amdgcn_s_barrier();                        // ... and so have every other wave's; stage st^1 is free again
     const unsigned char* sa = lds + st * STAGE;
     const unsigned char* sb = sa + SLAB;

@@ -126,6 +126,78 @@ __device__ __forceinline__ void glds16x3_asm(__amdgpu_buffer_rsrc_t rsrc, const 
 #endif
 }
 
+// ---- building blocks of the MFMA kernels (gemm.hip, attention.hip, attention_bwd.hip, backward.hip, mlp_fused.hip): one definition each ----
+
+// XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (ids congruent mod 8 share an XCD and its private L2): linear
+// workgroup id `id` of a launch of `n` becomes a tile index such that every XCD walks one contiguous slice of the tile space -- the
+// first n % 8 XCDs own n / 8 + 1 tiles, the others n / 8.  A bijection on [0, n) for every n; `n` must be the launch's workgroup count.
+__device__ __forceinline__ int xcd_tile_order(int id, int n) {
+  const int q = n / 8, rem = n % 8, xcd = id % 8;
+  return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + id / 8;
+}
+
+// Raw buffer descriptor over `bytes` bytes at p: stride 0 (raw addressing, offset = voffset + soffset), num_records = bytes -- a lane
+// whose voffset is >= bytes reads 0 / drops its store (soffset is NOT range-checked on gfx9) -- and word 3 = 0x00020000 (DATA_FORMAT 32:
+// the only field a raw gfx9 descriptor needs).  Default: 0x7fffffff, "no bound": the kernel clamps its rows itself.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* p, int bytes = 0x7fffffff) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+
+// The ONLY way a kernel states a vector-memory wait: at most N of this wave's loads / LDS-DMA pieces / stores (one in-order counter) are
+// still in flight afterwards.  Write N as a multiple of the kernel's pieces-per-wave constant where it is one.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int FM, int FN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[FM][FN]) {
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+template <int FN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[FN]) {
+#pragma unroll
+  for (int j = 0; j < FN; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
+}
+
+// LDS image of a K-contiguous operand tile that LDS-DMA fills and ds_read_b128 fragment reads drain: rows of ROW_BYTES (128: 64 k per
+// tile, 64: 32 k), the 16-byte chunk c of row r in slot c ^ swz(r).  swz spreads the rows that share a 256-byte bank row over distinct
+// slots, so every 16-lane ds_read_b128 group of the 32x32x16 operand map (16 rows, one chunk) is conflict free.  The DMA writes LDS
+// linearly (piece base + 16 * lane: lane l fills slot l % CPR of row l / CPR of its 1-KiB piece), so the swizzle is applied to the per-lane
+// SOURCE address.  Both sides go through swz(): they cannot disagree.
+template <int ROW_BYTES_>
+struct DmaImage {
+  static constexpr int ROW_BYTES = ROW_BYTES_;
+  static_assert(ROW_BYTES == 128 || ROW_BYTES == 64, "two images exist: 128-byte rows, slot c ^ ((r >> 1) & 7); 64-byte rows, c ^ ((r >> 2) & 3)");
+  static constexpr int CPR = ROW_BYTES / 16;            // chunks per row
+  static constexpr int PIECE_ROWS = 1024 / ROW_BYTES;   // rows of one DMA piece (one instruction of a wave)
+  __device__ __forceinline__ static int swz(int r) { return (r >> (ROW_BYTES == 128 ? 1 : 2)) & (CPR - 1); }
+  // tile row that `lane` fills in DMA piece `piece` of the tile
+  __device__ __forceinline__ static int piece_row(int piece, int lane) { return piece * PIECE_ROWS + (lane >> (ROW_BYTES == 128 ? 3 : 2)); }
+  // DMA side: the chunk of its global row that `lane` must fetch for tile row r (it lands in slot lane % CPR)
+  __device__ __forceinline__ static int src_chunk(int r, int lane) { return (lane & (CPR - 1)) ^ swz(r); }
+  // fragment side: chunk c of row r is at byte r * ROW_BYTES + ((c ^ swz(r)) << 4) of the image
+};
+typedef DmaImage<128> Img128;
+typedef DmaImage<64> Img64;
+
+// host: raise kernel K's dynamic-LDS limit once per process (per kernel instance); the return code is ignored
+template <auto K>
+static inline void ensure_dyn_lds(int bytes) {
+  static bool done = false;
+  if (!done) {
+    hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = true;
+  }
+}
+
 // exact-erf GELU (nn.GELU default): gelu(x) = x Phi(x), Phi(x) = 0.5 (1 + erf(x / sqrt 2)).
 // Phi(x) - 0.5 is odd: x Q(x^2) with Q a degree-8 polynomial in x^2 (minimax fit of the GELU's own absolute error on |x| <= 4.5, end
 // value pinned so that Phi(+-4.5) = 1 / 0; outside, x is clamped: Phi(-4.5) = 3.4e-6).  |gelu_poly - gelu| <= 5e-5 absolute over all x

@@ -201,11 +201,7 @@ extern "C" int msam2_patch_embed7x7s4(const float* img, const void* w_perm, cons
   const dim3 grid((unsigned)min(n_seg, 1024)), block(256);
 #define PE_LAUNCH(NTV, TOKV) \
   do { \
-    static bool attr_set = false; \
-    if (!attr_set) {     /* (NT = 4, hiera_b+: 69 KB of dynamic LDS) */ \
-      hipFuncSetAttribute((const void*)patch_embed_kernel<NTV, TOKV>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-      attr_set = true; \
-    } \
+    ensure_dyn_lds<patch_embed_kernel<NTV, TOKV>>(80 * 1024);     /* (NT = 4, hiera_b+: 69 KB of dynamic LDS) */ \
     hipLaunchKernelGGL((patch_embed_kernel<NTV, TOKV>), grid, block, lds, (hipStream_t)stream, img, (const op16*)w_perm, bias, pos, out, (int)B, (int)S, (int)E); \
   } while (0)
 #define PE_TOK(NTV) \

@@ -233,8 +233,8 @@ __device__ __forceinline__ void gemm_epilogue_direct(const GemmParams& p, f32x16
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int ES = OUT16 ? 2 : 4;
   const int r = lane & 31, h = lane >> 5, odd = lane & 1;
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)((int64_t)p.M * p.ldc * ES), 0x00020000);
-  const auto r_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res), 0, (int)((int64_t)p.M * p.ldr * 4), 0x00020000);
+  const auto c_rsrc = raw_rsrc(p.C, (int)((int64_t)p.M * p.ldc * ES));
+  const auto r_rsrc = raw_rsrc(p.res, (int)((int64_t)p.M * p.ldr * 4));
   float bias_j[FN], cs_j[FN];
   bool colok[FN];
 #pragma unroll
@@ -408,7 +408,7 @@ template <int FM, int FN>
 __device__ __forceinline__ void gemm_epilogue_pool(const GemmParams& p, f32x16 (&acc)[FM][FN], int64_t row0, int64_t col0, int lane) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int r = lane & 31, h = lane >> 5;
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)(((int64_t)p.M >> 2) * p.ldc * 4), 0x00020000);
+  const auto c_rsrc = raw_rsrc(p.C, (int)(((int64_t)p.M >> 2) * p.ldc * 4));
   const int vbase = (int)(((row0 >> 2) + h) * p.ldc + col0 + r) * 4;
   const int ldc_b = (int)p.ldc * 4;
   float bias_j[FN];                                          // every bias value before the first store (one in-order counter for loads and stores)
@@ -439,8 +439,8 @@ template <int FM, int FN>
 __device__ __forceinline__ void gemm_epilogue_qpool(const GemmParams& p, f32x16 (&acc)[FM][FN], int64_t row0, int64_t col0, int lane) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const int r = lane & 31, h = lane >> 5, odd = lane & 1;
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)((int64_t)p.M * p.ldc * 2), 0x00020000);
-  const auto q_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.Q2, 0, (int)(((int64_t)p.M >> 2) * p.ldq * 2), 0x00020000);
+  const auto c_rsrc = raw_rsrc(p.C, (int)((int64_t)p.M * p.ldc * 2));
+  const auto q_rsrc = raw_rsrc(p.Q2, (int)(((int64_t)p.M >> 2) * p.ldq * 2));
   auto swap = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false)); };
   float bias_j[FN];                                          // every bias value before the first store (one in-order counter for loads and stores)
 #pragma unroll
@@ -571,12 +571,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmParams p) {
   const int64_t n0 = (int64_t)blockIdx.x * BN;
 
   f32x16 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   uint4 ra[A_PER], rw[W_PER];
   const int nk_all = (p.K + GEMM_BK - 1) / GEMM_BK;
@@ -699,9 +694,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmParams p) {
 // ------------------------------------------------------------------------------------------------------------------
 // Large-shape variant: 128x128x64 tiles, operands streamed global -> LDS by LDS-DMA (global_load_lds_dwordx4, no staging
 // registers), 2-stage ring per workgroup and 2 workgroups per CU so that a tile is always in flight behind the MFMA phase.
-// LDS image per operand: [128 rows][64 k] op16 with 128-byte rows; the 16-byte chunk c of row r sits in slot
-// c ^ ((r >> 1) & 7), which makes every ds_read_b128 fragment read (16-lane groups of the 32x32x16 operand map) conflict
-// free.  The DMA writes LDS linearly (wave base + lane*16), so the swizzle is applied to the per-lane SOURCE address.
+// LDS image per operand: [128 rows][64 k] op16 = DmaImage<128> (common.h: 128-byte rows, chunk slots swizzled by the row), which
+// makes every ds_read_b128 fragment read (16-lane groups of the 32x32x16 operand map) conflict free.  The DMA writes LDS
+// linearly (wave base + lane*16), so the swizzle is applied to the per-lane SOURCE address.
 // Requires K % 64 == 0; rows beyond M / N are clamped on load and dropped in the epilogue.
 // ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmParams p) {
@@ -714,72 +709,53 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmParams p) {
   // XCD-aware tile order: workgroups that share an XCD (ids congruent mod 8) walk the N tiles of the same M panel
   const int n_tiles_n = (p.N + BN - 1) / BN, n_tiles_m = (p.M + BM - 1) / BM;
   const int nwg = n_tiles_n * n_tiles_m;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-    bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, nwg);
   const int64_t m0 = (int64_t)(bid / n_tiles_n) * BM;
   const int64_t n0 = (int64_t)(bid % n_tiles_n) * BN;
 
   // this wave's 4 A pieces and 4 W pieces (a piece = 8 rows x 128 B = one DMA instruction): buffer descriptors in SGPRs,
   // loop-invariant 32-bit per-lane byte offsets, scalar k offset -> no 64-bit per-lane pointer arithmetic in the loop
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
   unsigned offsA[4], offsW[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    const int row = Img128::piece_row(wave * 4 + i, lane), chunk = Img128::src_chunk(row, lane);
     const int64_t ga = gemm_a_row(p, min(m0 + row, (int64_t)p.M - 1)), gw = min(n0 + row, (int64_t)p.N - 1);
     offsA[i] = (unsigned)(ga * p.lda * 2 + chunk * 16);
     offsW[i] = (unsigned)(gw * p.ldw * 2 + chunk * 16);
   }
-  auto issue = [&](int kt, int stage) {
+  // one DMA piece of tile kt (i < 4: A piece i, else W piece i-4)
+  auto issue_piece = [&](int kt, int stage, int i) {
     unsigned char* base = lds + stage * STAGE_BYTES + wave * 4096;
     const unsigned so = (unsigned)kt * BK * 2;
+    if (i < 4) glds16(a_rsrc, base + i * 1024, offsA[i], so);
+    else glds16(w_rsrc, base + BM * BK * 2 + (i - 4) * 1024, offsW[i - 4], so);
+  };
+  auto issue = [&](int kt, int stage) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i], so, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + BM * BK * 2 + i * 1024), 16, offsW[i], so, 0, 0);
+    for (int i = 0; i < 8; ++i) issue_piece(kt, stage, i);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   // fragment read offsets (bytes) inside a stage, without the k-substep term
   int offA[2], offB[2], swz[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int ra = wm * 64 + i * 32 + r, rb = wn * 64 + i * 32 + r;
-    offA[i] = ra * 128;
-    offB[i] = BM * BK * 2 + rb * 128;
-    swz[0][i] = (ra >> 1) & 7;
-    swz[1][i] = (rb >> 1) & 7;
+    offA[i] = ra * Img128::ROW_BYTES;
+    offB[i] = BM * BK * 2 + rb * Img128::ROW_BYTES;
+    swz[0][i] = Img128::swz(ra);
+    swz[1][i] = Img128::swz(rb);
   }
 
   const int nk = p.K / BK;
-  // one DMA piece of tile kt (i < 4: A piece i, else W piece i-4)
-  auto issue_piece = [&](int kt, int stage, int i) {
-    unsigned char* base = lds + stage * STAGE_BYTES + wave * 4096;
-    const unsigned so = (unsigned)kt * BK * 2;
-    if (i < 4)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i], so, 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + BM * BK * 2 + (i - 4) * 1024), 16,
-                                               offsW[i - 4], so, 0, 0);
-  };
   issue(0, 0);
   for (int kt = 0; kt < nk; ++kt) {
     const int st = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA pieces of tile kt have landed
+    wait_vmcnt<0>();     // this wave's DMA pieces of tile kt have landed
     __builtin_amdgcn_s_barrier();                        // ... and so have every other wave's; stage st^1 is free again
     const unsigned char* sb = lds + st * STAGE_BYTES;
     // all 16 operand fragments of the tile in one burst (64 VGPRs), then 16 MFMAs with the next tile's DMA pieces issued in
@@ -817,9 +793,10 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(GemmParams p) {
 // per CU, ONE barrier per k-step.  The deeper ring is what hides the L2 -> LDS latency (~1.5-2k cycles under load) that the
 // 2-stage kernel above exposes every step; K only needs to be a multiple of 32, which also brings the K = 96 / 160 layers
 // of Hiera stage 1 onto the DMA path.
-// LDS image per operand: [128 rows][32 k] op16 = 64-byte rows; chunk c (0..3) of row r sits in slot c ^ ((r >> 2) & 3):
+// LDS image per operand: [128 rows][32 k] op16 = DmaImage<64> (common.h: 64-byte rows, chunk c (0..3) of row r in slot c ^ swz(r)):
 // every 16-lane ds_read_b128 group of the 32x32x16 operand map then covers 16 distinct (row mod 4, slot) positions of the
-// 256-byte bank rows it touches (conflict free).
+// 256-byte bank rows it touches (conflict free).  This kernel and gemm_wide_kernel WRITE THE IMAGE'S FORMULAS OUT (source chunk and
+// fragment offset, `(row >> 2) & 3` twice): through the helper the compiler shares a shift between the two sides and the listing changes.
 // ------------------------------------------------------------------------------------------------------------------
 template <int NST, int OCC>
 __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
@@ -833,17 +810,13 @@ __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
   const int r = lane & 31, h = lane >> 5;
   const int n_tiles_n = (p.N + BN - 1) / BN, n_tiles_m = (p.M + BM - 1) / BM;
   const int nwg = n_tiles_n * n_tiles_m;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-    bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, nwg);
   const int64_t m0 = (int64_t)(bid / n_tiles_n) * BM;
   const int64_t n0 = (int64_t)(bid % n_tiles_n) * BN;
 
   // a DMA piece = 16 rows x 64 B; the A tile has 8 pieces, so has the W tile: 2 + 2 per wave
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
   unsigned offsA[2], offsW[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -858,19 +831,14 @@ __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
     const unsigned so = (unsigned)kt * BK * 2;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i], so, 0, 0);
+      glds16(a_rsrc, base + i * 1024, offsA[i], so);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + BM * BK * 2 + i * 1024), 16, offsW[i], so, 0, 0);
+      glds16(w_rsrc, base + BM * BK * 2 + i * 1024, offsW[i], so);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   int offA[2], offB[2], swz[2][2];
 #pragma unroll
@@ -878,8 +846,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
     const int ra = wm * 64 + i * 32 + r, rb = wn * 64 + i * 32 + r;
     offA[i] = ra * 64;
     offB[i] = BM * BK * 2 + rb * 64;
-    swz[0][i] = (ra >> 2) & 3;
-    swz[1][i] = (rb >> 2) & 3;
+    swz[0][i] = ((ra >> 2) & 3);
+    swz[1][i] = ((rb >> 2) & 3);
   }
 
   const int nk = p.K / BK;
@@ -892,6 +860,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
     if (kt == 1) GSTAMP(1);
 #endif
     const int ahead = min(nk - 1 - kt, NST - 2);         // DMA groups younger than tile kt still allowed in flight
+    // 2 x 4 / 1 x 4 pieces per wave and tile.  The one place that does not go through wait_vmcnt<N> (common.h): three asm statements
+    // with the same text and different operands are merged differently from three different texts, and this kernel's listing changes
     if (ahead >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -933,13 +903,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_glds32_kernel(GemmParams p) {
 // Why: what bounds the 128x128 kernels is bytes in flight -- at 64 flop per DMA byte a CU needs ~64 B/clk from L2, i.e. more
 // than 100 KiB in flight to cover the ~2k-cycle L2->LDS latency.  A 256x128 tile needs 1.33x fewer bytes per flop, twice the
 // MFMA work per barrier, and with 3 stages keeps two tiles in flight per workgroup (2 workgroups per CU: 144 KiB of LDS).
-// Same 64-byte-row image and chunk swizzle (c ^ ((r >> 2) & 3)) as gemm_glds32_kernel.
+// Same 64-byte-row image (DmaImage<64>, formulas written out) as gemm_glds32_kernel.
 // ------------------------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int BM, int BN, int NST, int OCC>
 __global__ __launch_bounds__(256, OCC) void gemm_wide_kernel(GemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -956,16 +921,12 @@ __global__ __launch_bounds__(256, OCC) void gemm_wide_kernel(GemmParams p) {
   const int r = lane & 31, h = lane >> 5;
   const int n_tiles_n = (p.N + BN - 1) / BN, n_tiles_m = (p.M + BM - 1) / BM;
   const int nwg = n_tiles_n * n_tiles_m;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-    bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, nwg);
   const int64_t m0 = (int64_t)(bid / n_tiles_n) * BM;
   const int64_t n0 = (int64_t)(bid % n_tiles_n) * BN;
 
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
   unsigned offsA[PA], offsW[PWW];
 #pragma unroll
   for (int i = 0; i < PA; ++i) {
@@ -984,15 +945,14 @@ __global__ __launch_bounds__(256, OCC) void gemm_wide_kernel(GemmParams p) {
     const unsigned so = (unsigned)kt * BK * 2;
 #pragma unroll
     for (int i = 0; i < PA; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + (wave * PA + i) * 1024), 16,
-                                               offsA[i], so, 0, 0);
+      glds16(a_rsrc, base + (wave * PA + i) * 1024, offsA[i], so);
 #pragma unroll
     for (int i = 0; i < PWW; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + A_BYTES + (wave * PWW + i) * 1024),
-                                               16, offsW[i], so, 0, 0);
+      glds16(w_rsrc, base + A_BYTES + (wave * PWW + i) * 1024, offsW[i], so);
   };
 
   f32x16 acc[FM][FN];
+  // (not zero_acc: through the helper this kernel's accumulators get other registers)
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -1080,23 +1040,19 @@ __global__ __launch_bounds__(256, OCC) void gemm_wide_kernel(GemmParams p) {
 // One workgroup (4 waves, one per SIMD) per CU: 160 KB of LDS at K = 384.  Requires M % 128 == 0, N % 128 == 0, 16-bit output,
 // no residual / column scale / RoPE / pooling; grid = groups x panels <= 256.
 // ------------------------------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void wstat_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void wstat_wait_dyn(int n) {      // n: multiple of 4, 0..40 (wave-uniform)
   switch (n >> 2) {
-    case 0: wstat_wait<0>(); break;
-    case 1: wstat_wait<4>(); break;
-    case 2: wstat_wait<8>(); break;
-    case 3: wstat_wait<12>(); break;
-    case 4: wstat_wait<16>(); break;
-    case 5: wstat_wait<20>(); break;
-    case 6: wstat_wait<24>(); break;
-    case 7: wstat_wait<28>(); break;
-    case 8: wstat_wait<32>(); break;
-    case 9: wstat_wait<36>(); break;
-    default: wstat_wait<40>(); break;
+    case 0: wait_vmcnt<0>(); break;
+    case 1: wait_vmcnt<4>(); break;
+    case 2: wait_vmcnt<8>(); break;
+    case 3: wait_vmcnt<12>(); break;
+    case 4: wait_vmcnt<16>(); break;
+    case 5: wait_vmcnt<20>(); break;
+    case 6: wait_vmcnt<24>(); break;
+    case 7: wait_vmcnt<28>(); break;
+    case 8: wait_vmcnt<32>(); break;
+    case 9: wait_vmcnt<36>(); break;
+    default: wait_vmcnt<40>(); break;
   }
 }
 
@@ -1137,9 +1093,10 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
   const int64_t n0 = (int64_t)panel * BN;
   const int total = my_tiles * NK;
 
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
-  // a piece = 8 rows x 128 B = one DMA instruction; 128-byte-row image, chunk c of row r in slot c ^ ((r >> 1) & 7) (as gemm_glds_kernel)
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
+  // a piece = 8 rows x 128 B = one DMA instruction; the 128-byte-row image of gemm_glds_kernel (DmaImage<128>, common.h) with its formulas
+  // WRITTEN OUT, here and at the fragment reads: through the helper this kernel's listing changes (register allocation)
   unsigned offsA[LPC], offsW[LPC];
 #pragma unroll
   for (int i = 0; i < LPC; ++i) {
@@ -1155,7 +1112,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
     unsigned char* base = ring + (g & (NST - 1)) * KT_BYTES + wave * (LPC * 1024);
 #pragma unroll
     for (int i = 0; i < LPC; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i], so, 0, 0);
+      glds16(a_rsrc, base + i * 1024, offsA[i], so);
   };
   // this workgroup's columns never change: bias once, BEFORE any DMA is in flight (the compiler waits for these loads with vmcnt(0))
   float bias_j[2];
@@ -1170,8 +1127,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
   for (int kt = 0; kt < NK; ++kt)
 #pragma unroll
     for (int i = 0; i < LPC; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(lds + kt * KT_BYTES + (wave * LPC + i) * 1024), 16,
-                                               offsW[i], (unsigned)kt * BK * 2, 0, 0);
+      glds16(w_rsrc, lds + kt * KT_BYTES + (wave * LPC + i) * 1024, offsW[i], (unsigned)kt * BK * 2);
 #pragma unroll
   for (int g = 0; g < (APF ? NST : NST - 1); ++g)
     if (g < total) issue_a(g);
@@ -1186,7 +1142,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
     offB[j] = rb * 128;
     swzB[j] = (rb >> 1) & 7;
   }
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)((int64_t)p.M * p.ldc * 2), 0x00020000);
+  const auto c_rsrc = raw_rsrc(p.C, (int)((int64_t)p.M * p.ldc * 2));
   const int ldc_b = (int)p.ldc * 2;
   const int vcol = (int)(n0 + wn * 64 + (r & ~1)) * 2;
 
@@ -1234,10 +1190,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
   op16x8 bfr[2][4][2];                                // double buffer: chunk kt uses [kt & 1] (NK is even), loads [(kt + 1) & 1]
   static_assert(NK % 2 == 0, "the W-fragment double buffer alternates with the chunk index");
   auto tile = [&](f32x16 (&cur)[2], f32x16 (&prev)[2], int ti, bool has_prev, int prev_row0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) cur[j][e] = 0.f;
+    zero_acc(cur);
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
       const int g = ti * NK + kt;
@@ -1252,17 +1205,17 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
       if constexpr (!APF) {
         const int rem = total - 1 - g;
         if (rem >= 2) {
-          if (st == 0) wstat_wait<2 * LPC>();
-          else if (st == SPR) wstat_wait<2 * LPC + SPR>();
-          else wstat_wait<2 * LPC + 2 * SPR>();
+          if (st == 0) wait_vmcnt<2 * LPC>();
+          else if (st == SPR) wait_vmcnt<2 * LPC + SPR>();
+          else wait_vmcnt<2 * LPC + 2 * SPR>();
         } else if (rem == 1) {
-          if (st == 0) wstat_wait<LPC>();
-          else if (st == SPR) wstat_wait<LPC + SPR>();
-          else wstat_wait<LPC + 2 * SPR>();
+          if (st == 0) wait_vmcnt<LPC>();
+          else if (st == SPR) wait_vmcnt<LPC + SPR>();
+          else wait_vmcnt<LPC + 2 * SPR>();
         } else {
-          if (st == 0) wstat_wait<0>();
-          else if (st == SPR) wstat_wait<SPR>();
-          else wstat_wait<2 * SPR>();
+          if (st == 0) wait_vmcnt<0>();
+          else if (st == SPR) wait_vmcnt<SPR>();
+          else wait_vmcnt<2 * SPR>();
         }
         __builtin_amdgcn_s_barrier();                   // chunk g is complete for every wave; stage (g-1) % NST is free again
         if (g + NST - 1 < total) issue_a(g + NST - 1);
@@ -1284,17 +1237,17 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
         if (g + 1 < total) {
           const int rem = total - 2 - g;                // chunks issued beyond g+1 (at most g+2, g+3)
           if (rem >= 2) {
-            if (st == 0) wstat_wait<2 * LPC>();
-            else if (st == SPR) wstat_wait<2 * LPC + SPR>();
-            else wstat_wait<2 * LPC + 2 * SPR>();
+            if (st == 0) wait_vmcnt<2 * LPC>();
+            else if (st == SPR) wait_vmcnt<2 * LPC + SPR>();
+            else wait_vmcnt<2 * LPC + 2 * SPR>();
           } else if (rem == 1) {
-            if (st == 0) wstat_wait<LPC>();
-            else if (st == SPR) wstat_wait<LPC + SPR>();
-            else wstat_wait<LPC + 2 * SPR>();
+            if (st == 0) wait_vmcnt<LPC>();
+            else if (st == SPR) wait_vmcnt<LPC + SPR>();
+            else wait_vmcnt<LPC + 2 * SPR>();
           } else {
-            if (st == 0) wstat_wait<0>();
-            else if (st == SPR) wstat_wait<SPR>();
-            else wstat_wait<2 * SPR>();
+            if (st == 0) wait_vmcnt<0>();
+            else if (st == SPR) wait_vmcnt<SPR>();
+            else wait_vmcnt<2 * SPR>();
           }
         }
         __builtin_amdgcn_s_barrier();
@@ -1340,11 +1293,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat_kernel(GemmParams p, int n_
 template <int NK, int ACT, bool NT, bool APF>
 static void launch_wstat(const GemmParams& p, int n_panels, int groups, hipStream_t s) {
   constexpr int LDS = (NK + 4) * 128 * 64 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_wstat_kernel<NK, ACT, NT, APF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  ensure_dyn_lds<gemm_wstat_kernel<NK, ACT, NT, APF>>(LDS);
   hipLaunchKernelGGL((gemm_wstat_kernel<NK, ACT, NT, APF>), dim3(256), dim3(512), LDS, s, p, n_panels, groups);
 }
 
@@ -1438,20 +1387,18 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat256_kernel(GemmParams p, int
     return (grp + u * groups) * 128;
   };
 
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
-  // a piece = 8 rows x 128 B = one DMA instruction; 128-byte-row images, chunk c of row r in slot c ^ ((r >> 1) & 7) (as gemm_glds_kernel)
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
+  // a piece = 8 rows x 128 B = one DMA instruction; the 128-byte-row image of gemm_glds_kernel (Img128, common.h)
   unsigned offsA[LPA], offsW[2];
 #pragma unroll
   for (int i = 0; i < LPA; ++i) {
-    const int row = ((wave & 3) * LPA + i) * 8 + (lane >> 3);            // row inside this wave's unit (0..127)
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    const int row = Img128::piece_row((wave & 3) * LPA + i, lane), chunk = Img128::src_chunk(row, lane);            // row inside this wave's unit (0..127)
     offsA[i] = (unsigned)((int64_t)row * p.lda * 2 + chunk * 16);
   }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int row = (wave * 2 + i) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    const int row = Img128::piece_row(wave * 2 + i, lane), chunk = Img128::src_chunk(row, lane);
     offsW[i] = (unsigned)((n0 + row) * p.ldw * 2 + chunk * 16);
   }
   unsigned char* const ring = lds + W_BYTES;
@@ -1461,7 +1408,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat256_kernel(GemmParams p, int
     unsigned char* base = ring + (s % NST) * A_STAGE + wave * (LPA * 1024);   // stage rows wave * 32 ..: unit a = rows 0..127, b = 128..255
 #pragma unroll
     for (int i = 0; i < LPA; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i], so, 0, 0);
+      glds16(a_rsrc, base + i * 1024, offsA[i], so);
   };
   float bias_j[2];
 #pragma unroll
@@ -1472,8 +1419,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat256_kernel(GemmParams p, int
   for (int kt = 0; kt < NK; ++kt)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(lds + kt * KT_BYTES + (wave * 2 + i) * 1024), 16,
-                                               offsW[i], (unsigned)kt * BK * 2, 0, 0);
+      glds16(w_rsrc, lds + kt * KT_BYTES + (wave * 2 + i) * 1024, offsW[i], (unsigned)kt * BK * 2);
 #pragma unroll
   for (int s = 0; s < NST - 1; ++s)
     if (s < total) issue_a(s);
@@ -1482,12 +1428,12 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat256_kernel(GemmParams p, int
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int ra = wm * 64 + i * 32 + r, rb = wn * 64 + i * 32 + r;
-    offA[i] = ra * 128;
-    swzA[i] = (ra >> 1) & 7;
-    offB[i] = rb * 128;
-    swzB[i] = (rb >> 1) & 7;
+    offA[i] = ra * Img128::ROW_BYTES;
+    swzA[i] = Img128::swz(ra);
+    offB[i] = rb * Img128::ROW_BYTES;
+    swzB[i] = Img128::swz(rb);
   }
-  const auto c_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)((int64_t)p.M * p.ldc * 2), 0x00020000);
+  const auto c_rsrc = raw_rsrc(p.C, (int)((int64_t)p.M * p.ldc * 2));
   const int ldc_b = (int)p.ldc * 2;
   const int vcol = (int)(n0 + wn * 64 + (r & ~1)) * 2;
   unsigned sink = 0;
@@ -1522,12 +1468,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wstat256_kernel(GemmParams p, int
 #pragma unroll
     for (int e = 0; e < 8; ++e) keep_a[i][e] = keep_b[i][e] = (op16)0.f;
   auto tile = [&](f32x16 (&cur)[2][2], f32x16 (&prev)[2][2], int pair, int prev_row0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) cur[i][j][e] = 0.f;
+    zero_acc(cur);
 #pragma unroll
     for (int kt = 0; kt < NK; ++kt) {
       const int s = pair * NK + kt;
@@ -1592,11 +1533,7 @@ static void launch_wstat256(const GemmParams& p, int n_panels, int groups, hipSt
   constexpr int W_BYTES = NK * 128 * 64 * 2;
   constexpr int NST = (160 * 1024 - W_BYTES) / (32 * 1024) >= 3 ? 3 : 2;
   constexpr int LDS = W_BYTES + NST * 32 * 1024;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_wstat256_kernel<NK, ACT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  ensure_dyn_lds<gemm_wstat256_kernel<NK, ACT, NT>>(LDS);
   hipLaunchKernelGGL((gemm_wstat256_kernel<NK, ACT, NT>), dim3(256), dim3(512), LDS, s, p, n_panels, groups);
 }
 
@@ -1876,22 +1813,17 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   const int r = lane & 31, h = lane >> 5, li = lane & 15;
   const int n_tiles_n = (p.N + BN - 1) / BN, n_tiles_m = (p.M + BM - 1) / BM;
   const int nwg = n_tiles_n * n_tiles_m;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg / 8, rem = nwg % 8, xcd = bid % 8;
-    bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + bid / 8;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, nwg);
   const int64_t m0 = (int64_t)(bid / n_tiles_n) * BM;
   const int n0 = (bid % n_tiles_n) * BN;
 
-  const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, 0x7fffffff, 0x00020000);
-  const auto w_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, 0x7fffffff, 0x00020000);
+  const auto a_rsrc = raw_rsrc(p.A);
+  const auto w_rsrc = raw_rsrc(p.W);
   // A: 4 pieces per wave of 8 rows x 128 B (as gemm_glds_kernel); B: 4 pieces per wave of 4 k-rows x 256 B (as gemm_tt_dma_kernel)
   unsigned offsA[4], offsW[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
+    const int row = Img128::piece_row(wave * 4 + i, lane), chunk = Img128::src_chunk(row, lane);
     offsA[i] = (unsigned)(min(m0 + row, (int64_t)p.M - 1) * p.lda * 2 + chunk * 16);
     const int krow = 4 * (4 * wave + i) + (lane >> 4);
     const int col = ((lane & 15) ^ ((krow & 3) << 2)) * 8;
@@ -1900,27 +1832,20 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   auto issue_piece = [&](int kt, int stage, int i) {
     unsigned char* base = lds + stage * STAGE_BYTES + wave * 4096;
     if (i < 4)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rsrc, (__attribute__((address_space(3))) void*)(base + i * 1024), 16, offsA[i],
-                                               (unsigned)kt * BK * 2, 0, 0);
+      glds16(a_rsrc, base + i * 1024, offsA[i], (unsigned)kt * BK * 2);
     else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(base + A_BYTES + (i - 4) * 1024), 16, offsW[i - 4],
-                                               (unsigned)kt * BK * (unsigned)p.ldw * 2u, 0, 0);
+      glds16(w_rsrc, base + A_BYTES + (i - 4) * 1024, offsW[i - 4], (unsigned)kt * BK * (unsigned)p.ldw * 2u);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  zero_acc(acc);
 
   int offA[2], swzA[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int ra = wm * 64 + i * 32 + r;
-    offA[i] = ra * 128;
-    swzA[i] = (ra >> 1) & 7;
+    offA[i] = ra * Img128::ROW_BYTES;
+    swzA[i] = Img128::swz(ra);
   }
   // transposed fragment of column block cb (32 columns) x k-step ks (16 rows) of the slab: lane 4 q + p of a 16-lane group addresses row
   // q of the block, columns 4 p .. 4 p + 3; the group of lanes (16 cgrp .. +15) of half h takes rows 8 h + q (elements 0..3) and
@@ -1944,7 +1869,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   for (int i = 0; i < 8; ++i) issue_piece(0, 0, i);
   for (int kt = 0; kt < nk; ++kt) {
     const int st = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's DMA pieces of tile kt have landed
+    wait_vmcnt<0>();     // this wave's DMA pieces of tile kt have landed
     __builtin_amdgcn_s_barrier();                        // ... and so have every other wave's; stage st^1 is free again
     const unsigned char* sa = lds + st * STAGE_BYTES;
     const unsigned char* sb = sa + A_BYTES;

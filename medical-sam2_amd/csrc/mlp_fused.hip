@@ -18,7 +18,8 @@
 //   * LayerNorm runs on the lane's half row (the other half sits 32 lanes away: one cross-half add), the residual is added in the
 //     store.
 // LDS images: rows of 192 B use chunk' = (c & ~3) | ((c & 3) ^ ((r >> 2) & 3)), rows of 384 B chunk' = (c & ~7) | ((c & 7) ^ ((r >> 1) & 7))
-// (both conflict free for the 32-row ds_read_b128 fragment reads); applied on the DMA source address and on the reads.
+// (both conflict free for the 32-row ds_read_b128 fragment reads); applied on the DMA source address and on the reads.  Not the images of
+// common.h's DmaImage: a row is 12 / 24 chunks long and the swizzle permutes inside groups of 4 / 8 of them.
 #include "common.h"
 
 struct MlpFusedParams {
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
   for (int i = tid; i < HID; i += NWV * 64) prm[3 * DIM + i] = p.b1[i];
 
   // ---- weight stream: per-lane source offsets of this wave's DMA pieces (chunk-independent part), scalar chunk offset added per issue
-  const auto w1_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, HID * DIM * 2, 0x00020000);
-  const auto w2_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2p, 0, HID * DIM * 2, 0x00020000);
+  const auto w1_rsrc = raw_rsrc(p.w1, HID * DIM * 2);
+  const auto w2_rsrc = raw_rsrc(p.w2p, HID * DIM * 2);
   unsigned off1[PW1], off2[PW2];
 #pragma unroll
   for (int j = 0; j < PW1; ++j) {
@@ -85,11 +86,11 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
 #pragma unroll
     for (int j = 0; j < PW1; ++j)
       if (j * NWV + wave < PIECES1)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w1_rsrc, (__attribute__((address_space(3))) void*)(d1 + (j * NWV + wave) * 1024), 16, off1[j], s1, 0, 0);
+        glds16(w1_rsrc, d1 + (j * NWV + wave) * 1024, off1[j], s1);
 #pragma unroll
     for (int j = 0; j < PW2; ++j)
       if (j * NWV + wave < PIECES2)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w2_rsrc, (__attribute__((address_space(3))) void*)(d2 + (j * NWV + wave) * 1024), 16, off2[j], s2, 0, 0);
+        glds16(w2_rsrc, d2 + (j * NWV + wave) * 1024, off2[j], s2);
   };
 
   const int64_t pass_tokens = NWV * 32 * TB;
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
     issue(0, 0);
     if constexpr (RESIDENT) issue(1, 1);
   }
-  if constexpr (RESIDENT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (RESIDENT) wait_vmcnt<0>();
   __syncthreads();                                           // parameters visible (streaming form: the DMA is waited for inside the loop)
 
   for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
     for (int chunk = 0; chunk < NCH; ++chunk, ++g_chunk) {
       const int buf = RESIDENT ? chunk : (int)(g_chunk & 1);
       if constexpr (!RESIDENT) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of the chunk have landed
+        wait_vmcnt<0>();     // this wave's pieces of the chunk have landed
         __builtin_amdgcn_s_barrier();                        // ... every wave's; the other buffer is no longer read
         const bool more_here = chunk + 1 < NCH;
         const bool more = more_here || (pass + gridDim.x < n_pass);
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
 //     LDS-DMA ring, two chunks (96 KB) in flight, one barrier per chunk;
 //   * W2 is given chunk-major and already in its LDS image (msam2_mlp_fused_permute_w2 at dim 384): its DMA is a linear 24 KB copy of whole
 //     128-byte lines (as [384][1536] rows a chunk would be 384 pieces of 64 bytes).
-// LDS images: W1 rows of 768 B, 16-byte chunk c of row r at (c & ~15) | ((c & 15) ^ (r & 15)); W2 rows of 64 B, chunk c at c ^ ((r >> 2) & 3)
+// LDS images: W1 rows of 768 B, 16-byte chunk c of row r at (c & ~15) | ((c & 15) ^ (r & 15)); W2 rows of 64 B = DmaImage<64> (common.h)
 // (both conflict free for the 16-lane groups of a 32-row ds_read_b128 fragment read).
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int mlp_swz768(int c, int r) { return (c & ~15) | ((c & 15) ^ (r & 15)); }
@@ -311,8 +312,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
     for (int q = 0; q < 2; ++q) v[k][q] = *reinterpret_cast<const f32x4*>(xr + 16 * k + 8 * h + 4 * q);
 
   // ---- weight stream
-  const auto w1_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w1, 0, HID * DIM * 2, 0x00020000);
-  const auto w2_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.w2p, 0, HID * DIM * 2, 0x00020000);
+  const auto w1_rsrc = raw_rsrc(p.w1, HID * DIM * 2);
+  const auto w2_rsrc = raw_rsrc(p.w2p, HID * DIM * 2);
   unsigned off1[PW];
 #pragma unroll
   for (int j = 0; j < PW; ++j) {
@@ -329,13 +330,13 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
       const unsigned s = (unsigned)i * W1B;
 #pragma unroll
       for (int j = 0; j < PW; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w1_rsrc, (__attribute__((address_space(3))) void*)(d1 + (j * 4 + wave) * 1024), 16, off1[j], s, 0, 0);
+        glds16(w1_rsrc, d1 + (j * 4 + wave) * 1024, off1[j], s);
     }
     if (i >= 1) {
       const unsigned s = (unsigned)(i - 1) * W2B;
 #pragma unroll
       for (int j = 0; j < PW; ++j)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(w2_rsrc, (__attribute__((address_space(3))) void*)(d2 + (j * 4 + wave) * 1024), 16, off2, s + j * 4096, 0, 0);
+        glds16(w2_rsrc, d2 + (j * 4 + wave) * 1024, off2, s + j * 4096);
     }
   };
   issue(0);
@@ -478,7 +479,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
     for (int d = 0; d < DBW; ++d) {
       const int row2 = (dh * DBW + d) * 32 + r;
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) a2[d][s2] = *reinterpret_cast<const op16x8*>(w2s + row2 * 64 + (((2 * s2 + h) ^ ((row2 >> 2) & 3)) << 4));
+      for (int s2 = 0; s2 < 2; ++s2) a2[d][s2] = *reinterpret_cast<const op16x8*>(w2s + row2 * Img64::ROW_BYTES + (((2 * s2 + h) ^ Img64::swz(row2)) << 4));
     }
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)                           // s2 outer: six independent accumulators between the two MFMAs of an output block
@@ -488,7 +489,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
 
   f32x16 acur;
   // step 0: W1 chunk 0 only
-  asm volatile("s_waitcnt vmcnt(12)" ::: "memory");          // step 1's 12 pieces may still be in flight
+  wait_vmcnt<12>();          // step 1's 12 pieces may still be in flight
   __builtin_amdgcn_s_barrier();
   issue(2);
   {
@@ -498,8 +499,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
 #pragma unroll 1
   for (int i = 1; i < NCH; ++i) {
     // this wave's pieces of step i have landed (step i + 1's 12 -- 6 for the last step -- may still be in flight) ...
-    if (i + 1 < NCH) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    if (i + 1 < NCH) wait_vmcnt<12>();
+    else wait_vmcnt<6>();
     __builtin_amdgcn_s_barrier();                            // ... every wave's; the slot of step i - 1 is no longer read
     if (i + 2 <= NCH) issue(i + 2);
     const unsigned char* w1s = smem + (i % NST) * BUF;
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused384_kernel(MlpFusedParams p) 
     acur = anext;
   }
   {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     op16x8 hf[2];
     gelu16(acur, hf);
@@ -557,7 +558,7 @@ __global__ void mlp_fused384_pack_kernel(const op16* __restrict__ w2, op16* __re
   const int64_t total = (int64_t)dim * hid;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int chunk = (int)(i / ((int64_t)dim * 32)), d = (int)((i / 32) % dim), q = (int)(i & 31);
-    const int c = (q >> 3) ^ ((d >> 2) & 3), j = q & 7, pos = c * 8 + j;
+    const int c = (q >> 3) ^ Img64::swz(d), j = q & 7, pos = c * 8 + j;
     const int s = pos >> 4, hh = (pos >> 3) & 1;
     w2q[i] = w2[(int64_t)d * hid + chunk * 32 + 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3)];
   }
@@ -596,11 +597,7 @@ extern "C" int msam2_ln_mlp_residual_supported(int64_t dim) {
 
 static int launch_mlp_fused384(const MlpFusedParams& p, hipStream_t s) {
   constexpr int LDS = 3 * 49152 + (3 * 384 + 1536) * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)mlp_fused384_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  ensure_dyn_lds<mlp_fused384_kernel>(LDS);
   hipLaunchKernelGGL(mlp_fused384_kernel, dim3((unsigned)((p.T + 63) / 64)), dim3(256), LDS, s, p);
   return msam2_check_launch("ln_mlp_residual_fwd(384)");
 }
@@ -608,11 +605,7 @@ static int launch_mlp_fused384(const MlpFusedParams& p, hipStream_t s) {
 template <int DIM, int HC, int TB, int OCC = 1, int NWV = 4>
 static int launch_mlp_fused(const MlpFusedParams& p, hipStream_t s) {
   constexpr int LDS = 2 * (2 * HC * DIM * 2) + (3 * DIM + 4 * DIM) * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)mlp_fused_kernel<DIM, HC, TB, OCC, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  ensure_dyn_lds<mlp_fused_kernel<DIM, HC, TB, OCC, NWV>>(LDS);
   const int64_t n_pass = (p.T + NWV * 32 * TB - 1) / (NWV * 32 * TB);
   hipLaunchKernelGGL((mlp_fused_kernel<DIM, HC, TB, OCC, NWV>), dim3((unsigned)min((int64_t)256 * OCC, n_pass)), dim3(NWV * 64), LDS, s, p);
   return msam2_check_launch("ln_mlp_residual_fwd");

@@ -1,0 +1,80 @@
+"""Is the device code of two source trees the same?  (CPU only.)  Compiles every csrc/*.hip of both trees with the Makefile's flags plus
+`-S --cuda-device-only`, normalises the listings (comments, .file / .loc / .ident, debug sections and the per-translation-unit
+__hip_cuid_<hash> symbol dropped) and compares them line for line: every instruction, every .amdhsa_ field, the set of kernel symbols.
+A listing is kept beside its source (isa/ or isa_bf16/, ignored by git) and reused while no source or header is newer.
+usage: python tools/isa_diff.py <parent-tree> <new-tree> [--bf16]   ->  per source file `identical` or the first differing kernel."""
+import os
+import re
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_scan import kernels  # noqa: E402
+
+CSRC = os.path.join("medical-sam2_amd", "csrc")
+
+
+def make_var(makefile, name):
+    return re.search(rf"^{name}\s*[:?]?=\s*(.*)$", makefile, re.M).group(1).strip()
+
+
+def listing(tree, src, bf16):
+    """Path of the ISA listing of `src` in `tree`, compiled if stale."""
+    csrc = os.path.join(tree, CSRC)
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    extra = "-DMSAM2_OPERAND_BF16" if bf16 else ""
+    flags = make_var(mk, "FLAGS").replace("$(ARCH)", make_var(mk, "ARCH")).replace("$(EXTRA)", extra).split()
+    out = os.path.join(csrc, "isa_bf16" if bf16 else "isa", src[:-4] + ".s")
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if f == src or f.endswith(".h") or f == "Makefile"]
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call([make_var(mk, "HIPCC")] + flags + ["-S", "--cuda-device-only", "-o", out, src], cwd=csrc,
+                              stderr=subprocess.DEVNULL)
+    return out
+
+
+def normalised(path):
+    keep, debug = [], False
+    for line in open(path):
+        line = re.sub(r"\s*;.*$", "", line.rstrip())
+        s = line.strip()
+        if s.startswith(".section"):
+            debug = ".debug" in s
+        if debug or not s or s.startswith(("//", ".file", ".loc", ".ident")) or "__hip_cuid_" in s:
+            continue
+        keep.append(line)
+    return "\n".join(keep) + "\n"
+
+
+def compare(a, b):
+    if a == b:
+        return "identical (%d lines)" % a.count("\n")
+    ka, kb = (dict(kernels(re.sub(r"^(_Z\w+):$", r"\1: ", t, flags=re.M))) for t in (a, b))
+    if set(ka) != set(kb):
+        return "kernel symbols differ: only in parent %s, only in new %s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))
+    for name in ka:
+        if ka[name] != kb[name]:
+            n = next((i for i, (x, y) in enumerate(zip(ka[name], kb[name])) if x != y), min(len(ka[name]), len(kb[name])))
+            return "DIFFERS: %s at its line %d (%d / %d lines)" % (name, n, len(ka[name]), len(kb[name]))
+    return "DIFFERS outside the kernel bodies (metadata or .amdhsa_ fields)"
+
+
+def main():
+    args = [a for a in sys.argv[1:] if a != "--bf16"]
+    bf16 = "--bf16" in sys.argv
+    if len(args) != 2:
+        sys.exit(__doc__)
+    srcs = sorted(f for f in os.listdir(os.path.join(args[1], CSRC)) if f.endswith(".hip"))
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
+        jobs = {(t, s): pool.submit(listing, t, s, bf16) for s in srcs for t in dict.fromkeys(args)}
+        bad = 0
+        for s in srcs:
+            verdict = compare(normalised(jobs[args[0], s].result()), normalised(jobs[args[1], s].result()))
+            bad += not verdict.startswith("identical")
+            print("%-20s %s" % (s, verdict), flush=True)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
