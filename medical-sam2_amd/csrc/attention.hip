@@ -892,7 +892,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
     g_stamp[15] = __builtin_amdgcn_s_memtime() - ct0_;          // shader cycles over the loop
   }
 #endif
-  if (t_full_end < t_end) {
+  // (t_begin < t_end: a trailing split that a device-side key count left empty has t_end = tiles_total < t_begin and must not take the
+  //  partial tile of the last live split a second time)
+  if (t_begin < t_end && t_full_end < t_end) {
     // partial last tile: rows past Lk re-read the last valid key (their scores are masked to -inf)
     const int key0 = t_full_end * BK, last = Lk - 1 - key0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -231,9 +231,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, splits: int 
 
 def attention_kv64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, splits: int = 1, scale: Optional[float] = None,
                    workspace: Optional[torch.Tensor] = None, defer_merge: bool = False,
-                   key_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   key_count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(q k^T / sqrt(256)) v for q [B,H,Lq,256], k [B,H,Lk,256] and 64-wide value rows v [B,H,Lk,64] (the memory bank itself:
-    the memory cross-attention with v_proj folded into out_proj).  Returns the [B,H,Lq,64] view of a [B,Lq,H,64] buffer.
+    the memory cross-attention with v_proj folded into out_proj).  Returns the [B,H,Lq,64] view of a [B,Lq,H,64] buffer (or `out`, a
+    [B,H,Lq,64] view with contiguous rows).
     defer_merge: the split pass only (finish with attention_merge on the returned view).
     key_count: int32 device scalar in [1, Lk]: only the first `key_count` keys are attended to, Lk being the capacity the launch is
     shaped for (a hipGraph captured for a padded memory bank serves every fill level)."""
@@ -244,7 +245,9 @@ def attention_kv64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, splits:
          "attention_kv64: key_count is one int32 on the tensors' device")
     for t in (q, k, v):
         _req(t.dtype == OP16 and t.stride(3) == 1, "attention tensors must be 16-bit (ops.OP16) with contiguous head dim")
-    out = torch.empty(B, Lq, H, 64, dtype=OP16, device=q.device).permute(0, 2, 1, 3)
+    if out is None:
+        out = torch.empty(B, Lq, H, 64, dtype=OP16, device=q.device).permute(0, 2, 1, 3)
+    _req(out.dtype == OP16 and out.shape == (B, H, Lq, 64) and out.stride(3) == 1, "attention_kv64: out is a 16-bit [B,H,Lq,64] view")
     ws_bytes = lib().msam2_attention_workspace_bytes(B, H, Lq, 64, splits)
     ws = workspace if workspace is not None else (torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=q.device) if splits > 1 else None)
     _req(not defer_merge or (workspace is not None and splits > 1), "defer_merge needs splits > 1 and a caller-owned workspace")
@@ -296,7 +299,8 @@ def attention_merge(out: torch.Tensor, Lk: int, splits: int, workspace: torch.Te
 
 
 def window_attention(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, ws: int, qkv_bias: torch.Tensor,
-                     q_pooled: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+                     q_pooled: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Hiera windowed MHA straight from the fused qkv tokens [B*H*W, 3*heads*D] (bf16); if q_pooled is given
     ([B*(H/2)*(W/2), heads*D]) queries come from it with window ws/2.  Returns o [B*Hq*Wq, heads*D] bf16."""
     dim_out = qkv.shape[1] // 3
@@ -306,7 +310,8 @@ def window_attention(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, ws: 
         qt, q_ts, hq, wq, ws_q = qkv, qkv.stride(0), H, W, ws
     else:
         qt, q_ts, hq, wq, ws_q = q_pooled, q_pooled.stride(0), H // 2, W // 2, ws // 2
-    o = torch.empty(B * hq * wq, dim_out, dtype=OP16, device=qkv.device)
+    o = out if out is not None else torch.empty(B * hq * wq, dim_out, dtype=OP16, device=qkv.device)
+    _req(o.dtype == OP16 and o.shape == (B * hq * wq, dim_out) and o.stride(1) == 1, "window_attention: out is 16-bit [B*Hq*Wq, heads*D] rows")
     kpad = qkv_bias[dim_out:2 * dim_out]
     vpad = qkv_bias[2 * dim_out:]
     kptr = qkv.data_ptr() + dim_out * 2
@@ -316,14 +321,15 @@ def window_attention(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, ws: 
     return o
 
 
-def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int) -> torch.Tensor:
+def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decoder attention with head dim 16/32: q [B,Lq,C], k/v [B,Lk,C] bf16 (C = heads*D contiguous) -> [B,Lq,C] bf16."""
     B, Lq, C = q.shape
     Lk = k.shape[1]
     D = C // heads
     for t in (q, k, v):
         _req(t.dtype == OP16 and t.stride(2) == 1, "attention_small tensors must be 16-bit (ops.OP16), channel-contiguous")
-    o = torch.empty(B, Lq, C, dtype=OP16, device=q.device)
+    o = out if out is not None else torch.empty(B, Lq, C, dtype=OP16, device=q.device)
+    _req(o.dtype == OP16 and o.shape == (B, Lq, C) and o.stride(2) == 1, "attention_small: out is 16-bit [B,Lq,C] with contiguous channels")
     check(lib().msam2_attention_small_fwd(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1), _p(v), v.stride(0),
                                           v.stride(1), _p(o), o.stride(0), o.stride(1), B, heads, Lq, Lk, D,
                                           1.0 / math.sqrt(D), _stream()))

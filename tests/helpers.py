@@ -1,6 +1,7 @@
-"""Shared test helpers (CPU side)."""
+"""Shared test helpers."""
 import json
 import os
+import re
 
 import numpy as np
 import torch
@@ -123,3 +124,64 @@ def all_gather_flat(flat: torch.Tensor, world: int):
     out = [torch.empty_like(t) for _ in range(world)]
     dist.all_gather(out, t)
     return [o.cpu() for o in out]
+
+
+# ---- kernel-variant matrices (tests/test_gemm_variants_gpu.py, tests/test_attention_variants_gpu.py)
+SENT16, SENT32 = 0x7E5A, 0x7FC0DEAD            # bit patterns no kernel writes in these tests: the canaries around every output view
+
+
+def kernel_key(name: str) -> str:
+    """'void gemm_kernel<128, 32, 4, 1>(GemmParams)' or its mangled form '_Z11gemm_kernelILi128ELi32ELi4ELi1EEv10GemmParams' ->
+    'gemm_kernel<128,32,4,1>'"""
+    m = re.match(r"_Z(\d+)", name)
+    if m:
+        n = int(m.group(1))
+        base = name[m.end():m.end() + n]
+        rest = name[m.end() + n:]
+        if not rest.startswith("I"):
+            return base
+        args = re.findall(r"L([ib])(\d+)E", rest[:rest.find("EE") + 1] if "EE" in rest else rest)
+        return base + "<" + ",".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args) + ">"
+    name = re.sub(r"^void ", "", name.strip())
+    return re.sub(r"\s+", "", name.split("(")[0])
+
+
+def kernels_launched(fn, prefix: str):
+    """run fn under torch.profiler (kernel activity) and return the set of kernels it launched whose kernel_key starts with `prefix`"""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    keys = {kernel_key(e.name) for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA}
+    return {k for k in keys if k.startswith(prefix)}
+
+
+def nan_padded(rows, cols, ld, dtype, src, device="cuda"):
+    """src [rows, cols] as the leading block of a [rows + 5, ld] buffer whose other elements are NaN"""
+    buf = torch.full((rows + 5, ld), float("nan"), dtype=dtype, device=device)
+    buf[:rows, :cols] = src.to(dtype)
+    return buf[:rows, :cols]
+
+
+class Canvas:
+    """an [M, N] output view inside a sentinel-filled buffer: `aligned` puts the view on a 16-byte boundary with ldc % 8 == 0 (direct-store
+    epilogues), otherwise the view starts one element in and ldc is odd (generic epilogue)"""
+
+    def __init__(self, M, N, dtype, aligned=True, device="cuda"):
+        es = dtype.itemsize
+        self.itype = torch.int16 if es == 2 else torch.int32
+        self.pr, self.pc = 3, (16 // es if aligned else 1)
+        ldc = self.pc + N + (16 // es) + 8
+        ldc = (ldc + 7) // 8 * 8 if aligned else (ldc | 1)
+        self.buf = torch.empty(M + 2 * self.pr, ldc, dtype=dtype, device=device)
+        self.sent = SENT16 if es == 2 else SENT32
+        self.buf.view(self.itype).fill_(self.sent)
+        self.view = self.buf[self.pr:self.pr + M, self.pc:self.pc + N]
+        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=device)
+        self.inside[self.pr:self.pr + M, self.pc:self.pc + N] = True
+
+    def sentinels_intact(self):
+        return bool((self.buf.view(self.itype)[~self.inside] == self.sent).all())
+
+    def bits(self):
+        return self.buf.view(self.itype).clone()

@@ -27,9 +27,11 @@ pytestmark = pytest.mark.gpu
 
 from oracle import sam2_oracle as O  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import Canvas, kernels_launched, nan_padded  # noqa: E402
+
 DEV = "cuda"
 SWITCHES = ("MSAM2_GEMM_V1", "MSAM2_GEMM_VARIANT", "MSAM2_GEMM_WSTAT", "MSAM2_NT_BYTES", "MSAM2_NT_BYTES_F32", "MSAM2_NO_SPLITK")
-SENT16, SENT32 = 0x7E5A, 0x7FC0DEAD            # bit patterns no GEMM writes here: the canaries around every output view
 
 
 @pytest.fixture(scope="module")
@@ -86,30 +88,9 @@ def error_bound(S, n_terms, pre, ref, *, act=0, colscale=None, out16=False, fp16
     return e
 
 
-def kernel_key(name: str) -> str:
-    """'void gemm_kernel<128, 32, 4, 1>(GemmParams)' or its mangled form '_Z11gemm_kernelILi128ELi32ELi4ELi1EEv10GemmParams' ->
-    'gemm_kernel<128,32,4,1>'"""
-    m = re.match(r"_Z(\d+)", name)
-    if m:
-        n = int(m.group(1))
-        base = name[m.end():m.end() + n]
-        rest = name[m.end() + n:]
-        if not rest.startswith("I"):
-            return base
-        args = re.findall(r"L([ib])(\d+)E", rest[:rest.find("EE") + 1] if "EE" in rest else rest)
-        return base + "<" + ",".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args) + ">"
-    name = re.sub(r"^void ", "", name.strip())
-    return re.sub(r"\s+", "", name.split("(")[0])
-
-
 def gemm_kernels_launched(fn):
-    """run fn under torch.profiler (kernel activity) and return the set of GEMM kernels of libmsam2_hip.so it launched"""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    keys = {kernel_key(e.name) for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA}
-    return {k for k in keys if k.startswith("gemm_")}
+    """the set of GEMM kernels of libmsam2_hip.so that fn launched (torch.profiler, kernel activity)"""
+    return kernels_launched(fn, "gemm_")
 
 
 def assert_reached(launched, expect, what):
@@ -121,37 +102,6 @@ def assert_reached(launched, expect, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-def nan_padded(rows, cols, ld, dtype, src):
-    """src [rows, cols] as the leading block of a [rows + 5, ld] buffer whose other elements are NaN"""
-    buf = torch.full((rows + 5, ld), float("nan"), dtype=dtype, device=DEV)
-    buf[:rows, :cols] = src.to(dtype)
-    return buf[:rows, :cols]
-
-
-class Canvas:
-    """an [M, N] output view inside a sentinel-filled buffer: `aligned` puts the view on a 16-byte boundary with ldc % 8 == 0 (direct-store
-    epilogues), otherwise the view starts one element in and ldc is odd (generic epilogue)"""
-
-    def __init__(self, M, N, dtype, aligned=True):
-        es = dtype.itemsize
-        self.itype = torch.int16 if es == 2 else torch.int32
-        self.pr, self.pc = 3, (16 // es if aligned else 1)
-        ldc = self.pc + N + (16 // es) + 8
-        ldc = (ldc + 7) // 8 * 8 if aligned else (ldc | 1)
-        self.buf = torch.empty(M + 2 * self.pr, ldc, dtype=dtype, device=DEV)
-        self.sent = SENT16 if es == 2 else SENT32
-        self.buf.view(self.itype).fill_(self.sent)
-        self.view = self.buf[self.pr:self.pr + M, self.pc:self.pc + N]
-        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=DEV)
-        self.inside[self.pr:self.pr + M, self.pc:self.pc + N] = True
-
-    def sentinels_intact(self):
-        return bool((self.buf.view(self.itype)[~self.inside] == self.sent).all())
-
-    def bits(self):
-        return self.buf.view(self.itype).clone()
-
-
 def int_operands(M, N, K, seed):
     """small integers with structure: column 0 carries the row index mod 3 / 4, every row has a +1 in its own k-chunk (8 m + 3 mod K), the
     last column (inside the last, possibly partial k-tile) varies per 32-row / 32-column block, plus a few random entries per row"""

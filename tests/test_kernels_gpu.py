@@ -361,7 +361,7 @@ def test_attention_d96_four_wave_shape_in_a_child_process():
     env = dict(_os.environ)
     env["MSAM2_G96_X2"] = "1"
     r = subprocess.run([sys.executable, "-m", "pytest", _os.path.abspath(__file__), "-q", "-m", "gpu", "-k", "test_attention_vs_oracle and 96"],
-                       env=env, capture_output=True, text=True, cwd=_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
+                       env=env, capture_output=True, text=True, timeout=600, cwd=_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))))
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
