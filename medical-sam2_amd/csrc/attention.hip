@@ -51,9 +51,9 @@ struct AttnParams {
   // split-KV
   int splits;
   int defer_merge;  // split-KV partials stay in the workspace; msam2_attention_merge finishes (benchmark / overlap use)
-  int split_begin, split_cnt;  // attn_kv64_kernel only: this launch computes splits [split_begin, split_begin + split_cnt) of `splits`
-  // attn_kv64_kernel only: when non-null the key count is read from the device (1 <= *lk_dev <= Lk; Lk = the capacity the buffers and
-  // the split count were sized for).  A hipGraph captured once for a padded memory bank then serves every fill level of the bucket.
+  int split_begin, split_cnt;  // attn_kv64_kernel / attn_kv64x2_kernel only: this launch computes splits [split_begin, split_begin + split_cnt) of `splits`
+  // attn_kv64_kernel / attn_kv64x2_kernel only: when non-null the key count is read from the device (1 <= *lk_dev <= Lk; Lk = the capacity the
+  // buffers and the split count were sized for).  A hipGraph captured once for a padded memory bank then serves every fill level of the bucket.
   const int* lk_dev;
   op16* o_part;    // [splits][Bz][H][Lq][D] 16-bit, each split's own softmax-normalised output
   float* ml_part;  // [splits][Bz][H][Lq][2]  (running max in log2 domain, partial sum)
@@ -72,6 +72,55 @@ struct AttnCfg {
   static constexpr int STAGE = BK * (KS + VS);
   static constexpr int LDS_BYTES = 2 * STAGE;
 };
+
+// ---- building blocks of the MFMA forward kernels: one definition each (split_tiles, lds_read_tr16_pair: common.h) ----
+
+// The workgroup's place in its (x, y, z) grid after the XCD remap: all x of one (y, z) -- the query tiles / owner blocks that stream the
+// SAME rows -- land on one XCD, whose L2 then serves those rows once.  Pure speed: any placement is correct.
+struct WgCoords {
+  int x, y, z;
+};
+__device__ __forceinline__ WgCoords xcd_wg_coords() {
+  const int gx = gridDim.x, gy = gridDim.y;
+  const int nwg = gx * gy * gridDim.z;
+  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
+  return {lid % gx, (lid / gx) % gy, lid / (gx * gy)};
+}
+
+// The 32x32 MFMA accumulator of lane (r = lane & 31, h = lane >> 5) holds column r, and in register e row (e & 3) + 8 * (e >> 2) + 4 * h.
+// For S^T = K Q^T that row is the key of score register e (the column is the lane's query); for O^T it is the channel within a 32-block.
+__device__ __forceinline__ constexpr int s_frag_key(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// Lazy move of a row's running softmax reference (MSAM2_RESCALE_SLACK above): only when some lane of the wave sees the tile maximum mx
+// exceed m_run by more than the slack are the running sum and the O accumulators rescaled to the new reference.
+template <int DBLK>
+__device__ __forceinline__ void softmax_move_reference(float mx, float& m_run, float& l_run, f32x16 (&o)[DBLK]) {
+  const float m_new = fmaxf(m_run, mx);
+  if (__any(m_new > m_run + MSAM2_RESCALE_SLACK)) {
+    const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
+    l_run *= alpha;
+#pragma unroll
+    for (int d = 0; d < DBLK; ++d)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
+    m_run = m_new;
+  }
+}
+
+// Normalise-and-store of this lane's O^T column (one query row of DBLK * 32 channels) at dst: register 4 g + e of block d is channel
+// 32 d + 8 g + 4 h + e (s_frag_key), so every group g is one 8-byte store.  A macro because a function changes the listing of EVERY kernel
+// that calls it (after inlining the stores' address arithmetic loses its inbounds / no-wrap marks and the epilogue is scheduled
+// differently); tools/isa_diff.py holds this text to the code the kernels had with the loop written out.
+#define ATTN_STORE_O_ROWS(DBLK, dst, o, inv, h)                                           \
+  do {                                                                                \
+    op16* const dst_ = (dst);                                                         \
+    _Pragma("unroll") for (int d_ = 0; d_ < DBLK; ++d_)                               \
+      _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) {                              \
+        op16x4 w_;                                                                    \
+        _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) w_[e_] = f2op((o)[d_][4 * g_ + e_] * (inv)); \
+        *reinterpret_cast<op16x4*>(dst_ + d_ * 32 + 8 * g_ + 4 * (h)) = w_;           \
+      }                                                                               \
+  } while (0)
 
 __device__ __forceinline__ int64_t win_token_offset(int t, int ws, int wy, int wx, int himg, int wimg, bool& valid) {
   const int ty = t / ws, tx = t - ty * ws;
@@ -123,10 +172,8 @@ __global__ __launch_bounds__(NW * 64, (WIN && NW == 4) ? 3 : 1) void attn_fwd_ke
   }
 
   // ---- key range of this split (multiple of BK per split except the tail)
-  const int tiles_total = (p.Lk + C::BK - 1) / C::BK;
-  const int tiles_per = (tiles_total + p.splits - 1) / p.splits;
-  const int t_begin = split * tiles_per;
-  const int t_end = min(tiles_total, t_begin + tiles_per);
+  const TileRange tr = split_tiles(p.Lk, C::BK, p.splits, split);
+  const int t_begin = tr.begin, t_end = tr.end;
 
   uint4 rk[PER], rv[PER];
   auto gload = [&](int tile) {
@@ -204,16 +251,17 @@ __global__ __launch_bounds__(NW * 64, (WIN && NW == 4) ? 3 : 1) void attn_fwd_ke
       const op16x8 kf = *reinterpret_cast<const op16x8*>(kbase + k_off + st * 32);
       s = MSAM2_MFMA_32x32x16(kf, qf[st], s, 0, 0, 0);
     }
-    // online softmax (log2 domain); keys of register e: (e&3) + 8*(e>>2) + 4*h
+    // online softmax (log2 domain)
     const int key0 = tile * C::BK;
     float mx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int key = key0 + s_frag_key(e, h);
       s[e] = (key < p.Lk) ? s[e] * p.scale_log2 : -INFINITY;
       mx = fmaxf(mx, s[e]);
     }
     mx = half_max(mx);
+    // (softmax_move_reference changes this kernel's listing: the step keeps its text)
     const float m_new = fmaxf(m_run, mx);
     if (__any(m_new > m_run + MSAM2_RESCALE_SLACK)) {
       const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
@@ -239,15 +287,7 @@ __global__ __launch_bounds__(NW * 64, (WIN && NW == 4) ? 3 : 1) void attn_fwd_ke
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const unsigned char* a0 = vbase + v_off + (16 * st) * C::VS + d * 64;
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (short4_t __attribute__((address_space(3)))*)(a0 + 8 * C::VS));
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        o[d] = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, vv8), pf[st], o[d], 0, 0, 0);
+        o[d] = MSAM2_MFMA_32x32x16(lds_read_tr16_pair(a0, 8 * C::VS), pf[st], o[d], 0, 0, 0);
       }
     }
     if (tile + 1 < t_end) lstore(cur ^ 1);
@@ -258,35 +298,20 @@ __global__ __launch_bounds__(NW * 64, (WIN && NW == 4) ? 3 : 1) void attn_fwd_ke
   // ---- epilogue
   const float l_tot = half_sum(l_run);
   if (!qvalid) return;
+  // (two branches, the partial slot written out: the single-loop form of attn_kv64_kernel changes this kernel's listing)
   if (p.splits == 1) {
     const float inv = 1.f / l_tot;
     if constexpr (!WIN) {
       if (p.lse && h == 0) p.lse[((int64_t)z * p.H + head) * p.Lq + qi] = m_run + __log2f(l_tot);
     }
     op16* ob = p.o + (int64_t)b * p.o_bs + (int64_t)head * p.o_hs + qtok * p.o_ts;
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(ob + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, ob, o, inv, h);
   } else {
     const int64_t Bz = gridDim.z / p.splits;
     const int64_t row = (((int64_t)split * Bz + z) * p.H + head) * p.Lq + qi;
     op16* op = p.o_part + row * D;
     const float inv = 1.f / l_tot;                            // > 0: every split owns at least one valid key
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(op + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, op, o, inv, h);
     if (h == 0) {
       p.ml_part[row * 2 + 0] = m_run;
       p.ml_part[row * 2 + 1] = l_tot;
@@ -361,6 +386,40 @@ __global__ void attn_merge_kernel(AttnParams p, int Bz) {
   }
 }
 
+// ---- host: what attention_fwd_impl, attention_kv64_impl and msam2_attention_merge share ----
+
+template <int D>
+static void launch_merge(const AttnParams& p, int Bz, hipStream_t s) {
+  const int64_t rows = (int64_t)Bz * p.H * p.Lq;   // one wave per row
+  hipLaunchKernelGGL((attn_merge_kernel<D>), dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, p, Bz);
+}
+
+// The split count of the ABI carries a flag in its sign: splits < 0 = run the split pass with |splits| and leave the partials in the
+// workspace for msam2_attention_merge.  Makes splits the count, returns the flag.
+static bool parse_splits(int& splits) {
+  const bool defer = splits < 0;
+  if (defer) splits = -splits;
+  return defer;
+}
+
+// tensors with their {batch, head, token} element strides; a tensor the call does not have is passed as (nullptr, nullptr)
+static void set_qkvo(AttnParams& p, const void* q, const int64_t* qs, const void* k, const int64_t* ks, const void* v, const int64_t* vs,
+                     void* o, const int64_t* os) {
+  p.q = (const op16*)q; p.k = (const op16*)k; p.v = (const op16*)v; p.o = (op16*)o;
+  if (qs) { p.q_bs = qs[0]; p.q_hs = qs[1]; p.q_ts = qs[2]; }
+  if (ks) { p.k_bs = ks[0]; p.k_hs = ks[1]; p.k_ts = ks[2]; }
+  if (vs) { p.v_bs = vs[0]; p.v_hs = vs[1]; p.v_ts = vs[2]; }
+  if (os) { p.o_bs = os[0]; p.o_hs = os[1]; p.o_ts = os[2]; }
+}
+
+// the (effective) split count and the two regions of the workspace: [splits][B][H][Lq][D] 16-bit partial outputs, then
+// [splits][B][H][Lq][2] fp32 (max, sum) pairs -- msam2_attention_workspace_bytes is their sum
+static void set_workspace(AttnParams& p, void* workspace, int splits, int64_t B, int64_t H, int64_t Lq, int64_t D) {
+  p.splits = splits;
+  p.o_part = (op16*)workspace;
+  p.ml_part = workspace ? reinterpret_cast<float*>(p.o_part + (size_t)splits * B * H * Lq * D) : nullptr;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // LDS-DMA variant for D = 128 / 256 (memory attention): K/V tiles go global -> LDS with global_load_lds_dwordx4 (no staging
 // registers, no ds_write), which brings the D=256 kernel under 256 registers => 2 workgroups (8 waves) per CU, so one
@@ -389,13 +448,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
   // XCD-aware work mapping.  Workgroups are dealt round-robin over the 8 XCDs (id % 8 share an XCD), each with a private L2;
   // all query tiles of one (batch, head, split) stream the SAME K/V range, so they are placed on one XCD (a contiguous slice
   // of the remapped id space per XCD): K/V then comes from that XCD's L2 instead of being re-fetched from the Infinity Cache
-  // by every XCD.  Pure speed: any placement is correct.
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int nwg = gx * gy * gridDim.z;
-  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
-  const int qtile = lid % gx;
-  const int head = (lid / gx) % gy;
-  const int zz = lid / (gx * gy);
+  // by every XCD.
+  const WgCoords wg = xcd_wg_coords();
+  const int qtile = wg.x, head = wg.y, zz = wg.z;
   const int split = zz % p.splits, z = zz / p.splits;
   const op16* qb = p.q + (int64_t)z * p.q_bs + (int64_t)head * p.q_hs;
   const op16* kb = p.k + (int64_t)z * p.k_bs + (int64_t)head * p.k_hs;
@@ -419,13 +474,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
     drop_seed = p.drop.seed + (p.drop.seed_dev ? *p.drop.seed_dev : 0ull);
   }
 
-  const int tiles_total = (p.Lk + BK - 1) / BK;
-  const int tiles_per = (tiles_total + p.splits - 1) / p.splits;
-  const int t_begin = split * tiles_per;
-  const int t_end = min(tiles_total, t_begin + tiles_per);
   // full tiles run in the pipelined loop; a partial last tile (only the split that owns it) is handled after the loop so
   // that the loop body carries no tail logic (and none of its registers)
-  const int t_full_end = min(t_end, p.Lk / BK);
+  const TileRange tr = split_tiles(p.Lk, BK, p.splits, split);
+  const int t_begin = tr.begin, t_full_end = tr.full_end;
 
   // DMA sources: buffer descriptors (SGPRs) + loop-invariant 32-bit per-lane byte offsets + a scalar tile offset
   // (buffer_load_dwordx4 ... offen lds); piece j of this wave covers flat chunks (wave*PW + j)*64 + lane of the [32][CPR] image
@@ -513,23 +565,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
     float mx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      if (masked) {
-        const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (key >= p.Lk) s[e] = -INFINITY;
-      }
+      if (masked && key0 + s_frag_key(e, h) >= p.Lk) s[e] = -INFINITY;
       mx = fmaxf(mx, s[e]);
     }
     mx = half_max(mx) * p.scale_log2;   // scale > 0: max commutes with it
-    const float m_new = fmaxf(m_run, mx);
-    if (__any(m_new > m_run + MSAM2_RESCALE_SLACK)) {
-      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
-      m_run = m_new;
-    }
+    softmax_move_reference(mx, m_run, l_run, o);
     op16x8 pf[2];
     // two elements per VALU slot where the ISA has packed fp32 ops (v_pk_fma_f32 for the exponent argument, v_pk_add_f32 for the
     // running sum): the softmax is issue-bound, and for D = 96 it is longer than the tile's MFMAs
@@ -543,7 +583,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
       for (int e = 0; e < 16; ++e) {
         const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], p.scale_log2, -m_run));
         psum2[e & 1] += pe;
-        const bool keep = dropout_keep(drop_seed, ebase + (uint64_t)((e & 3) + 8 * (e >> 2)), p.drop.thr);
+        const bool keep = dropout_keep(drop_seed, ebase + (uint64_t)s_frag_key(e, 0), p.drop.thr);
         pf[e >> 3][e & 7] = f2op_fast(keep ? pe * p.drop.inv_keep : 0.f);
       }
     } else {
@@ -559,18 +599,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
     }
     l_run += psum2[0] + psum2[1];
     STAMP(t3_);
+    auto vread = [&](int d, int st) {
+      const int cch = (d * 4 + v_c0) ^ v_sw;   // swizzled 16-byte chunk; (key & 3) == q for every read below
+      return lds_read_tr16_pair(vbase + v_row + (16 * st) * RB + (cch << 4), 8 * RB);
+    };
     if constexpr (D <= 128) {
-      typedef __attribute__((ext_vector_type(8))) short short8_t;
-      auto vread = [&](int d, int st) {
-        const int cch = (d * 4 + v_c0) ^ v_sw;   // swizzled 16-byte chunk; (key & 3) == q for every read below
-        const unsigned char* a0 = vbase + v_row + (16 * st) * RB + (cch << 4);
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        return __builtin_bit_cast(op16x8, vv8);
-      };
       op16x8 vf[2][2];
       vf[0][0] = vread(0, 0);
       vf[0][1] = vread(0, 1);
@@ -588,17 +621,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
 #pragma unroll
       for (int d = 0; d < DBLK; ++d) {
   #pragma unroll
-        for (int st = 0; st < 2; ++st) {
-          typedef __attribute__((ext_vector_type(8))) short short8_t;
-          const int cch = (d * 4 + v_c0) ^ v_sw;   // swizzled 16-byte chunk; (key & 3) == q for every read below
-          const unsigned char* a0 = vbase + v_row + (16 * st) * RB + (cch << 4);
-          const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-          const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-          short8_t vv8;
-          vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-          vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-          o[d] = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, vv8), pf[st], o[d], 0, 0, 0);
-        }
+        for (int st = 0; st < 2; ++st) o[d] = MSAM2_MFMA_32x32x16(vread(d, st), pf[st], o[d], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -629,7 +652,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
     g_stamp[5] = (unsigned long long)(t_full_end - t_begin);
   }
 #endif
-  if (t_full_end < t_end) {
+  if (tr.full_end < tr.end) {   // (host key count, never empty: partial_tail()'s begin < end adds a compare to the listing)
     // partial last tile: rows past Lk re-read the last valid key (their scores are masked to -inf)
     const int key0 = t_full_end * BK, last = p.Lk - 1 - key0;
     unsigned char* base = smem + wave * PW * 1024;
@@ -651,32 +674,17 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_glds_kernel(AttnParams p) {
 
   const float l_tot = half_sum(l_run);
   if (!qvalid) return;
+  // (two branches, the partial slot written out: the single-loop form of attn_kv64_kernel changes this kernel's listing)
   if (p.splits == 1) {
     const float inv = 1.f / l_tot;
     op16* ob = p.o + (int64_t)z * p.o_bs + (int64_t)head * p.o_hs + (int64_t)qi * p.o_ts;
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(ob + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, ob, o, inv, h);
   } else {
     const int64_t Bz = gridDim.z / p.splits;
     const int64_t row = (((int64_t)split * Bz + z) * p.H + head) * p.Lq + qi;
     op16* op = p.o_part + row * D;
     const float inv = 1.f / l_tot;                            // > 0: every split owns at least one valid key
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(op + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, op, o, inv, h);
     if (h == 0) {
       p.ml_part[row * 2 + 0] = m_run;
       p.ml_part[row * 2 + 1] = l_tot;
@@ -715,12 +723,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
   // XCD-aware work mapping (see attn_glds_kernel): the query tiles of one (batch, head, split) share an XCD's L2
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int nwg = gx * gy * gridDim.z;
-  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
-  const int qtile = lid % gx;
-  const int head = (lid / gx) % gy;
-  const int zz = lid / (gx * gy);
+  const WgCoords wg = xcd_wg_coords();
+  const int qtile = wg.x, head = wg.y, zz = wg.z;
   const int split = p.split_begin + zz % p.split_cnt, z = zz / p.split_cnt;
   const op16* qb = p.q + (int64_t)z * p.q_bs + (int64_t)head * p.q_hs;
   const op16* kb = p.k + (int64_t)z * p.k_bs + (int64_t)head * p.k_hs;
@@ -737,11 +741,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   }
 
   const int Lk = p.lk_dev ? min(*p.lk_dev, p.Lk) : p.Lk;   // wave-uniform scalar load
-  const int tiles_total = (Lk + BK - 1) / BK;
-  const int tiles_per = (tiles_total + p.splits - 1) / p.splits;
-  const int t_begin = split * tiles_per;
-  const int t_end = min(tiles_total, t_begin + tiles_per);
-  const int t_full_end = min(t_end, Lk / BK);
+  const TileRange tr = split_tiles(Lk, BK, p.splits, split);   // may be empty: device-side key count
+  const int t_begin = tr.begin, t_full_end = tr.full_end;
 
   const auto k_rsrc = raw_rsrc(kb);
   const auto v_rsrc = raw_rsrc(vb);
@@ -789,20 +790,13 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
   auto compute = [&](int stage, int key0, const bool masked) __attribute__((always_inline)) {
     const unsigned char* kbase = smem + stage * STAGE;
     const unsigned char* vbase = kbase + TILE_K;
-    typedef __attribute__((ext_vector_type(8))) short short8_t;
     auto kread = [&](int st) {
       const int c = 2 * st + h;
       return *reinterpret_cast<const op16x8*>(kbase + k_row + (((c & ~15) | ((c & 15) ^ k_x)) << 4));
     };
     auto vread = [&](int d, int st) {
       const int cch = (d * 4 + v_c0) ^ v_sw;
-      const unsigned char* a0 = vbase + v_row + (16 * st) * RBV + (cch << 4);
-      const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-      const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RBV));
-      short8_t vv8;
-      vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-      vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-      return __builtin_bit_cast(op16x8, vv8);
+      return lds_read_tr16_pair(vbase + v_row + (16 * st) * RBV + (cch << 4), 8 * RBV);
     };
     // S^T = K Q^T: a rolling window of KPF K fragments stays in flight ahead of the MFMA that consumes the oldest one
 #ifndef MSAM2_KV64_KPF
@@ -830,23 +824,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
     float mx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      if (masked) {
-        const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (key >= Lk) s[e] = -INFINITY;
-      }
+      if (masked && key0 + s_frag_key(e, h) >= Lk) s[e] = -INFINITY;
       mx = fmaxf(mx, s[e]);
     }
     mx = half_max(mx) * p.scale_log2;   // scale > 0: max commutes with it
-    const float m_new = fmaxf(m_run, mx);
-    if (__any(m_new > m_run + MSAM2_RESCALE_SLACK)) {
-      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
-      m_run = m_new;
-    }
+    softmax_move_reference(mx, m_run, l_run, o);
     op16x8 pf[2];
     float psum = 0.f;
     const float nm = -m_run;   // finite: every tile holds >= 1 valid key
@@ -892,9 +874,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
     g_stamp[15] = __builtin_amdgcn_s_memtime() - ct0_;          // shader cycles over the loop
   }
 #endif
-  // (t_begin < t_end: a trailing split that a device-side key count left empty has t_end = tiles_total < t_begin and must not take the
-  //  partial tile of the last live split a second time)
-  if (t_begin < t_end && t_full_end < t_end) {
+  if (tr.partial_tail()) {   // (false for a trailing split that the device-side key count left empty: see split_tiles)
     // partial last tile: rows past Lk re-read the last valid key (their scores are masked to -inf)
     const int key0 = t_full_end * BK, last = Lk - 1 - key0;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -938,15 +918,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kv64_kernel(AttnParams p) {
       p.ml_part[row * 2 + 1] = l_tot;
     }
   }
-#pragma unroll
-  for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      op16x4 w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) w[e] = f2op(o[d][4 * g + e] * inv);
-      *reinterpret_cast<op16x4*>(dst + d * 32 + 8 * g + 4 * h) = w;
-    }
+  ATTN_STORE_O_ROWS(DBLK, dst, o, inv, h);
 #ifdef MSAM2_STAMP
   if (threadIdx.x == 0) {
     const int wg = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -1000,12 +972,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int nwg = gx * gy * gridDim.z;
-  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
-  const int qtile = lid % gx;
-  const int head = (lid / gx) % gy;
-  const int zz = lid / (gx * gy);
+  const WgCoords wg = xcd_wg_coords();
+  const int qtile = wg.x, head = wg.y, zz = wg.z;
   const int split = p.split_begin + zz % p.split_cnt, z = zz / p.split_cnt;
   const op16* qb = p.q + (int64_t)z * p.q_bs + (int64_t)head * p.q_hs;
   const op16* kb = p.k + (int64_t)z * p.k_bs + (int64_t)head * p.k_hs;
@@ -1027,12 +995,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
   }
 
   const int Lk = p.lk_dev ? min(*p.lk_dev, p.Lk) : p.Lk;   // wave-uniform scalar load
-  const int tiles_total = (Lk + BK - 1) / BK;
-  const int tiles_per = (tiles_total + p.splits - 1) / p.splits;
-  const int t_begin = split * tiles_per;
-  const int t_end = min(tiles_total, t_begin + tiles_per);
-  const int t_full_end = min(t_end, Lk / BK);
-  const int nt = t_end - t_begin;
+  const TileRange tr = split_tiles(Lk, BK, p.splits, split);   // may be empty: device-side key count
+  const int t_begin = tr.begin, t_end = tr.end, t_full_end = tr.full_end;
+  const int nt = tr.count();                                   // <= 0: empty, everything below is skipped
 
   const auto k_rsrc = raw_rsrc(kb);
   const auto v_rsrc = raw_rsrc(vb);
@@ -1099,7 +1064,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
   const int li = lane & 15, vq = li >> 2, vp = li & 3, cgrp = (lane >> 4) & 1;
   const int v_row = (4 * h + vq) * RBV + ((vp & 1) << 3);
   const int v_sw = ((vq >> 1) & 1) << 2, v_c0 = 2 * cgrp + (vp >> 1);
-  typedef __attribute__((ext_vector_type(8))) short short8_t;
 
   // S^T(a), S^T(b) = K Q_a^T, K Q_b^T: every K fragment read feeds two MFMAs; a rolling window of 4 fragments stays in flight
   auto s_phase = [&](int stage, f32x16 (&s)[QB]) __attribute__((always_inline)) {
@@ -1169,10 +1133,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[b][e], p.scale_log2, nm));
-        if (masked) {
-          const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (key >= Lk) pe = 0.f;
-        }
+        if (masked && key0 + s_frag_key(e, h) >= Lk) pe = 0.f;
         psum += pe;
         pf[b][e >> 3][e & 7] = f2op_fast(pe);
       }
@@ -1187,13 +1148,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const int cch = (d * 4 + v_c0) ^ v_sw;
-        const unsigned char* a0 = vbase + v_row + (16 * st) * RBV + (cch << 4);
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RBV));
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        vf[d][st] = __builtin_bit_cast(op16x8, vv8);
+        vf[d][st] = lds_read_tr16_pair(vbase + v_row + (16 * st) * RBV + (cch << 4), 8 * RBV);
       }
   };
   auto pv_phase = [&](const op16x8 (&vf)[DBLK][2], const op16x8 (&pf)[QB][2]) __attribute__((always_inline)) {
@@ -1274,15 +1229,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_kv64x2_kernel(AttnParams p) {
         p.ml_part[row * 2 + 1] = l_tot;
       }
     }
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[b][d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(dst + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, dst, o[b], inv, h);
   }
 #endif
 }
@@ -1303,10 +1250,7 @@ static int launch_attn_kv64(const AttnParams& p, int Bz, hipStream_t s) {
     dim3 grid(cdiv(p.Lq, 128), p.H, Bz * p.split_cnt);
     hipLaunchKernelGGL((attn_kv64_kernel<4, MSAM2_KV64_OCC>), grid, dim3(256), 0, s, p);
   }
-  if (p.splits > 1 && !p.defer_merge) {
-    const int64_t rows = (int64_t)Bz * p.H * p.Lq;
-    hipLaunchKernelGGL((attn_merge_kernel<64>), dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, p, Bz);
-  }
+  if (p.splits > 1 && !p.defer_merge) launch_merge<64>(p, Bz, s);
   return msam2_check_launch("attention_kv64_fwd");
 }
 
@@ -1358,12 +1302,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int nwg = gx * gy * gridDim.z;
-  const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), nwg);
-  const int qtile = lid % gx;
-  const int head = (lid / gx) % gy;
-  const int zz = lid / (gx * gy);
+  const WgCoords wg = xcd_wg_coords();
+  const int qtile = wg.x, head = wg.y, zz = wg.z;
   const int split = zz % p.splits, z = zz / p.splits;
   const op16* qb = p.q + (int64_t)z * p.q_bs + (int64_t)head * p.q_hs;
   const op16* kb = p.k + (int64_t)z * p.k_bs + (int64_t)head * p.k_hs;
@@ -1398,11 +1338,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
     for (int i = 0; i < 8; ++i) mref[b][i] = (op16)0.f;
 
   const int Lk = p.Lk;
-  const int stages_total = (Lk + SK - 1) / SK;
-  const int stages_per = (stages_total + p.splits - 1) / p.splits;
-  const int s_begin = split * stages_per;
-  const int s_end = min(stages_total, s_begin + stages_per);
-  const int ns = s_end - s_begin;                                        // >= 1 (launcher)
+  const TileRange sr = split_tiles(Lk, SK, p.splits, split);             // in 64-key stages
+  const int s_begin = sr.begin, s_end = sr.end;
+  const int ns = sr.count();                                             // >= 1 (launcher)
   const int key_end = min(Lk, s_end * SK);
   const int nt = (key_end - s_begin * SK + BK - 1) / BK;                 // 32-key sub-tiles of this split
   const bool partial = (key_end % BK) != 0;                              // the last sub-tile is short
@@ -1457,7 +1395,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
   const int k_row = r * RB, k_x = (r >> 2) & 3;
   const int li = lane & 15;
   const int v_off = (4 * h + (li >> 2)) * RB + (16 * ((lane >> 4) & 1) + 4 * (li & 3)) * 2;
-  typedef __attribute__((ext_vector_type(8))) short short8_t;
 
   // S^T(a), S^T(b) = K Q_a^T, K Q_b^T of one 32-key sub-tile: every K fragment read feeds QB MFMAs.  The six fragments of sub-tile
   // i+2 are read from LDS a whole iteration before their MFMAs (k_fetch at the top of iteration i; two register sets used
@@ -1556,10 +1493,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
         if constexpr (PROBE >= 1) pe = s[b][e] * p.scale_log2 + nm;
         else if constexpr (MREF) pe = __builtin_amdgcn_exp2f(s[b][e]);          // the accumulator is the exponent
         else pe = __builtin_amdgcn_exp2f(__builtin_fmaf(s[b][e], p.scale_log2, nm));
-        if (masked) {
-          const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-          if (key >= Lk) pe = 0.f;
-        }
+        if (masked && key0 + s_frag_key(e, h) >= Lk) pe = 0.f;
         psum += pe;
         pf[b][e >> 3][e & 7] = f2op_fast(pe);
       }
@@ -1571,15 +1505,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
 #pragma unroll
     for (int d = 0; d < DBLK; ++d)
 #pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const unsigned char* a0 = vbase + (16 * st) * RB + d * 64;
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        vf[d][st] = __builtin_bit_cast(op16x8, vv8);
-      }
+      for (int st = 0; st < 2; ++st) vf[d][st] = lds_read_tr16_pair(vbase + (16 * st) * RB + d * 64, 8 * RB);
   };
   auto pv_phase = [&](const op16x8 (&vf)[DBLK][2], const op16x8 (&pf)[QB][2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1683,15 +1609,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_g96x2_kernel(AttnParams p) {
         p.ml_part[row * 2 + 1] = l_tot;
       }
     }
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 w;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = f2op(o[b][d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(dst + d * 32 + 8 * g + 4 * h) = w;
-      }
+    ATTN_STORE_O_ROWS(DBLK, dst, o[b], inv, h);
   }
 #endif
 }
@@ -1724,10 +1642,7 @@ static int launch_attn_glds(const AttnParams& p, int Bz, hipStream_t s) {
       hipLaunchKernelGGL((attn_glds_kernel<96, 128, 4, 3>), grid, dim3(256), 0, s, p);
     }
   } else hipLaunchKernelGGL((attn_glds_kernel<D, D, 4, 2>), grid, dim3(256), 0, s, p);
-  if (p.splits > 1 && !p.defer_merge) {
-    const int64_t rows = (int64_t)Bz * p.H * p.Lq;
-    hipLaunchKernelGGL((attn_merge_kernel<D>), dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, p, Bz);
-  }
+  if (p.splits > 1 && !p.defer_merge) launch_merge<D>(p, Bz, s);
   return msam2_check_launch("attention_fwd(glds)");
 }
 
@@ -1740,10 +1655,7 @@ static int launch_attn(const AttnParams& p, int Bz, hipStream_t s) {
   // doubles the workgroups a CU holds, and these launches are bound by how many loads are in flight
   const int lds = ((p.Lk + C::BK - 1) / C::BK <= p.splits) ? C::STAGE : C::LDS_BYTES;
   hipLaunchKernelGGL((attn_fwd_kernel<D, NW, WIN>), grid, dim3(NW * 64), lds, s, p);
-  if (p.splits > 1 && !p.defer_merge) {
-    const int64_t rows = (int64_t)Bz * p.H * p.Lq;
-    hipLaunchKernelGGL((attn_merge_kernel<D>), dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, p, Bz);
-  }
+  if (p.splits > 1 && !p.defer_merge) launch_merge<D>(p, Bz, s);
   return msam2_check_launch("attention_fwd");
 }
 
@@ -1773,24 +1685,20 @@ extern "C" int msam2_attention_merge(void* o, const int64_t* o_strides, int64_t 
                                      int splits, void* workspace, size_t workspace_bytes, void* stream) {
   MSAM2_REQUIRE(o && workspace && B > 0 && H > 0 && Lq > 0 && Lk > 0, "attention_merge: bad arguments");
   MSAM2_REQUIRE(D == 96 || D == 256 || D == 64 || D == 128, "attention_merge: head dim %lld not built", (long long)D);
-  splits = attn_effective_splits(Lk, splits < 0 ? -splits : splits);
+  parse_splits(splits);
+  splits = attn_effective_splits(Lk, splits);
   MSAM2_REQUIRE(splits > 1, "attention_merge: nothing to merge");
   MSAM2_REQUIRE(workspace_bytes >= msam2_attention_workspace_bytes(B, H, Lq, D, splits), "attention_merge: workspace too small");
   AttnParams p = {};
-  p.o = (op16*)o;
-  p.o_bs = o_strides[0]; p.o_hs = o_strides[1]; p.o_ts = o_strides[2];
+  set_qkvo(p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, o, o_strides);
   p.B = (int)B; p.H = (int)H; p.Lq = (int)Lq; p.Lk = (int)Lk;
-  p.splits = splits;
-  p.o_part = (op16*)workspace;
-  p.ml_part = reinterpret_cast<float*>(p.o_part + (size_t)splits * B * H * Lq * D);
-  const int64_t rows = B * H * Lq;
-  dim3 grid(cdiv(rows * 64, 256));
+  set_workspace(p, workspace, splits, B, H, Lq, D);
   hipStream_t s = (hipStream_t)stream;
   switch (D) {
-    case 96: hipLaunchKernelGGL((attn_merge_kernel<96>), grid, dim3(256), 0, s, p, (int)B); break;
-    case 256: hipLaunchKernelGGL((attn_merge_kernel<256>), grid, dim3(256), 0, s, p, (int)B); break;
-    case 64: hipLaunchKernelGGL((attn_merge_kernel<64>), grid, dim3(256), 0, s, p, (int)B); break;
-    default: hipLaunchKernelGGL((attn_merge_kernel<128>), grid, dim3(256), 0, s, p, (int)B); break;
+    case 96: launch_merge<96>(p, (int)B, s); break;
+    case 256: launch_merge<256>(p, (int)B, s); break;
+    case 64: launch_merge<64>(p, (int)B, s); break;
+    default: launch_merge<128>(p, (int)B, s); break;
   }
   return msam2_check_launch("attention_merge");
 }
@@ -1805,8 +1713,7 @@ static int attention_fwd_impl(const void* q, const int64_t* q_strides, const voi
   MSAM2_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, "attention: empty problem");
   MSAM2_REQUIRE(D == 96 || D == 256 || D == 64 || D == 128, "attention: head dim %lld not built (96/256/64/128)", (long long)D);
   // splits < 0: run the split-KV pass only and leave the partials in the workspace for msam2_attention_merge
-  const bool defer = splits < 0;
-  if (defer) splits = -splits;
+  const bool defer = parse_splits(splits);
   MSAM2_REQUIRE(splits >= 1 && splits <= 64, "attention: bad split count %d", splits);
   // the log-sum-exp rows come from the merge kernel: at least two splits whenever the keys allow (the tuned single-pass kernels
   // stay untouched); a single tile of keys goes through the register-staged kernel, which writes them itself
@@ -1819,17 +1726,11 @@ static int attention_fwd_impl(const void* q, const int64_t* q_strides, const voi
   MSAM2_REQUIRE(workspace_bytes >= msam2_attention_workspace_bytes(B, H, Lq, D, splits), "attention: workspace too small");
   MSAM2_REQUIRE(!defer || splits > 1, "attention: a deferred merge needs an effective split count > 1");
   AttnParams p = {};
-  p.q = (const op16*)q; p.k = (const op16*)k; p.v = (const op16*)v; p.o = (op16*)o;
-  p.q_bs = q_strides[0]; p.q_hs = q_strides[1]; p.q_ts = q_strides[2];
-  p.k_bs = k_strides[0]; p.k_hs = k_strides[1]; p.k_ts = k_strides[2];
-  p.v_bs = v_strides[0]; p.v_hs = v_strides[1]; p.v_ts = v_strides[2];
-  p.o_bs = o_strides[0]; p.o_hs = o_strides[1]; p.o_ts = o_strides[2];
+  set_qkvo(p, q, q_strides, k, k_strides, v, v_strides, o, o_strides);
   p.B = (int)B; p.H = (int)H; p.Lq = (int)Lq; p.Lk = (int)Lk;
   p.scale_log2 = scale * 1.4426950408889634f;
-  p.splits = splits;
+  set_workspace(p, workspace, splits, B, H, Lq, D);
   p.defer_merge = defer ? 1 : 0;
-  p.o_part = (op16*)workspace;
-  p.ml_part = workspace ? reinterpret_cast<float*>(p.o_part + (size_t)splits * B * H * Lq * D) : nullptr;
   p.lse = lse;
   MSAM2_REQUIRE(splits == 1 || workspace, "attention: split-KV needs a workspace");
   hipStream_t s = (hipStream_t)stream;
@@ -2007,22 +1908,12 @@ __global__ __launch_bounds__(512) void attn_win_kernel(AttnParams p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       if constexpr (MASKED) {
-        const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (key >= p.Lk) s[e] = -INFINITY;
+        if (key0 + s_frag_key(e, h) >= p.Lk) s[e] = -INFINITY;
       }
       mx = fmaxf(mx, s[e]);
     }
     mx = half_max(mx) * p.scale_log2;   // scale > 0: max commutes with it
-    const float m_new = fmaxf(m_run, mx);
-    if (__any(m_new > m_run + MSAM2_RESCALE_SLACK)) {
-      const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - m_new);
-      l_run *= alpha;
-#pragma unroll
-      for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
-      m_run = m_new;
-    }
+    softmax_move_reference(mx, m_run, l_run, o);
     float psum = 0.f;
     op16x8 pf[2];
     const float nm = -m_run;                                 // finite: every tile holds >= 1 valid key
@@ -2038,7 +1929,7 @@ __global__ __launch_bounds__(512) void attn_win_kernel(AttnParams p) {
     for (int d = 0; d < DBLK; ++d) {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
+        // (not lds_read_tr16_pair: either half of the pair may lie past the window's last V row and is then not read)
         const unsigned char* a0 = vsm + (key0 + 16 * st) * RB + v_off + d * 64;
         short4_t lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
         if (!MASKED || 16 * st < nv) lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
@@ -2057,18 +1948,7 @@ __global__ __launch_bounds__(512) void attn_win_kernel(AttnParams p) {
   ws2_ = __builtin_amdgcn_s_memrealtime();
 #endif
   const float inv = 1.f / l_tot;
-  if (qvalid) {
-  op16* ob = p.o + (int64_t)b * p.o_bs + (int64_t)head * p.o_hs + qtok * p.o_ts;
-#pragma unroll
-  for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      op16x4 wv;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) wv[e] = f2op(o[d][4 * g + e] * inv);
-      *reinterpret_cast<op16x4*>(ob + d * 32 + 8 * g + 4 * h) = wv;
-    }
-  }
+  if (qvalid) ATTN_STORE_O_ROWS(DBLK, p.o + (int64_t)b * p.o_bs + (int64_t)head * p.o_hs + qtok * p.o_ts, o, inv, h);
 #ifdef MSAM2_STAMP
   wait_vmcnt<0>();
   ws3_ = __builtin_amdgcn_s_memrealtime();
@@ -2204,7 +2084,7 @@ __global__ __launch_bounds__(256) void attn_tinywin_kernel(AttnParams p, int n_u
     float mx = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int key = key0 + s_frag_key(e, h);
       if (KW > 1 && key / p.Lk != qwin) s[e] = -INFINITY;      // the other windows of the unit
       mx = fmaxf(mx, s[e]);
     }
@@ -2232,30 +2112,13 @@ __global__ __launch_bounds__(256) void attn_tinywin_kernel(AttnParams p, int n_u
     for (int d = 0; d < DBLK; ++d) {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
         const unsigned char* a0 = vsm + (key0 + 16 * st) * RB + v_off + d * 64;
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        o[d] = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, vv8), pf[st], o[d], 0, 0, 0);
+        o[d] = MSAM2_MFMA_32x32x16(lds_read_tr16_pair(a0, 8 * RB), pf[st], o[d], 0, 0, 0);
       }
     }
   }
   const float inv = 1.f / half_sum(l_run);
-  if (qvalid) {
-    op16* ob = p.o + (int64_t)qb_ * p.o_bs + (int64_t)head * p.o_hs + qoff * p.o_ts;
-#pragma unroll
-    for (int d = 0; d < DBLK; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        op16x4 wv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wv[e] = f2op(o[d][4 * g + e] * inv);
-        *reinterpret_cast<op16x4*>(ob + d * 32 + 8 * g + 4 * h) = wv;
-      }
-  }
+  if (qvalid) ATTN_STORE_O_ROWS(DBLK, p.o + (int64_t)qb_ * p.o_bs + (int64_t)head * p.o_hs + qoff * p.o_ts, o, inv, h);
 }
 
 // windows of 16 keys (two per wave), tiling both token images exactly, D = 96.  (The 64-key windows of the q-pooled stage 1 -> 2 block run
@@ -2291,8 +2154,7 @@ static int attention_kv64_impl(const void* q, const int64_t* q_strides, const vo
                                size_t workspace_bytes, void* stream, const int* lk_dev = nullptr) {
   MSAM2_REQUIRE(q && k && v && (o || split_cnt >= 0), "attention_kv64: null tensor");
   MSAM2_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, "attention_kv64: empty problem");
-  bool defer = splits < 0;
-  if (defer) splits = -splits;
+  bool defer = parse_splits(splits);
   MSAM2_REQUIRE(splits >= 1 && splits <= 64, "attention_kv64: bad split count %d", splits);
   for (int i = 0; i < 3; ++i)
     MSAM2_REQUIRE(q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && (!o || o_strides[i] % 4 == 0),
@@ -2313,20 +2175,14 @@ static int attention_kv64_impl(const void* q, const int64_t* q_strides, const vo
   MSAM2_REQUIRE(!defer || splits > 1, "attention_kv64: a deferred merge needs an effective split count > 1");
   MSAM2_REQUIRE(splits == 1 || workspace, "attention_kv64: split-KV needs a workspace");
   AttnParams p = {};
-  p.q = (const op16*)q; p.k = (const op16*)k; p.v = (const op16*)v; p.o = (op16*)o;
-  p.q_bs = q_strides[0]; p.q_hs = q_strides[1]; p.q_ts = q_strides[2];
-  p.k_bs = k_strides[0]; p.k_hs = k_strides[1]; p.k_ts = k_strides[2];
-  p.v_bs = v_strides[0]; p.v_hs = v_strides[1]; p.v_ts = v_strides[2];
-  if (o) { p.o_bs = o_strides[0]; p.o_hs = o_strides[1]; p.o_ts = o_strides[2]; }
+  set_qkvo(p, q, q_strides, k, k_strides, v, v_strides, o, o ? o_strides : nullptr);   // (the partial launches have no o)
   p.B = (int)B; p.H = (int)H; p.Lq = (int)Lq; p.Lk = (int)Lk;
   p.scale_log2 = scale * 1.4426950408889634f;
-  p.splits = splits;
+  set_workspace(p, workspace, splits, B, H, Lq, 64);
   p.split_begin = split_begin;
   p.split_cnt = split_cnt;
   p.lk_dev = lk_dev;
   p.defer_merge = defer ? 1 : 0;
-  p.o_part = (op16*)workspace;
-  p.ml_part = workspace ? reinterpret_cast<float*>(p.o_part + (size_t)splits * B * H * Lq * 64) : nullptr;
   return launch_attn_kv64(p, (int)B, (hipStream_t)stream);
 }
 
@@ -2339,7 +2195,10 @@ extern "C" int msam2_attention_kv64_fwd(const void* q, const int64_t* q_strides,
 }
 
 // The split count msam2_attention_fwd / _kv64_fwd actually run with for a requested one (every split owns >= one 32-key tile).
-extern "C" int msam2_attention_effective_splits(int64_t Lk, int splits) { return attn_effective_splits(Lk, splits < 0 ? -splits : splits); }
+extern "C" int msam2_attention_effective_splits(int64_t Lk, int splits) {
+  parse_splits(splits);
+  return attn_effective_splits(Lk, splits);
+}
 
 // Splits [split_begin, split_begin + split_count) of a `splits`-way msam2_attention_kv64_fwd (splits = the EFFECTIVE count): their
 // partial (max, sum, O') triples land in the same workspace slots as in the full call; nothing is merged.  The cross-GPU key split of
@@ -2692,8 +2551,7 @@ __global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restric
       float mx = -INFINITY;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int key = key0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (key >= key_hi) sacc[e] = -INFINITY;
+        if (key0 + s_frag_key(e, h) >= key_hi) sacc[e] = -INFINITY;
         mx = fmaxf(mx, sacc[e]);
       }
       mx = half_max(mx) * scale_log2;                                            // finite: every step holds >= 1 key of the range
@@ -2714,16 +2572,8 @@ __global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restric
       l_run += psum;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // the wave's own V tile is in LDS
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
-        const unsigned char* a0 = vt[wave] + (16 * s2) * RB + v_off;
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-        short8_t vv8;
-        vv8[0] = lo[0]; vv8[1] = lo[1]; vv8[2] = lo[2]; vv8[3] = lo[3];
-        vv8[4] = hi[0]; vv8[5] = hi[1]; vv8[6] = hi[2]; vv8[7] = hi[3];
-        oacc = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, vv8), pf[s2], oacc, 0, 0, 0);
-      }
+      for (int s2 = 0; s2 < 2; ++s2)
+        oacc = MSAM2_MFMA_32x32x16(lds_read_tr16_pair(vt[wave] + (16 * s2) * RB + v_off, 8 * RB), pf[s2], oacc, 0, 0, 0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         // tile read before the next step overwrites it
     }
   }
@@ -2733,7 +2583,7 @@ __global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restric
     float* pp = part[wave][r];
     if (h == 0) { pp[0] = m_run; pp[1] = l_tot; }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) pp[2 + (e & 3) + 8 * (e >> 2) + 4 * h] = oacc[e];
+    for (int e = 0; e < 8; ++e) pp[2 + (e & 3) + 8 * (e >> 2) + 4 * h] = oacc[e];   // (s_frag_key here changes the listing: 2 + ... associates otherwise)
   }
   __syncthreads();
   if (tid < Lq * D) {

@@ -97,6 +97,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
   const int r = lane & 31, h = lane >> 5;
   // XCD-aware placement (as in the forward): workgroups are dealt round-robin over the 8 XCDs, each with a private L2; all owner
   // blocks of one (batch, head) stream the SAME rows, so they go to one XCD (a contiguous slice of the remapped id space).
+  // (the forward's xcd_wg_coords changes both backward kernels' listings: the decode keeps its text here)
   const int gx = gridDim.x, gy = gridDim.y;
   const int lid = xcd_tile_order(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
   const int bx = lid % gx, head = (lid / gx) % gy, b = lid / (gx * gy);
@@ -147,10 +148,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
                (ROLE == ROLE_DQ ? (uint64_t)(ovalid ? oi : 0) * (uint64_t)p.Lk : (uint64_t)(ovalid ? oi : 0));
   }
 
-  const int tiles_all = (n_str + C::BK - 1) / C::BK;
-  const int tiles_per = (tiles_all + nsplit - 1) / nsplit;
-  const int t_begin = split * tiles_per, tiles = min(tiles_all, t_begin + tiles_per);
-  if (t_begin >= tiles) return;
+  const TileRange tr = split_tiles(n_str, C::BK, nsplit, split);
+  if (tr.empty()) return;
+  const int t_begin = tr.begin, tiles = tr.end;
   uint4 r1[PER], r2[PER];
   float rs_lse = 0.f, rs_del = 0.f;
   auto gload = [&](int tile) {
@@ -262,13 +262,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const unsigned char* a0 = trb + (16 * st) * TRS + d * 64;
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * TRS));
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
-        short8_t t8;
-        t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
-        t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
-        acc[d] = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, t8), wf[st], acc[d], 0, 0, 0);
+        acc[d] = MSAM2_MFMA_32x32x16(lds_read_tr16_pair(a0, 8 * TRS), wf[st], acc[d], 0, 0, 0);
       }
     }
     if (tile + 1 < tiles) lstore(cur ^ 1);
@@ -371,6 +365,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
                (ROLE == ROLE_DQ ? (uint64_t)(ovalid ? oi : 0) * (uint64_t)p.Lk : (uint64_t)(ovalid ? oi : 0));
   }
 
+  // (split_tiles, same formula: it changes this kernel's listing, the range keeps its text)
   const int tiles_all = (n_str + BK - 1) / BK;
   const int tiles_per = (tiles_all + nsplit - 1) / nsplit;
   const int t_begin = split * tiles_per, t_end = min(tiles_all, t_begin + tiles_per);
@@ -493,15 +488,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dma_kernel(AttnBwdParams 
     for (int d = 0; d < DBLK; ++d) {
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
-        typedef __attribute__((ext_vector_type(8))) short short8_t;
         const int cch = (d * 4 + v_c0) ^ v_sw;
         const unsigned char* a0 = imgt + v_row + (16 * st) * RB + (cch << 4);
-        const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-        const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-        short8_t t8;
-        t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
-        t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
-        acc[d] = MSAM2_MFMA_32x32x16(__builtin_bit_cast(op16x8, t8), wf[st], acc[d], 0, 0, 0);
+        acc[d] = MSAM2_MFMA_32x32x16(lds_read_tr16_pair(a0, 8 * RB), wf[st], acc[d], 0, 0, 0);
       }
     }
   };

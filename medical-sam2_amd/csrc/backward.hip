@@ -99,14 +99,7 @@ __global__ __launch_bounds__(256) void gemm_tt_kernel(GemmTTParams p) {
   // transposed-read lane offsets (same pattern as the attention kernels' V^T fragments): rows = k, columns = m / n
   const int tr_off = (4 * h + (li >> 2)) * TT_PITCH + (16 * ((lane >> 4) & 1) + 4 * (li & 3)) * 2;
   auto frag = [&](const unsigned char* slab, int st, int col0) -> op16x8 {
-    const unsigned char* a0 = slab + tr_off + (16 * st) * TT_PITCH + col0 * 2;
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * TT_PITCH));
-    typedef __attribute__((ext_vector_type(8))) short short8_t;
-    short8_t t8;
-    t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
-    t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
-    return __builtin_bit_cast(op16x8, t8);
+    return lds_read_tr16_pair(slab + tr_off + (16 * st) * TT_PITCH + col0 * 2, 8 * TT_PITCH);
   };
   gload(kt0);
   lstore(0);
@@ -213,15 +206,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   const int vq = li >> 2, vp = li & 3, cgrp = (lane >> 4) & 1;
   const int t_row = (4 * h + vq) * RB + ((vp & 1) << 3);
   const int t_sw = vq << 2, t_c0 = 2 * cgrp + (vp >> 1);
-  typedef __attribute__((ext_vector_type(8))) short short8_t;
   auto frag = [&](const unsigned char* slab, int ks, int cb) -> op16x8 {
-    const unsigned char* a0 = slab + t_row + (16 * ks) * RB + (((cb * 4 + t_c0) ^ t_sw) << 4);
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 8 * RB));
-    short8_t t8;
-    t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
-    t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
-    return __builtin_bit_cast(op16x8, t8);
+    return lds_read_tr16_pair(slab + t_row + (16 * ks) * RB + (((cb * 4 + t_c0) ^ t_sw) << 4), 8 * RB);
   };
 
 #pragma unroll

@@ -19,6 +19,7 @@ typedef __attribute__((ext_vector_type(8))) op16 op16x8;
 typedef __attribute__((ext_vector_type(4))) op16 op16x4;
 typedef __attribute__((ext_vector_type(2))) op16 op16x2;
 typedef __attribute__((ext_vector_type(4))) short short4_t;
+typedef __attribute__((ext_vector_type(8))) short short8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -134,6 +135,38 @@ __device__ __forceinline__ void glds16x3_asm(__amdgpu_buffer_rsrc_t rsrc, const 
 __device__ __forceinline__ int xcd_tile_order(int id, int n) {
   const int q = n / 8, rem = n % 8, xcd = id % 8;
   return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + id / 8;
+}
+
+// Which tiles of BK rows does split `split` of `splits` own, of n rows in all?  Tiles [begin, end); [begin, full_end) are whole, and
+// end - 1 is the partial last tile iff the range is not empty and full_end < end (only the last live split can own it).
+// Every split gets ceil(tiles / splits) tiles, so a trailing split is EMPTY whenever (splits - 1) * ceil(tiles / splits) >= tiles.  The
+// hosts rule that out for a row count they know (attn_effective_splits, g96x2_applies); a key count read on the device
+// (AttnParams::lk_dev) below the capacity the split count was sized for brings it back.  Then end = tiles < begin: test empty() /
+// partial_tail() / count() <= 0, never full_end < end alone (min(end, n / BK) < end also holds for an empty range behind a partial
+// tile, which would be taken a second time).  An empty split must report (max = -inf, sum = 0, O' = 0); the merge gives it weight 0.
+struct TileRange {
+  int begin, end, full_end;
+  __device__ __forceinline__ int count() const { return end - begin; }   // <= 0: empty
+  __device__ __forceinline__ bool empty() const { return begin >= end; }
+  __device__ __forceinline__ bool partial_tail() const { return begin < end && full_end < end; }
+};
+__device__ __forceinline__ TileRange split_tiles(int n, int BK, int splits, int split) {
+  const int tiles_total = (n + BK - 1) / BK;
+  const int tiles_per = (tiles_total + splits - 1) / splits;
+  const int begin = split * tiles_per;
+  const int end = min(tiles_total, begin + tiles_per);
+  return {begin, end, min(end, n / BK)};
+}
+
+// Transposed 16-bit fragment of a row-major LDS tile (A operand of O^T += V^T P^T and of the transposed-B GEMMs): two ds_read_b64_tr_b16,
+// the second `hi_bytes` (8 rows, or 4 of a 16-row k-step image) behind the first, packed into the eight k-slots of a 32x32x16 operand.
+__device__ __forceinline__ op16x8 lds_read_tr16_pair(const unsigned char* a0, int hi_bytes) {
+  const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
+  const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + hi_bytes));
+  short8_t t8;
+  t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
+  t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
+  return __builtin_bit_cast(op16x8, t8);
 }
 
 // Raw buffer descriptor over `bytes` bytes at p: stride 0 (raw addressing, offset = voffset + soffset), num_records = bytes -- a lane

@@ -1853,15 +1853,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
   const int vq = li >> 2, vp = li & 3, cgrp = (lane >> 4) & 1;
   const int t_row = (8 * h + vq) * 256 + ((vp & 1) << 3);
   const int t_sw = vq << 2, t_c0 = 2 * cgrp + (vp >> 1);
-  typedef __attribute__((ext_vector_type(8))) short short8_t;
   auto bfrag = [&](const unsigned char* slab, int ks, int cb) -> op16x8 {
-    const unsigned char* a0 = slab + t_row + (16 * ks) * 256 + (((cb * 4 + t_c0) ^ t_sw) << 4);
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0));
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3)))*)(a0 + 4 * 256));
-    short8_t t8;
-    t8[0] = lo[0]; t8[1] = lo[1]; t8[2] = lo[2]; t8[3] = lo[3];
-    t8[4] = hi[0]; t8[5] = hi[1]; t8[6] = hi[2]; t8[7] = hi[3];
-    return __builtin_bit_cast(op16x8, t8);
+    return lds_read_tr16_pair(slab + t_row + (16 * ks) * 256 + (((cb * 4 + t_c0) ^ t_sw) << 4), 4 * 256);
   };
 
   const int nk = p.K / BK;

@@ -2,7 +2,10 @@
 `-S --cuda-device-only`, normalises the listings (comments, .file / .loc / .ident, debug sections and the per-translation-unit
 __hip_cuid_<hash> symbol dropped) and compares them line for line: every instruction, every .amdhsa_ field, the set of kernel symbols.
 A listing is kept beside its source (isa/ or isa_bf16/, ignored by git) and reused while no source or header is newer.
-usage: python tools/isa_diff.py <parent-tree> <new-tree> [--bf16]   ->  per source file `identical` or the first differing kernel."""
+Three verdicts per source file: `identical`; `operand order only` (same line counts, and the listings become equal once the two source
+operands of every instruction in COMMUTATIVE are put in one order -- the kernels it concerns are named); DIFFERS with the first
+differing kernel.  Exit status 0 iff no file DIFFERS.
+usage: python tools/isa_diff.py <parent-tree> <new-tree> [--bf16]"""
 import os
 import re
 import subprocess
@@ -13,6 +16,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa_scan import kernels  # noqa: E402
 
 CSRC = os.path.join("medical-sam2_amd", "csrc")
+# Two-source opcodes whose result bits do not depend on the order of the sources (the compiler picks the order from value numbering,
+# which moving code into a helper can change).  Extend only with such opcodes, and only as they show up.  Caveat:
+# v_mul_f32 of two NaNs propagates the payload of one source -- which one depends on the order.
+COMMUTATIVE = ("s_add_i32", "s_mul_i32", "v_mul_f32_e32")
+COMMUTATIVE_RE = re.compile(r"^(\s*(?:%s)\s+[^,]+),\s*([^,]+),\s*([^,]+)$" % "|".join(COMMUTATIVE))
 
 
 def make_var(makefile, name):
@@ -47,21 +55,33 @@ def normalised(path):
     return "\n".join(keep) + "\n"
 
 
+def canonical(line):
+    m = COMMUTATIVE_RE.match(line)
+    return "%s, %s, %s" % ((m.group(1),) + tuple(sorted(m.group(2, 3)))) if m else line
+
+
 def compare(a, b):
     if a == b:
         return "identical (%d lines)" % a.count("\n")
     ka, kb = (dict(kernels(re.sub(r"^(_Z\w+):$", r"\1: ", t, flags=re.M))) for t in (a, b))
     if set(ka) != set(kb):
         return "kernel symbols differ: only in parent %s, only in new %s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))
+    swapped = []
     for name in ka:
         if ka[name] != kb[name]:
+            if len(ka[name]) == len(kb[name]) and [canonical(l) for l in ka[name]] == [canonical(l) for l in kb[name]]:
+                swapped.append(name)
+                continue
             n = next((i for i, (x, y) in enumerate(zip(ka[name], kb[name])) if x != y), min(len(ka[name]), len(kb[name])))
             return "DIFFERS: %s at its line %d (%d / %d lines)" % (name, n, len(ka[name]), len(kb[name]))
-    return "DIFFERS outside the kernel bodies (metadata or .amdhsa_ fields)"
+    if [canonical(l) for l in a.split("\n")] != [canonical(l) for l in b.split("\n")]:
+        return "DIFFERS outside the kernel bodies (metadata or .amdhsa_ fields)"
+    return "operand order only (%s) in %d of %d kernels, the others identical:\n  %s" % (
+        ", ".join(COMMUTATIVE), len(swapped), len(ka), "\n  ".join(swapped))
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--bf16"]
+    args = [os.path.abspath(a) for a in sys.argv[1:] if a != "--bf16"]   # (the compiler runs inside csrc/)
     bf16 = "--bf16" in sys.argv
     if len(args) != 2:
         sys.exit(__doc__)
@@ -71,7 +91,7 @@ def main():
         bad = 0
         for s in srcs:
             verdict = compare(normalised(jobs[args[0], s].result()), normalised(jobs[args[1], s].result()))
-            bad += not verdict.startswith("identical")
+            bad += verdict.startswith("DIFFERS") or verdict.startswith("kernel symbols differ")
             print("%-20s %s" % (s, verdict), flush=True)
     sys.exit(1 if bad else 0)
 
