@@ -116,6 +116,13 @@ SIGNATURES = {
     "msam2_mask_rle": (c_i, [c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_p, c_p]),
     "msam2_box_nms_workspace_bytes": (c_z, [c_l]),
     "msam2_box_nms": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_z, c_p]),
+    "msam2_bank_dots_chain": (c_i, [c_l, c_i]),
+    "msam2_bank_dots_workspace_bytes": (c_z, [c_l, c_l]),
+    "msam2_bank_dots": (c_i, [c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_z, c_p]),
+    "msam2_bank_sample": (c_i, [c_p, c_l, c_p, c_p, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_p, c_p]),
+    "msam2_bank_gather": (c_i, [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_p, c_p, c_p]),
+    "msam2_bank_decide": (c_i, [c_p, c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_p]),
+    "msam2_bank_commit": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

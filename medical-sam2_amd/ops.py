@@ -802,3 +802,122 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
     check(lib().msam2_box_nms(_p(b), _p(s), K, _f32_below(iou_threshold), _p(keep), _p(n_keep), _p(ws), nb, _stream()))
     return keep[: int(n_keep.item())]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
+# arbitrary strides, read in place.
+BANK_MAX = 32          # physical slots the device tables are laid out for
+BANK_MAX_ROWS = 8      # candidates / images of a step
+
+
+def _bank_operand(t: torch.Tensor, what: str):
+    _req(t.dim() == 3 and t.dtype == F32, f"{what}: fp32 [rows, n_ch, n_px] view")
+    return _p(t), (ctypes.c_int64 * 3)(*t.stride())
+
+
+def bank_dots_chain(K: int, vec: int) -> int:
+    """n of the bound |computed - exact| <= gamma_n sum|x_i y_i| of bank_dots for rows of K elements read `vec` (1 / 4) at a time."""
+    return lib().msam2_bank_dots_chain(int(K), int(vec))
+
+
+def bank_dots_workspace(R: int, Cn: int, device) -> torch.Tensor:
+    return torch.empty(max(lib().msam2_bank_dots_workspace_bytes(R, Cn), 4) // 4, dtype=F32, device=device)
+
+
+def bank_dots(x: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None, *, dots: Optional[torch.Tensor] = None,
+              xx: Optional[torch.Tensor] = None, yy: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """dots [R, Cn] = X Y^T over the flattened (n_ch, n_px) maps, Y = rows of y then rows of y2; xx [R], yy [Cn] squared norms
+    (written when given).  Returns dots."""
+    px, sx = _bank_operand(x, "bank_dots x")
+    py, sy = _bank_operand(y, "bank_dots y")
+    R, n_ch, n_px = x.shape
+    rows_a = y.shape[0]
+    _req(tuple(y.shape[1:]) == (n_ch, n_px), "bank_dots: y rows differ in shape from x rows")
+    py2, sy2, rows_b = None, None, 0
+    if y2 is not None:
+        py2, sy2 = _bank_operand(y2, "bank_dots y2")
+        rows_b = y2.shape[0]
+        _req(tuple(y2.shape[1:]) == (n_ch, n_px), "bank_dots: y2 rows differ in shape from x rows")
+    Cn = rows_a + rows_b
+    if dots is None:
+        dots = torch.empty(R, Cn, dtype=F32, device=x.device)
+    _req(dots.dtype == F32 and dots.is_contiguous() and dots.numel() >= R * Cn, "bank_dots: dots fp32 contiguous [R, Cn]")
+    if workspace is None:
+        workspace = bank_dots_workspace(R, Cn, x.device)
+    check(lib().msam2_bank_dots(px, sx, R, py, sy, rows_a, py2, sy2, rows_b, n_ch, n_px, _p(dots), _p(xx), _p(yy), _p(workspace),
+                                workspace.numel() * 4, _stream()))
+    return dots
+
+
+def bank_sample(dots: torch.Tensor, xx: torch.Tensor, yy: torch.Tensor, order: torch.Tensor, N: int, cap: int, u: torch.Tensor,
+                indices: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 indices [B, S] (logical bank positions) drawn by inverse CDF with the uniforms u [B, S] from softmax(cosines)."""
+    _req(dots.dim() == 2 and dots.dtype == F32 and dots.stride(1) == 1 and u.dim() == 2 and u.dtype == F32 and u.is_contiguous(),
+         "bank_sample: dots fp32 [B, >= cap], u fp32 contiguous [B, S]")
+    _req(order.dtype == torch.int32 and order.numel() >= BANK_MAX, "bank_sample: order int32 [32]")
+    B, S = u.shape
+    _req(dots.shape[0] == B and dots.shape[1] >= N, "bank_sample: dots rows / columns")
+    if indices is None:
+        indices = torch.empty(B, S, dtype=torch.int32, device=u.device)
+    # the kernel indexes dots by physical slot < cap; a [B, N] tensor (live slots are 0 .. N-1) is addressed with cap = N
+    cap_k = min(int(cap), dots.shape[1])
+    check(lib().msam2_bank_sample(_p(dots), dots.stride(0), _p(xx), _p(yy), _p(order), int(N), cap_k, _p(u), B, S, _p(indices), _p(probs),
+                                  _stream()))
+    return indices
+
+
+def bank_gather(feats: torch.Tensor, pos: torch.Tensor, order: torch.Tensor, indices: torch.Tensor, N: int,
+                memory: Optional[torch.Tensor] = None, memory_pos: Optional[torch.Tensor] = None):
+    """feats / pos: the bank's token-major stores [cap, HW, C]; indices int32 [B, S] -> memory, memory_pos [S*HW, B, C]."""
+    _req(feats.dim() == 3 and feats.is_contiguous() and pos.shape == feats.shape and pos.is_contiguous() and feats.dtype == F32 and pos.dtype == F32,
+         "bank_gather: fp32 contiguous stores [cap, HW, C]")
+    _req(indices.dtype == torch.int32 and indices.is_contiguous() and indices.dim() == 2, "bank_gather: indices int32 [B, S]")
+    cap, HW, C = feats.shape
+    B, S = indices.shape
+    if memory is None:
+        memory = torch.empty(S * HW, B, C, dtype=F32, device=feats.device)
+    if memory_pos is None:
+        memory_pos = torch.empty(S * HW, B, C, dtype=F32, device=feats.device)
+    _req(memory.is_contiguous() and memory_pos.is_contiguous() and memory.numel() == S * HW * B * C and memory_pos.numel() == memory.numel(),
+         "bank_gather: outputs fp32 contiguous [S*HW, B, C]")
+    check(lib().msam2_bank_gather(_p(feats), _p(pos), _p(order), _p(indices), B, S, HW, C, int(N), cap, _p(memory), _p(memory_pos), _stream()))
+    return memory, memory_pos
+
+
+def bank_decide(gram: torch.Tensor, iou_bank: torch.Tensor, order: torch.Tensor, N: int, cap: int, dots: torch.Tensor,
+                iou_pred: torch.Tensor, fill: bool, accept: Optional[torch.Tensor] = None, slot_cand: Optional[torch.Tensor] = None,
+                iou_out: Optional[torch.Tensor] = None):
+    """Runs the replacement (or fill) loop on the device tables in place; returns (accept int32 [B], slot_cand int32 [32])."""
+    _req(gram.dtype == F32 and gram.is_contiguous() and gram.numel() == BANK_MAX * BANK_MAX, "bank_decide: gram fp32 [32, 32]")
+    _req(iou_bank.dtype == F32 and iou_bank.numel() == BANK_MAX and order.dtype == torch.int32 and order.numel() == BANK_MAX,
+         "bank_decide: iou_bank fp32 [32], order int32 [32]")
+    _req(iou_pred.dim() == 2 and iou_pred.dtype == F32 and iou_pred.is_contiguous(), "bank_decide: iou_pred fp32 contiguous [B, M]")
+    B, M = iou_pred.shape
+    _req(dots.dtype == F32 and dots.is_contiguous() and dots.numel() >= B * (N + B), "bank_decide: dots fp32 contiguous [B, N + B]")
+    if accept is None:
+        accept = torch.empty(B, dtype=torch.int32, device=gram.device)
+    if slot_cand is None:
+        slot_cand = torch.empty(BANK_MAX, dtype=torch.int32, device=gram.device)
+    check(lib().msam2_bank_decide(_p(gram), _p(iou_bank), _p(order), int(N), int(cap), _p(dots), _p(iou_pred), B, M, 1 if fill else 0, _p(accept),
+                                  _p(slot_cand), _p(iou_out), _stream()))
+    return accept, slot_cand
+
+
+def bank_commit(slot_cand: torch.Tensor, feats: torch.Tensor, pos: torch.Tensor, embed: torch.Tensor, feats_store: torch.Tensor,
+                pos_store: torch.Tensor, embed_store: torch.Tensor) -> None:
+    """feats / pos [B, C, HW] and embed [B, Ce, HW] views (any strides) -> the slots slot_cand names: token-major feats_store / pos_store
+    [cap, HW, C], embed_store [cap, Ce*HW] in (channel, pixel) order."""
+    pf, sf = _bank_operand(feats, "bank_commit feats")
+    pp, sp = _bank_operand(pos, "bank_commit pos")
+    pe, se = _bank_operand(embed, "bank_commit embed")
+    B, C, HW = feats.shape
+    Ce = embed.shape[1]
+    cap = feats_store.shape[0]
+    _req(pos.shape == feats.shape and embed.shape[0] == B and embed.shape[2] == HW, "bank_commit: candidate shapes")
+    _req(feats_store.is_contiguous() and pos_store.is_contiguous() and embed_store.is_contiguous() and feats_store.numel() == cap * HW * C
+         and pos_store.numel() == cap * HW * C and embed_store.numel() == cap * Ce * HW and feats_store.dtype == F32 and pos_store.dtype == F32
+         and embed_store.dtype == F32, "bank_commit: fp32 contiguous stores [cap, HW, C], [cap, HW, C], [cap, Ce*HW]")
+    _req(slot_cand.dtype == torch.int32 and slot_cand.numel() >= cap, "bank_commit: slot_cand int32 [32]")
+    check(lib().msam2_bank_commit(_p(slot_cand), cap, pf, sf, pp, sp, C, pe, se, Ce, HW, B, _p(feats_store), _p(pos_store), _p(embed_store),
+                                  _stream()))

@@ -102,6 +102,13 @@ DOC = {
     "msam2_mask_rle": "Pass 2: uncompressed RLE of (up-sampled logits > thr) in the reference's format -- column-major over the (H, W) frame, counts\nstarting with a 0 when the first pixel is set -- written as int32 at counts[offsets[m] .. offsets[m+1]) (offsets int64 [M + 1], the\nexclusive scan of msam2_mask_rle_runs); one workgroup per mask, ballot-ordered compaction, deterministic.",
     "msam2_box_nms_workspace_bytes": "Scratch (rank order + K x ceil(K/64) IoU bitmask) for msam2_box_nms.",
     "msam2_box_nms": "Greedy NMS with torchvision.ops.nms semantics (automatic_mask_generator.py's batched_nms with one category): boxes fp32 [K, 4] xyxy\n(16-byte aligned), scores fp32 [K]; ranks by score descending, ties to the lower input index (stable); IoU = inter / (area_a + area_b -\ninter) in fp32; a box is suppressed by a kept higher-ranked box with IoU > iou_thr.  keep int64 [K]: input indices of the kept boxes in\nrank order, n_keep int32 [1] their number.  K <= 65536 (the workspace is then 512 MiB).",
+    "msam2_bank_dots_chain": "Length n of the longest chain of roundings behind one msam2_bank_dots value for rows of K elements read `vec` (1 or 4) at a time:\n|computed - exact| <= gamma_n sum_i |x_i y_i| (the thread's sequential fma chain plus the depth of the fixed reduction tree).",
+    "msam2_bank_dots_workspace_bytes": "Scratch (fp32 partials of the K split) for msam2_bank_dots.",
+    "msam2_bank_dots": "The dot products behind both halves of the 2-D memory bank (func_2d/function.py:102-107 F.normalize + torch.mm of the draw, 216-231 of the\nreplacement) in one pass over the operands, fp32: dots [R, rows_a + rows_b] = X Y^T, xx [R] and yy [rows] the squared norms (optional).\nEvery row is a [n_ch, n_px] map in the logical flat order (channel, pixel); *_strides: HOST pointers to 3 element strides {row, channel,\npixel}, so token-major views and contiguous rows are read in place.  Y rows come from two operands (the bank's storage, then the\ncandidates of the step).  R <= 8, rows <= 32.  K is split over up to 512 workgroups, partials are summed in a fixed order (no atomics):\nbit-reproducible.",
+    "msam2_bank_sample": "The draw of func_2d/function.py:105-110 with caller-supplied uniforms in place of torch.multinomial's stream: cosines from raw dots\n[B, ld] (column = physical slot) and squared norms with F.normalize's eps = 1e-12 clamp, softmax over the N live entries in logical order\n(order: int32 [32], logical -> physical slot), inclusive CDF, indices int32 [B, S] = first n with u[b][s] < cdf[b][n].  probs [B, N] optional.",
+    "msam2_bank_gather": "memory / memory_pos fp32 [S*HW, B, C] as func_2d/function.py:112-116 builds them, from the bank's token-major slots [cap, HW, C] and the\nindices of msam2_bank_sample on the device (resolved through `order`); one read and one write per element.",
+    "msam2_bank_decide": "The replacement loop of func_2d/function.py:205-243 for the B candidates of a step, one wave on device tables: gram fp32 [32][32] (raw\ndots of the stored memory features by physical slot, squared norms on the diagonal), iou_bank fp32 [32], order int32 [32].  dots [B, N + B]:\ncandidates against slots 0 .. N-1, then against each other.  iou = mean_b max_m iou_pred[b][m]; per candidate i = argmin cos(entry, cand),\nj = argmax_{n != i} cos(entry i, entry n), accepted iff cos_i < cos_ij and iou > iou_bank[j] - 0.1: logical pop(j) + append, tables updated in\nplace (ties: first index).  fill != 0: every candidate is appended (205-210).  accept int32 [B]; slot_cand int32 [32]: per physical slot the\nlast candidate assigned to it, or -1; iou_out [1] optional.",
+    "msam2_bank_commit": "Copies every candidate named by slot_cand (msam2_bank_decide, read on the device) into its slot: features and position encoding to the\ntoken-major stores [cap, HW, C], the image embedding to [cap, Ce*HW] in (channel, pixel) flat order -- the order func_2d/function.py:210\nstores and :102-107 compare against.  Sources by HOST strides {row, channel, pixel}.  Workgroups of unnamed slots exit.",
     "msam2_cc_workspace_bytes": "Scratch (union-find parents + area histogram) for msam2_cc_label.",
     "msam2_cc_label": "Drop-in for the reference's only native op, `_C.get_connected_componnets` (sam2_train/csrc/connected_components.cu:\n213-282; Python wrapper utils/misc.py:47-63): 8-connected labels (1 + smallest 2x2-block corner index of the component)\nand per-pixel component areas for uint8 masks [N,1,H,W], H and W even.  The caller allocates labels/counts/workspace.",
     "msam2_fill_holes_workspace_bytes": "Scratch for msam2_fill_holes.",
@@ -119,7 +126,7 @@ DOC = {
 
 def main():
     decls = []
-    for f in ["api.hip", "gemm.hip", "attention.hip", "attention_bwd.hip", "elementwise.hip", "conv.hip", "cc.hip", "backward.hip", "mlp_fused.hip", "amg.hip"]:
+    for f in ["api.hip", "gemm.hip", "attention.hip", "attention_bwd.hip", "elementwise.hip", "conv.hip", "cc.hip", "backward.hip", "mlp_fused.hip", "amg.hip", "bank.hip"]:
         s = open(os.path.join(CSRC, f)).read()
         for m in re.finditer(r'extern "C" ([^{;]+?)\s*\{', s, re.S):
             decls.append(" ".join(m.group(1).split()))
