@@ -1,0 +1,243 @@
+// End of the 3-D path: label volumes and per-organ counts straight from the low-resolution logits [T, n, lh, lw] fp32 that
+// volume.segment_volume returns, gfx950.
+//
+// The composition this replaces up-samples every slice to video resolution (n x H x W fp32 written and read back: 54.5 MB per slice for 13
+// organs at 1024^2), takes the per-pixel arg-max with torch reductions and scores every (slice, object) with a call and a host copy of
+// its own.  Here one kernel re-evaluates the bilinear resize (align_corners = False) per output voxel, as mask_stats_kernel (amg.hip)
+// does, with the ROUNDINGS of the kernel msam2_bilinear_upsample would run for the same output size (resize_taps / resize_value below),
+// so every label and every count equals, integer for integer, the one taken from msam2_bilinear_upsample's output, and no high-res
+// logits exist: a slice reads n x lh x lw floats (L2-resident) and writes one byte per voxel.  Counters are integers (ballot / popcount
+// per wave, LDS, one global atomic per workgroup and counter): exact and independent of order.
+#include "common.h"
+
+namespace {
+
+// ---- the per-pixel value of msam2_bilinear_upsample, rounding for rounding ------------------------------------------------------------
+// Siblings: bilinear_kernel / bilinear4_kernel (elementwise.hip) and bilerp_at (amg.hip) all spell the same expression,
+//   (1 - ly) * ((1 - lx) * a + lx * b) + ly * ((1 - lx) * c + lx * d),      a b = row y0, c d = row y1,
+// and leave its contraction into fused multiply-adds to the compiler (hipcc's default -ffp-contract=fast).  Which products get fused is
+// then decided per kernel by the vectoriser, and the listings (tools/isa_diff.py keeps them) show that the siblings do NOT agree in the
+// last bit:
+//   * bilinear4_kernel (W % 4 == 0, what msam2_bilinear_upsample runs for every size of the 3-D path), pixel X:
+//       B = fma(1 - lx, c, lx * d)  in both cases;
+//       X even:  A = fma(1 - lx, a, lx * b),  v = fma(ly, B, (1 - ly) * A);
+//       X odd:   A = fma(lx, b, (1 - lx) * a),  v = fma(1 - ly, A, ly * B);
+//   * bilinear_kernel when every thread has one pixel (W % 4 != 0 and planes * H * W <= 2^22; bilerp_at in mask_stats_kernel compiles to
+//     the same):  A = fma(lx, b, (1 - lx) * a),  B as above,  v = (1 - ly) * A + ly * B  with both products rounded;
+//   * bilinear_kernel beyond 2^22 output elements runs a two-pixel body with a third pattern for the threads that have two pixels and
+//     the one above for the rest: the bits of a pixel then depend on the launch, and no per-pixel function can follow them.
+// A label or a count differs between two such forms only where a value lies within an ulp of a threshold or of another object's value,
+// which a test meets once in ~10^8 comparisons; "equal, integer for integer" has to hold by construction, so this file does not share the
+// spelled-out expression: it states the fused multiply-adds explicitly, contraction off, in the form of the kernel that
+// msam2_bilinear_upsample runs for the same W (first form for W % 4 == 0, second otherwise).  tests/test_volume_labels_gpu.py compares
+// against msam2_bilinear_upsample's output for both.  If elementwise.hip or the compiler changes those kernels' contraction, that test
+// is what notices.
+struct ResizeTaps {            // what a pixel's value needs besides the plane: independent of the object, hoisted out of its loop
+  int o00, o01, o10, o11;      // element offsets of a, b, c, d in a plane
+  float lx, mx, ly, my;        // mx = 1 - lx, my = 1 - ly
+};
+
+__device__ __forceinline__ ResizeTaps resize_taps(int h, int w, float sy, float sx, int Y, int X) {
+#pragma clang fp contract(off)
+  const float fy = fmaxf(__builtin_fmaf(Y + 0.5f, sy, -0.5f), 0.f), fx = fmaxf(__builtin_fmaf(X + 0.5f, sx, -0.5f), 0.f);
+  const int y0 = (int)fy, x0 = (int)fx;
+  const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+  ResizeTaps t;
+  t.o00 = y0 * w + x0;
+  t.o01 = y0 * w + x1;
+  t.o10 = y1 * w + x0;
+  t.o11 = y1 * w + x1;
+  t.ly = fy - y0;
+  t.lx = fx - x0;
+  t.my = 1.f - t.ly;
+  t.mx = 1.f - t.lx;
+  return t;
+}
+
+// vec4_form: the roundings of bilinear4_kernel (W % 4 == 0), else those of the one-pixel path of bilinear_kernel; odd = X & 1
+__device__ __forceinline__ float resize_value(const float* __restrict__ p, const ResizeTaps& t, bool vec4_form, bool odd) {
+#pragma clang fp contract(off)
+  const float a = p[t.o00], b = p[t.o01], c = p[t.o10], d = p[t.o11];
+  const float B = __builtin_fmaf(t.mx, c, t.lx * d);
+  const float A_first = __builtin_fmaf(t.mx, a, t.lx * b), A_second = __builtin_fmaf(t.lx, b, t.mx * a);
+  const float even4 = __builtin_fmaf(t.ly, B, t.my * A_first), odd4 = __builtin_fmaf(t.my, A_second, t.ly * B);
+  const float one = t.my * A_second + t.ly * B;
+  return vec4_form ? (odd ? odd4 : even4) : one;
+}
+
+constexpr int LBL_THREADS = 256, LBL_ITER = 4;          // voxel groups per thread: a workgroup owns 1024 groups of VPT voxels of one slice
+constexpr int LBL_MAX_OBJ = 32, LBL_MAX_THR = 8;
+
+// Counts of one object over the VPT voxels of each lane of this wave, added to the workgroup's LDS counters c[k * kstride + (0, 1, 2)] =
+// (|P & G|, |P|, |G|) of threshold k.  P = in && v > th[k]; the ballots are wave-uniform, so are the branches around the LDS atomics.
+template <int VPT>
+__device__ __forceinline__ void tally_object(int* c, int kstride, const float (&v)[VPT], const bool (&in)[VPT], const bool (&g)[VPT],
+                                             const float (&th)[LBL_MAX_THR], int K, bool lane0) {
+  unsigned long long mg[VPT];
+  int cg = 0;
+#pragma unroll
+  for (int e = 0; e < VPT; ++e) {
+    mg[e] = __ballot(g[e]);
+    cg += __popcll(mg[e]);
+  }
+#pragma unroll
+  for (int k = 0; k < LBL_MAX_THR; ++k) {
+    if (k >= K) break;
+    int cp = 0, ci = 0;
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+      const unsigned long long mp = __ballot(in[e] && v[e] > th[k]);
+      cp += __popcll(mp);
+      ci += __popcll(mp & mg[e]);
+    }
+    if (lane0) {
+      if (ci) atomicAdd(c + k * kstride + 0, ci);
+      if (cp) atomicAdd(c + k * kstride + 1, cp);
+      if (cg) atomicAdd(c + k * kstride + 2, cg);
+    }
+  }
+}
+
+// One thread: VPT consecutive X of one row (VPT = 4 needs W % 4 == 0 and 4-byte aligned labels / gt: one 4-byte load and store), the
+// object loop innermost, so a voxel's n values never leave the registers; the taps and weights do not depend on the object.
+// VPT = 4: the form of a pixel's value is known at compile time (W % 4 == 0, parity of e); VPT = 1 also serves W % 4 == 0 with unaligned
+// labels / gt, so it selects per lane.  blockIdx.y = slice.  labels / gt / counts may each be null (the host entry checks which).
+template <int VPT, bool COUNT>
+__global__ __launch_bounds__(LBL_THREADS) void label_slices_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ ids, int n,
+                                                                   int lh, int lw, int H, int W, float label_thr,
+                                                                   const float* __restrict__ thr, int K, const uint8_t* __restrict__ gt,
+                                                                   int exclusive, uint8_t* __restrict__ labels, int* __restrict__ counts,
+                                                                   int T) {
+  const int t = blockIdx.y;
+  const int plane = lh * lw;
+  const float* base = logits + (int64_t)t * n * plane;
+  const float sy = (float)lh / H, sx = (float)lw / W;
+  const int Wg = W / VPT, groups = H * Wg;                  // H * W < 2^31 (host)
+  const int64_t slice = (int64_t)t * H * W;
+  const bool lane0 = (threadIdx.x & 63) == 0;
+  __shared__ int cnt[COUNT ? LBL_MAX_THR * LBL_MAX_OBJ * 3 : 1];
+  float th[LBL_MAX_THR];
+  if (COUNT) {
+#pragma unroll
+    for (int k = 0; k < LBL_MAX_THR; ++k) th[k] = k < K ? thr[k] : INFINITY;
+    for (int i = threadIdx.x; i < K * n * 3; i += LBL_THREADS) cnt[i] = 0;
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int it = 0; it < LBL_ITER; ++it) {
+    const int64_t gi = ((int64_t)blockIdx.x * LBL_ITER + it) * LBL_THREADS + threadIdx.x;
+    const bool live = gi < groups;
+    const int g = live ? (int)gi : groups - 1;               // dead lanes recompute the last group (no divergent loads), masked below
+    const int Y = g / Wg, X0 = (g - Y * Wg) * VPT;
+    uint8_t gb[VPT];
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) gb[e] = 0;
+    const bool has_gt = COUNT && gt != nullptr;
+    if (has_gt) {
+      if (VPT == 4) {
+        const unsigned u = *reinterpret_cast<const unsigned*>(gt + slice + (int64_t)g * 4);
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) gb[e] = (uint8_t)(u >> (8 * e));
+      } else {
+        gb[0] = gt[slice + g];
+      }
+    }
+    float bv[VPT];
+    int bo[VPT];
+    bool in[VPT], gbit[VPT];
+    ResizeTaps taps[VPT];
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+      bv[e] = label_thr;
+      bo[e] = -1;
+      in[e] = live;
+      taps[e] = resize_taps(lh, lw, sy, sx, Y, X0 + e);
+    }
+    const bool vec4_form = VPT == 4 || (W & 3) == 0;
+    for (int o = 0; o < n; ++o) {
+      const float* p = base + (int64_t)o * plane;
+      float v[VPT];
+#pragma unroll
+      for (int e = 0; e < VPT; ++e) {
+        v[e] = resize_value(p, taps[e], vec4_form, VPT == 4 ? (e & 1) != 0 : (X0 & 1) != 0);
+        if (v[e] > bv[e]) {                                   // strict: ties to the lower index, background at exactly label_thr, NaN never wins
+          bv[e] = v[e];
+          bo[e] = o;
+        }
+      }
+      if (COUNT && !exclusive) {
+        const uint8_t id = ids[o];
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) gbit[e] = live && has_gt && gb[e] == id;
+        tally_object<VPT>(cnt + o * 3, n * 3, v, in, gbit, th, K, lane0);
+      }
+    }
+    if (COUNT && exclusive) {
+      for (int o = 0; o < n; ++o) {
+        const uint8_t id = ids[o];
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) {
+          gbit[e] = live && has_gt && gb[e] == id;
+          in[e] = live && bo[e] == o;
+        }
+        tally_object<VPT>(cnt + o * 3, n * 3, bv, in, gbit, th, K, lane0);
+      }
+    }
+    if (labels != nullptr && live) {
+      if (VPT == 4) {
+        unsigned u = 0;
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) u |= (unsigned)(bo[e] >= 0 ? ids[bo[e]] : (uint8_t)0) << (8 * e);
+        *reinterpret_cast<unsigned*>(labels + slice + (int64_t)g * 4) = u;
+      } else {
+        labels[slice + g] = bo[0] >= 0 ? ids[bo[0]] : (uint8_t)0;
+      }
+    }
+  }
+  if (COUNT) {
+    __syncthreads();
+    const int per_k = n * 3;
+    for (int i = threadIdx.x; i < K * per_k; i += LBL_THREADS) {
+      const int c = cnt[i];
+      const int k = i / per_k;
+      if (c) atomicAdd(counts + ((int64_t)k * T + t) * per_k + (i - k * per_k), c);
+    }
+  }
+}
+
+template <int VPT, bool COUNT>
+void launch_label_slices(hipStream_t s, const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H,
+                         int64_t W, float label_thr, const float* thr, int64_t K, const uint8_t* gt, int exclusive, uint8_t* labels,
+                         int* counts) {
+  const int64_t groups = H * (W / VPT), per = (int64_t)LBL_THREADS * LBL_ITER;
+  hipLaunchKernelGGL((label_slices_kernel<VPT, COUNT>), dim3((unsigned)((groups + per - 1) / per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits,
+                     ids, (int)n, (int)lh, (int)lw, (int)H, (int)W, label_thr, thr, (int)K, gt, exclusive, labels, counts, (int)T);
+}
+
+}  // namespace
+
+extern "C" int msam2_label_slices(const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H, int64_t W,
+                                  float label_thr, const float* thresholds, int64_t K, const uint8_t* gt, int exclusive, uint8_t* labels,
+                                  int* counts, void* stream) {
+  MSAM2_REQUIRE(logits && ids, "label_slices: null logits / ids");
+  MSAM2_REQUIRE(n >= 1 && n <= LBL_MAX_OBJ, "label_slices: n = %lld objects (1 .. %d per call)", (long long)n, LBL_MAX_OBJ);
+  MSAM2_REQUIRE(K >= 0 && K <= LBL_MAX_THR, "label_slices: K = %lld thresholds (at most %d per call)", (long long)K, LBL_MAX_THR);
+  MSAM2_REQUIRE(T >= 1 && T <= 65535 && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
+                "label_slices: bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)T, (long long)lh, (long long)lw, (long long)H,
+                (long long)W);
+  MSAM2_REQUIRE(labels || counts, "label_slices: neither labels nor counts requested");
+  MSAM2_REQUIRE(!counts || (K >= 1 && thresholds), "label_slices: counts need 1 .. %d thresholds", LBL_MAX_THR);
+  hipStream_t s = (hipStream_t)stream;
+  if (counts && hipMemsetAsync(counts, 0, (size_t)(K * T * n * 3) * sizeof(int), s) != hipSuccess)
+    return msam2_check_launch("label_slices (memset)");
+  const uint8_t* g = counts ? gt : nullptr;
+  const bool vec4 = W % 4 == 0 && (((uintptr_t)labels | (uintptr_t)g) & 3) == 0;
+  if (vec4) {
+    if (counts) launch_label_slices<4, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
+    else launch_label_slices<4, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
+  } else {
+    if (counts) launch_label_slices<1, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
+    else launch_label_slices<1, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
+  }
+  return msam2_check_launch("label_slices");
+}

@@ -28,9 +28,10 @@ def seg_counts(pred: torch.Tensor, true_mask_p: torch.Tensor, threshold) -> np.n
     return torch.cat(out).view(len(th), b, c, 3).cpu().numpy().astype(np.int64)
 
 
-def eval_seg(pred: torch.Tensor, true_mask_p: torch.Tensor, threshold):
-    """Drop-in for the reference's eval_seg: pred / true_mask_p [b, c, h, w] on the GPU, threshold = iterable of floats."""
-    k = seg_counts(pred, true_mask_p, threshold)
+def scores_from_counts(k: np.ndarray):
+    """eval_seg's arithmetic on int64 counts [T, b, c, 3] = (|P & G|, |P|, |G|): IoU with the reference's 1e-6 smoothing in float64 (numpy in
+    the reference), Dice with its 1e-4 smoothing in a float32 running sum (dice_coeff), both averaged over the batch and the thresholds.
+    Returns the two lists of c per-class floats (ious, dices).  Shared with volume_labels.volume_scores."""
     T, b, c, _ = k.shape
     inter, ps, gs = k[..., 0], k[..., 1], k[..., 2]
     union = ps + gs - inter
@@ -43,6 +44,12 @@ def eval_seg(pred: torch.Tensor, true_mask_p: torch.Tensor, threshold):
     dice = dice / np.float32(b)
     ious = [float(iou[:, i].sum()) / T for i in range(c)]
     dices = [float(dice[:, i].astype(np.float64).sum()) / T for i in range(c)]
-    if c == 1:
+    return ious, dices
+
+
+def eval_seg(pred: torch.Tensor, true_mask_p: torch.Tensor, threshold):
+    """Drop-in for the reference's eval_seg: pred / true_mask_p [b, c, h, w] on the GPU, threshold = iterable of floats."""
+    ious, dices = scores_from_counts(seg_counts(pred, true_mask_p, threshold))
+    if len(ious) == 1:
         return ious[0], dices[0]
     return tuple(np.array(ious + dices))

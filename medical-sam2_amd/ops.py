@@ -805,6 +805,57 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# end of the 3-D path: label volumes and per-organ counts from low-res logits (csrc/volume_labels.hip)
+LABEL_MAX_OBJECTS = 32
+LABEL_MAX_THRESHOLDS = 8
+
+
+def label_ids(ids, device) -> torch.Tensor:
+    """Label values of the objects as the uint8 [n] device tensor label_slices takes: checked on the host (integers 1 .. 255, distinct)."""
+    vals = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+    _req(len(vals) >= 1 and all(1 <= v <= 255 for v in vals), "label_slices: ids must be integers in 1 .. 255 (0 is the background)")
+    _req(len(set(vals)) == len(vals), "label_slices: ids must be distinct")
+    return torch.tensor(vals, dtype=torch.uint8).to(device)
+
+
+def label_slices(logits: torch.Tensor, ids, H: int, W: int, label_thr: float = 0.0, gt: Optional[torch.Tensor] = None, thresholds=None,
+                 exclusive: bool = False, labels=True):
+    """fp32 [T, n, lh, lw] low-res logits -> (labels uint8 [T, H, W] | None, counts int32 [K, T, n, 3] | None) of their (H, W) bilinear
+    resize, which is never written: labels = ids[o] of the highest-scoring object above label_thr per voxel (ties to the lower index,
+    0 = background); counts = (|P & G|, |P|, |G|) per threshold, slice and object, P = v_o > threshold (exclusive: and o is the voxel's
+    label), G = gt == ids[o] (gt uint8 [T, H, W]; without it only |P| is filled).  counts are returned iff thresholds are given
+    (at most 8 per call, rounded to fp32 as metrics.seg_counts passes them); labels=False skips the label volume, a uint8 contiguous
+    [T, H, W] tensor is filled in place.
+    ids: host integers (checked: distinct, 1 .. 255), or the device tensor of label_ids() taken as is.  Nothing is copied to the host."""
+    _req(logits.dtype == F32 and logits.is_contiguous() and logits.dim() == 4, "label_slices: fp32 contiguous [T, n, lh, lw]")
+    T, n, lh, lw = logits.shape
+    dev = logits.device
+    on_dev = isinstance(ids, torch.Tensor) and ids.device == dev and dev.type != "cpu"
+    ids_d = ids.contiguous() if on_dev else label_ids(ids, dev)
+    _req(ids_d.dtype == torch.uint8 and ids_d.numel() == n, f"label_slices: {n} objects need {n} uint8 ids")
+    H, W = int(H), int(W)
+    thr_d = counts = out = None
+    K = 0
+    if thresholds is not None:
+        thr_d = thresholds if isinstance(thresholds, torch.Tensor) else torch.tensor([float(t) for t in thresholds], dtype=F32)
+        thr_d = thr_d.to(device=dev, dtype=F32).contiguous()
+        K = thr_d.numel()
+        counts = torch.empty(K, T, n, 3, dtype=torch.int32, device=dev)
+    if gt is not None:
+        _req(gt.dtype == torch.uint8 and gt.is_contiguous() and tuple(gt.shape) == (T, H, W) and gt.device == dev,
+             f"label_slices: gt must be uint8 contiguous [{T}, {H}, {W}] on the logits' device")
+    if isinstance(labels, torch.Tensor):
+        _req(labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (T, H, W) and labels.device == dev,
+             f"label_slices: labels must be uint8 contiguous [{T}, {H}, {W}] on the logits' device")
+        out = labels
+    elif labels:
+        out = torch.empty(T, H, W, dtype=torch.uint8, device=dev)
+    check(lib().msam2_label_slices(_p(logits), _p(ids_d), T, n, lh, lw, H, W, _f32(label_thr), _p(thr_d), K, _p(gt), int(bool(exclusive)),
+                                   _p(out), _p(counts), _stream()))
+    return out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
 # arbitrary strides, read in place.
 BANK_MAX = 32          # physical slots the device tables are laid out for

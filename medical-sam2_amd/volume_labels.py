@@ -1,0 +1,117 @@
+"""End of the 3-D path: from the low-res logits that `volume.segment_volume` returns to a label volume (one uint8 per voxel: organ id or 0)
+and per-organ scores against a ground-truth label volume, without ever writing the up-sampled logits.
+
+The reference's validation (`func_3d/function.py:215-330`) up-samples every slice's logits to video resolution and scores every
+(slice, object) pair with an `eval_seg` call of its own (one device-to-host copy each).  Here `ops.label_slices` (csrc/volume_labels.hip)
+re-evaluates the bilinear resize per voxel, `label_volume` feeds it the slices chunk by chunk, and the counts of the whole volume
+[K, T, n, 3] cross to the host once, in `volume_scores`.
+
+Label rule (per voxel): the highest-scoring object above `label_thr` (0: the mask threshold of the video predictor), ties to the lower
+object index, 0 = background -- the per-pixel rule of the reference's non-overlapping constraint (`sam2_base.py:812-830`) applied at
+video resolution.  Counts are taken per object on its own (`exclusive=False`: what the reference's validation scores) or on the label
+volume (`exclusive=True`)."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import ops
+from .metrics import scores_from_counts
+
+F32 = torch.float32
+REFERENCE_THRESHOLDS = (0.1, 0.3, 0.5, 0.7, 0.9)
+
+
+def _chunk(masks, order, i: int, j: int) -> torch.Tensor:
+    """slices order[i:j] as one contiguous fp32 [j - i, n, h, w] tensor (the only copy of logits this module makes)"""
+    if isinstance(masks, torch.Tensor):
+        return masks[i:j].to(F32).contiguous()
+    return torch.stack([masks[t][:, 0] for t in order[i:j]]).to(F32).contiguous()
+
+
+@torch.no_grad()
+def label_volume(masks: Union[Dict[int, torch.Tensor], torch.Tensor], H: int, W: int, obj_ids: Optional[Sequence[int]] = None,
+                 gt: Optional[torch.Tensor] = None, thresholds=REFERENCE_THRESHOLDS, exclusive: bool = False, slices_per_call: int = 8,
+                 label_thr: float = 0.0):
+    """masks: {slice: [n, 1, h, w]} as `segment_volume` returns it (slices in ascending key order) or a [T, n, h, w] tensor, on the GPU.
+    obj_ids: the label value of each object (default 1 .. n; distinct, 1 .. 255).  Returns labels uint8 [T, H, W] on the device; with
+    gt (uint8 [T, H, W] label volume, e.g. `labels_from_pack`) returns (labels, counts): counts int32 [K, T, n, 3] on the device =
+    (|P & G|, |P|, |G|) per threshold, slice and object (see `ops.label_slices`), for `volume_scores`.  The slices go through
+    `slices_per_call` at a time, so no copy of the logits is larger than one chunk; nothing is copied to the host."""
+    if isinstance(masks, torch.Tensor):
+        assert masks.dim() == 4, "masks: [T, n, h, w]"
+        order, T, n, dev = None, masks.shape[0], masks.shape[1], masks.device
+    else:
+        order = sorted(masks)
+        first = masks[order[0]]
+        assert first.dim() == 4 and first.shape[1] == 1, "masks: {slice: [n, 1, h, w]}"
+        T, n, dev = len(order), first.shape[0], first.device
+    H, W = int(H), int(W)
+    ids = ops.label_ids(list(range(1, n + 1)) if obj_ids is None else obj_ids, dev)
+    assert ids.numel() == n, f"{n} objects need {n} ids"
+    labels = torch.empty(T, H, W, dtype=torch.uint8, device=dev)
+    counts, thr = None, []
+    if gt is not None:
+        assert gt.dtype == torch.uint8 and tuple(gt.shape) == (T, H, W), f"gt: uint8 [{T}, {H}, {W}]"
+        gt = gt.to(dev).contiguous()
+        thr = [float(t) for t in thresholds]
+        assert thr, "scores need at least one threshold"
+        counts = torch.empty(len(thr), T, n, 3, dtype=torch.int32, device=dev)
+    step = max(1, int(slices_per_call))
+    for i in range(0, T, step):
+        j = min(T, i + step)
+        x = _chunk(masks, order, i, j)
+        if counts is None:
+            ops.label_slices(x, ids, H, W, label_thr, labels=labels[i:j])
+            continue
+        for k in range(0, len(thr), ops.LABEL_MAX_THRESHOLDS):            # at most 8 thresholds per launch; the labels with the first
+            part = thr[k: k + ops.LABEL_MAX_THRESHOLDS]
+            _, c = ops.label_slices(x, ids, H, W, label_thr, gt=gt[i:j], thresholds=part, exclusive=exclusive,
+                                    labels=labels[i:j] if k == 0 else False)
+            counts[k: k + len(part), i:j] = c
+    return labels if counts is None else (labels, counts)
+
+
+def volume_scores(counts) -> dict:
+    """Scores from `label_volume`'s counts [K, T, n, 3] (device tensor: the one device-to-host copy of the path; or a numpy array).
+
+    * "iou", "dice": the reference's validation figures (`func_3d/function.py:300-330`): the mean over (slice, object) of eval_seg's
+      threshold-averaged IoU / Dice -- the arithmetic, smoothing constants and float types of `metrics.eval_seg` (shared code);
+      "iou_per_pair" / "dice_per_pair" [T, n] hold what eval_seg returns for each pair.
+    * "volume_dice", "volume_iou" float64 [K, n]: per organ and threshold from the counts summed over the slices in int64,
+      2 I / (P + G) and I / (P + G - I); NaN where an organ is neither predicted nor present."""
+    k = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    k = k.astype(np.int64)
+    K, T, n, _ = k.shape
+    ious, dices = scores_from_counts(k.reshape(K, 1, T * n, 3))           # every (slice, object) as eval_seg sees it: b = c = 1
+    iou = dice = 0.0
+    for a, b in zip(ious, dices):                                         # the running sums of validate_volume, in its order
+        iou, dice = iou + a, dice + b
+    vol = k.sum(axis=1)                                                   # [K, n, 3] int64
+    inter, ps, gs = (vol[..., i].astype(np.float64) for i in range(3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v_dice = 2.0 * inter / (ps + gs)
+        v_iou = inter / (ps + gs - inter)
+    return {"iou": iou / (T * n), "dice": dice / (T * n),
+            "iou_per_pair": np.array(ious, dtype=np.float64).reshape(T, n), "dice_per_pair": np.array(dices, dtype=np.float64).reshape(T, n),
+            "volume_dice": v_dice, "volume_iou": v_iou}
+
+
+def labels_from_pack(label: Dict[int, Dict[int, torch.Tensor]], obj_list: Sequence[int], device=None) -> torch.Tensor:
+    """The data contract's ground truth (`data.BTCVVolumes[i]["label"]`: {frame: {obj: [1, S, S] int mask}}, frames 0 .. T-1) as one uint8
+    [T, S, S] label volume: voxel = obj where that object's mask is set, 0 elsewhere (where masks overlap, the object later in obj_list).
+    Built on the host, moved to `device` in one copy."""
+    frames = sorted(label)
+    assert frames == list(range(len(frames))), "frames must be 0 .. T-1"
+    assert all(1 <= int(o) <= 255 for o in obj_list), "object ids must be 1 .. 255"
+    shape = next((tuple(m.shape[-2:]) for f in frames for m in label[f].values()), None)
+    assert shape is not None, "no mask in the pack"
+    vol = torch.zeros(len(frames), *shape, dtype=torch.uint8)
+    for f in frames:
+        for o in obj_list:
+            m = label[f].get(o)
+            if m is not None:
+                vol[f][torch.as_tensor(m).reshape(shape) > 0] = int(o)
+    return vol if device is None else vol.to(device)
