@@ -856,6 +856,65 @@ def label_slices(logits: torch.Tensor, ids, H: int, W: int, label_thr: float = 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# start of the 3-D path: box and click prompts from a label volume (csrc/prompts.hip)
+LABEL_MAX_SLICES = 65535
+LABEL_MAX_SIDE = 8192
+
+
+def _label_volume_args(what: str, labels: torch.Tensor, ids):
+    """the checks label_stats and label_pick share -> (ids on the device, D, H, W, n)"""
+    _req(isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(),
+         f"{what}: labels must be a uint8 contiguous [D, H, W] label volume")
+    D, H, W = labels.shape
+    _req(1 <= D <= LABEL_MAX_SLICES and 1 <= H <= LABEL_MAX_SIDE and 1 <= W <= LABEL_MAX_SIDE,
+         f"{what}: sizes {D} x {H} x {W} (1 .. {LABEL_MAX_SLICES} slices of 1 .. {LABEL_MAX_SIDE} rows and columns)")
+    dev = labels.device
+    on_dev = isinstance(ids, torch.Tensor) and ids.device == dev and dev.type != "cpu"
+    ids_d = ids.contiguous() if on_dev else label_ids(ids, dev)
+    n = ids_d.numel()
+    _req(ids_d.dtype == torch.uint8 and ids_d.dim() == 1 and 1 <= n <= LABEL_MAX_OBJECTS,
+         f"{what}: ids must be 1 .. {LABEL_MAX_OBJECTS} uint8 label values, got {n}")
+    _req(labels.is_cuda, f"{what}: the label volume must be on the GPU")
+    return ids_d, D, H, W, n
+
+
+def label_stats(labels: torch.Tensor, ids, rows: Optional[torch.Tensor] = None):
+    """uint8 [D, H, W] label volume -> (stats int32 [D, n, 5], rows int32 [D, n, H]): stats = (count, r0, r1, c0, c1), the number of
+    voxels equal to ids[j] in slice d and their inclusive row / column extent ((0, -1, -1, -1, -1) where the object is absent); rows =
+    the count per row, the workspace label_pick reads (pass one of that shape to reuse it).  Voxels that are 0 or not in ids are ignored.
+    ids: host integers (checked: distinct, 1 .. 255), or the device tensor of label_ids() taken as is.  Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_stats", labels, ids)
+    dev = labels.device
+    if rows is None:
+        rows = torch.empty(D, n, H, dtype=torch.int32, device=dev)
+    _req(rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (D, n, H) and rows.device == dev,
+         f"label_stats: rows must be int32 contiguous [{D}, {n}, {H}] on the labels' device")
+    stats = torch.empty(D, n, 5, dtype=torch.int32, device=dev)
+    check(lib().msam2_label_stats(_p(labels), _p(ids_d), D, H, W, n, _p(stats), _p(rows), _stream()))
+    return stats, rows
+
+
+def label_pick(labels: torch.Tensor, ids, stats: torch.Tensor, rows: torch.Tensor, k: Optional[torch.Tensor] = None,
+               u: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """xy int32 [D, n, 2] = (column, row) of the k-th voxel of object j in slice d in raster order (np.argwhere's), from the volume and
+    label_stats' two tables.  k int32 [D, n]: explicit indices; or u uint32 [D, n] (int32 is taken as the same 32 bits): uniform random
+    words, k = (u * count) >> 32.  (-1, -1) where the object is absent; k outside [0, count) is clamped to count - 1."""
+    ids_d, D, H, W, n = _label_volume_args("label_pick", labels, ids)
+    dev = labels.device
+    _req((k is None) != (u is None), "label_pick: exactly one of k and u")
+    _req(stats.dtype == torch.int32 and stats.is_contiguous() and tuple(stats.shape) == (D, n, 5) and stats.device == dev,
+         f"label_pick: stats must be int32 contiguous [{D}, {n}, 5] on the labels' device")
+    _req(rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (D, n, H) and rows.device == dev,
+         f"label_pick: rows must be int32 contiguous [{D}, {n}, {H}] on the labels' device")
+    t = k if u is None else u
+    _req(t.dtype in ((torch.int32,) if u is None else (torch.uint32, torch.int32)) and t.is_contiguous() and tuple(t.shape) == (D, n)
+         and t.device == dev, f"label_pick: {'k must be int32' if u is None else 'u must be uint32'} contiguous [{D}, {n}] on the labels' device")
+    xy = torch.empty(D, n, 2, dtype=torch.int32, device=dev)
+    check(lib().msam2_label_pick(_p(labels), _p(ids_d), _p(stats), _p(rows), _p(k), _p(u), D, H, W, n, _p(xy), _stream()))
+    return xy
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
 # arbitrary strides, read in place.
 BANK_MAX = 32          # physical slots the device tables are laid out for
