@@ -126,6 +126,11 @@ SIGNATURES = {
     "msam2_label_slices": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_p, c_i, c_p, c_p, c_p]),
     "msam2_label_stats": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p]),
     "msam2_label_pick": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    "msam2_label_components_workspace_bytes": (c_z, [c_l, c_l, c_l]),
+    "msam2_label_components": (c_i, [c_p, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_z, c_p]),
+    "msam2_label_clean_workspace_bytes": (c_z, [c_l]),
+    "msam2_label_clean": (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, ctypes.c_uint32, c_p, c_p, c_p, c_z, c_l, c_l, c_l, c_p]),
+    "msam2_label_overlap": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

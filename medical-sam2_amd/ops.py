@@ -862,18 +862,20 @@ LABEL_MAX_SIDE = 8192
 
 
 def _label_volume_args(what: str, labels: torch.Tensor, ids):
-    """the checks label_stats and label_pick share -> (ids on the device, D, H, W, n)"""
+    """the checks the entries on label volumes share -> (ids on the device, D, H, W, n)"""
     _req(isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(),
          f"{what}: labels must be a uint8 contiguous [D, H, W] label volume")
     D, H, W = labels.shape
     _req(1 <= D <= LABEL_MAX_SLICES and 1 <= H <= LABEL_MAX_SIDE and 1 <= W <= LABEL_MAX_SIDE,
          f"{what}: sizes {D} x {H} x {W} (1 .. {LABEL_MAX_SLICES} slices of 1 .. {LABEL_MAX_SIDE} rows and columns)")
     dev = labels.device
-    on_dev = isinstance(ids, torch.Tensor) and ids.device == dev and dev.type != "cpu"
-    ids_d = ids.contiguous() if on_dev else label_ids(ids, dev)
-    n = ids_d.numel()
-    _req(ids_d.dtype == torch.uint8 and ids_d.dim() == 1 and 1 <= n <= LABEL_MAX_OBJECTS,
-         f"{what}: ids must be 1 .. {LABEL_MAX_OBJECTS} uint8 label values, got {n}")
+    ids_d, n = None, 0
+    if ids is not None:                                    # (label_components takes no ids)
+        on_dev = isinstance(ids, torch.Tensor) and ids.device == dev and dev.type != "cpu"
+        ids_d = ids.contiguous() if on_dev else label_ids(ids, dev)
+        n = ids_d.numel()
+        _req(ids_d.dtype == torch.uint8 and ids_d.dim() == 1 and 1 <= n <= LABEL_MAX_OBJECTS,
+             f"{what}: ids must be 1 .. {LABEL_MAX_OBJECTS} uint8 label values, got {n}")
     _req(labels.is_cuda, f"{what}: the label volume must be on the GPU")
     return ids_d, D, H, W, n
 
@@ -912,6 +914,86 @@ def label_pick(labels: torch.Tensor, ids, stats: torch.Tensor, rows: torch.Tenso
     xy = torch.empty(D, n, 2, dtype=torch.int32, device=dev)
     check(lib().msam2_label_pick(_p(labels), _p(ids_d), _p(stats), _p(rows), _p(k), _p(u), D, H, W, n, _p(xy), _stream()))
     return xy
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# between the two: connected components, island removal and overlap counts of label volumes (csrc/components.hip)
+LABEL_CONNECTIVITIES = (4, 8, 6, 18, 26)
+LABEL_MAX_VOXELS = 2 ** 31 - 2
+
+
+def _label_table(what: str, name: str, t: torch.Tensor, like: torch.Tensor, dtype=torch.int32):
+    _req(isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.shape == like.shape and t.device == like.device,
+         f"{what}: {name} must be {str(dtype).split('.')[-1]} contiguous {list(like.shape)} on the labels' device")
+
+
+def label_components(labels: torch.Tensor, connectivity: int = 26):
+    """uint8 [D, H, W] label volume -> (comp, size), both int32 [D, H, W].  Two voxels are adjacent iff they carry the same non-zero value
+    and differ by one offset of the neighbourhood: connectivity 6 / 18 / 26 in 3-D, 4 / 8 in plane (every slice on its own).  comp = 0 on
+    the background, else 1 + the smallest linear index of the voxel's component; size = the component's voxel count at that smallest voxel,
+    0 elsewhere.  All 255 values are handled at once.  Nothing is copied to the host."""
+    _req(int(connectivity) in LABEL_CONNECTIVITIES, f"label_components: connectivity {connectivity} (one of {LABEL_CONNECTIVITIES})")
+    _, D, H, W, _ = _label_volume_args("label_components", labels, None)
+    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_components: {D * H * W} voxels (at most 2^31 - 2)")
+    dev = labels.device
+    comp = torch.empty(D, H, W, dtype=torch.int32, device=dev)
+    size = torch.empty_like(comp)
+    nb = lib().msam2_label_components_workspace_bytes(D, H, W)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    check(lib().msam2_label_components(_p(labels), D, H, W, int(connectivity), _p(comp), _p(size), _p(ws), nb, _stream()))
+    return comp, size
+
+
+def label_largest_mask(keep_largest, n: int) -> int:
+    """keep_largest (one bool, or one per object) as the bit mask msam2_label_clean takes"""
+    if isinstance(keep_largest, (bool, int)):
+        return (2 ** n - 1) if keep_largest else 0
+    flags = [bool(f) for f in keep_largest]
+    _req(len(flags) == n, f"label_clean: keep_largest names {len(flags)} objects, ids {n}")
+    return sum(1 << j for j, f in enumerate(flags) if f)
+
+
+def label_clean(labels: torch.Tensor, comp: torch.Tensor, size: torch.Tensor, ids, min_voxels=None, keep_largest=True,
+                out: Optional[torch.Tensor] = None):
+    """Island removal with label_components' tables -> (out uint8 [D, H, W], info int32 [n, 6]).  A component of value ids[j] is kept iff
+    its size >= max(1, min_voxels[j]) and (keep_largest[j] is false or it is the largest of that value: ties to the smaller canonical
+    index; a largest one below min_voxels[j] leaves nothing).  Voxels that are 0 or not in ids stay.  min_voxels: None, one int, a sequence
+    or an int32 device tensor [n]; keep_largest: one bool or one per object; out: None (a new volume), or a uint8 volume to fill -- labels
+    itself for in place.  info = (components found, voxels found, largest size, its canonical name or 0, components kept, voxels kept).
+    Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_clean", labels, ids)
+    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_clean: {D * H * W} voxels (at most 2^31 - 2)")
+    dev = labels.device
+    _label_table("label_clean", "comp", comp, labels)
+    _label_table("label_clean", "size", size, labels)
+    mask = label_largest_mask(keep_largest, n)
+    mv = None
+    if isinstance(min_voxels, torch.Tensor):
+        mv = min_voxels.to(device=dev, dtype=torch.int32).contiguous()
+        _req(mv.shape == (n,), f"label_clean: min_voxels must hold {n} values")
+    elif min_voxels is not None:
+        vals = [int(min_voxels)] * n if isinstance(min_voxels, int) else [int(v) for v in min_voxels]
+        _req(len(vals) == n and all(0 <= v < 2 ** 31 for v in vals), f"label_clean: min_voxels must be {n} counts in 0 .. 2^31 - 1")
+        mv = torch.tensor(vals, dtype=torch.int32).to(dev) if any(vals) else None
+    if out is None:
+        out = torch.empty_like(labels)
+    _label_table("label_clean", "out", out, labels, torch.uint8)
+    info = torch.empty(n, 6, dtype=torch.int32, device=dev)
+    nb = lib().msam2_label_clean_workspace_bytes(n)
+    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().msam2_label_clean(_p(labels), _p(comp), _p(size), _p(ids_d), n, _p(mv), mask, _p(out), _p(info), _p(ws), nb, D, H, W, _stream()))
+    return out, info
+
+
+def label_overlap(pred: torch.Tensor, gt: torch.Tensor, ids) -> torch.Tensor:
+    """counts int32 [D, n, 3] = (|P & G|, |P|, |G|) per slice and object, P = pred == ids[j], G = gt == ids[j], of two uint8 [D, H, W] label
+    volumes: the triple label_slices gives with exclusive=True at one threshold.  Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_overlap", pred, ids)
+    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_overlap: {D * H * W} voxels (at most 2^31 - 2)")
+    _label_table("label_overlap", "gt", gt, pred, torch.uint8)
+    counts = torch.empty(D, n, 3, dtype=torch.int32, device=pred.device)
+    check(lib().msam2_label_overlap(_p(pred), _p(gt), _p(ids_d), D, H, W, n, _p(counts), _stream()))
+    return counts
 
 
 # ---------------------------------------------------------------------------------------------------------------------

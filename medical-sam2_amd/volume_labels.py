@@ -115,3 +115,33 @@ def labels_from_pack(label: Dict[int, Dict[int, torch.Tensor]], obj_list: Sequen
             if m is not None:
                 vol[f][torch.as_tensor(m).reshape(shape) > 0] = int(o)
     return vol if device is None else vol.to(device)
+
+
+@torch.no_grad()
+def clean_labels(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, connectivity: int = 26, keep_largest=True, min_voxels=0,
+                 in_place: bool = False, n: Optional[int] = None):
+    """Island removal between `label_volume` and the scores: the components of every listed value of the uint8 [T, H, W] label volume
+    (`ops.label_components`: 6 / 18 / 26 in 3-D, 4 / 8 slice by slice), of which only the largest per value (`keep_largest`) with at least
+    `min_voxels` voxels survive (`ops.label_clean`); voxels of other values stay.  keep_largest / min_voxels: one value, or one per object.
+    obj_ids: the label values (distinct, 1 .. 255; a device tensor of `ops.label_ids` is taken as is); None = 1 .. n with `n` given by the
+    caller -- the volume is never scanned on the host.  Returns (cleaned uint8 [T, H, W], info int32 [n, 6]) on the device, info =
+    (components found, voxels found, largest size, its canonical name or 0, components kept, voxels kept); in_place=True overwrites labels."""
+    if obj_ids is None:
+        assert n is not None and int(n) >= 1, "clean_labels: without obj_ids the number of objects n is needed (the volume is not scanned)"
+        obj_ids = list(range(1, int(n) + 1))
+    dev = labels.device
+    on_dev = isinstance(obj_ids, torch.Tensor) and obj_ids.device == dev and dev.type != "cpu"
+    ids = obj_ids if on_dev else ops.label_ids(obj_ids, dev)
+    assert n is None or ids.numel() == int(n), f"clean_labels: {ids.numel()} ids for n = {n}"
+    comp, size = ops.label_components(labels, connectivity)
+    mv = None if isinstance(min_voxels, int) and min_voxels == 0 else min_voxels
+    return ops.label_clean(labels, comp, size, ids, min_voxels=mv, keep_largest=keep_largest, out=labels if in_place else None)
+
+
+@torch.no_grad()
+def label_scores(pred: torch.Tensor, gt: torch.Tensor, obj_ids) -> dict:
+    """Scores of a label volume (e.g. `clean_labels`' output) against the ground-truth label volume, both uint8 [T, H, W] on the device:
+    `ops.label_overlap`'s counts [T, n, 3] as `volume_scores`' [1, T, n, 3] -- its keys and arithmetic at K = 1 (a label volume has no
+    threshold left), with the path's one device-to-host copy inside it."""
+    counts = ops.label_overlap(pred, gt, obj_ids)
+    return volume_scores(counts[None])
