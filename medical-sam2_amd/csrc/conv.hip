@@ -248,6 +248,7 @@ extern "C" int msam2_im2col3x3s2(const void* x, void* out, int64_t B, int64_t H,
                 "im2col3x3s2: bad arguments");
   const int64_t total = B * (H / 2) * (W / 2) * (ld / 4);
   MSAM2_REQUIRE(total < (1ll << 31), "im2col3x3s2: more than 2^31 output groups");
+  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 7) == 0, "im2col3x3s2: x and out must be 8-byte aligned (4-channel groups)");
   hipLaunchKernelGGL(im2col3x3s2_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, (const op16*)x, (op16*)out, (int)B, (int)H, (int)W, (int)C, (int)ld);
   return msam2_check_launch("im2col3x3s2");
@@ -400,6 +401,9 @@ extern "C" int msam2_dwconv7x7_ln(const float* x, const float* weight_tap_major,
                                   const float* ln_b, void* y, int64_t B, int64_t H, int64_t W, int64_t C, void* stream) {
   MSAM2_REQUIRE(x && weight_tap_major && bias && ln_w && ln_b && y, "dwconv7x7_ln: null tensor");
   MSAM2_REQUIRE(C == 256, "dwconv7x7_ln: built for C=256 (one wave per pixel group, 4 channels per lane)");
+  MSAM2_REQUIRE(B > 0 && H > 0 && W > 0, "dwconv7x7_ln: bad shape");
+  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)weight_tap_major | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0,
+                "dwconv7x7_ln: x, weight and bias must be 16-byte aligned, y 8-byte aligned (4-channel groups)");
   const int64_t groups = B * H * ((W + DW_PIX - 1) / DW_PIX);
   hipLaunchKernelGGL(dwconv7x7_ln_kernel, dim3(cdiv(groups * 64, 256)), dim3(256), 0, (hipStream_t)stream, x, weight_tap_major, bias,
                      ln_w, ln_b, (op16*)y, (int)B, (int)H, (int)W, (int)C);
@@ -596,6 +600,7 @@ extern "C" int msam2_hyper_masks(const float* hyper, const void* upscaled, float
                                  void* stream) {
   MSAM2_REQUIRE(hyper && upscaled && masks, "hyper_masks: null tensor");
   MSAM2_REQUIRE(C == 32 && K > 0 && K <= 8 && n > 0 && P > 0, "hyper_masks: built for C=32, K<=8");
+  MSAM2_REQUIRE(((uintptr_t)upscaled & 15) == 0, "hyper_masks: the up-scaled features must be 16-byte aligned (8-channel loads)");
   hipLaunchKernelGGL(hyper_masks_kernel, dim3(cdiv(P, 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, hyper,
                      (const op16*)upscaled, masks, (int)n, (int)K, (int)P, (int)C);
   return msam2_check_launch("hyper_masks");

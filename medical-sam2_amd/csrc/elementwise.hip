@@ -154,7 +154,10 @@ extern "C" int msam2_layernorm(const void* x, int in_is_16bit, int64_t ldx, cons
   MSAM2_REQUIRE(x && y && weight && bias, "layernorm: null tensor");
   MSAM2_REQUIRE(rows > 0 && C > 0 && C <= 1024, "layernorm: rows=%lld C=%lld unsupported (C<=1024)", (long long)rows, (long long)C);
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 7) == 0) &&
+  // the vector kernel moves four elements per access: 16 bytes of fp32, 8 bytes of the 16-bit type -- x and y must be aligned to the width
+  // of their own access (an fp32 y that is only 8-byte aligned takes the scalar kernel: tests/test_pointwise_variants_gpu.py::test_layernorm_scalar_paths)
+  const uintptr_t xmask = in_is_16bit ? 7 : 15, ymask = out_is_16bit ? 7 : 15;
+  const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x & xmask) == 0) && (((uintptr_t)y & ymask) == 0) &&
                    (((uintptr_t)weight & 15) == 0) && (((uintptr_t)bias & 15) == 0);
   if (vec) {
     dim3 grid(cdiv(rows * 16, 256)), block(256);
@@ -324,7 +327,7 @@ __global__ void maxpool2x2_kernel(const TI* __restrict__ x, int64_t ldx, TO* __r
     const int64_t base = ((int64_t)b * H + 2 * yo) * W + 2 * xo;
     const float v0 = (float)x[base * ldx + c], v1 = (float)x[(base + 1) * ldx + c];
     const float v2 = (float)x[(base + W) * ldx + c], v3 = (float)x[(base + W + 1) * ldx + c];
-    y[(((int64_t)b * Ho + yo) * Wo + xo) * ldy + c] = (TO)fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+    y[(((int64_t)b * Ho + yo) * Wo + xo) * ldy + c] = f2out<TO>(fmaxf(fmaxf(v0, v1), fmaxf(v2, v3)));   // saturating (common.h): test_maxpool_saturates
   }
 }
 
@@ -430,8 +433,8 @@ __global__ void rope_inplace_kernel(op16* __restrict__ x, int64_t bs, int64_t ld
     const int pos = l % n_pos;
     const float c = cs[(int64_t)pos * hp + pr], s = sn[(int64_t)pos * hp + pr];
     op16x2 o;
-    o[0] = (op16)(re * c - im * s);
-    o[1] = (op16)(re * s + im * c);
+    o[0] = f2op(re * c - im * s);                              // saturating (common.h): test_rope_saturates
+    o[1] = f2op(re * s + im * c);
     *px = o;
   }
 }
@@ -450,6 +453,16 @@ extern "C" int msam2_rope_inplace(void* x, int64_t batch_stride, int64_t ld, int
 // ------------------------------------------------------------------------------------------------------------------
 // Bilinear resize, align_corners=False, fp32 planes [P, h, w] -> [P, H, W] (F.interpolate at sam2_base.py:368-373)
 // ------------------------------------------------------------------------------------------------------------------
+// One pixel from its four neighbours with every rounding spelled out: written as (1 - ly) * ((1 - lx) * a + lx * b) + ly * (...) the compiler
+// chose which product of each sum to fuse per use -- differently in the two kernels below and even between the four pixels of one
+// bilinear4 thread, so the two forms disagreed in the last bit of a quarter of the pixels
+// (tests/test_pointwise_variants_gpu.py::test_bilinear_vector_and_scalar_forms_agree).
+__device__ __forceinline__ float bilerp(float p00, float p01, float p10, float p11, float lx, float ly) {
+  const float top = __builtin_fmaf(lx, p01, (1.f - lx) * p00);
+  const float bot = __builtin_fmaf(lx, p11, (1.f - lx) * p10);
+  return __builtin_fmaf(1.f - ly, top, ly * bot);
+}
+
 __global__ void bilinear_kernel(const float* __restrict__ x, float* __restrict__ y, int P, int h, int w, int H, int W) {
   const float sy = (float)h / H, sx = (float)w / W;
   const int64_t total = (int64_t)P * H * W;
@@ -463,14 +476,12 @@ __global__ void bilinear_kernel(const float* __restrict__ x, float* __restrict__
     const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
     const float ly = fy - y0, lx = fx - x0;
     const float* p = x + (int64_t)pl * h * w;
-    const float v = (1.f - ly) * ((1.f - lx) * p[y0 * w + x0] + lx * p[y0 * w + x1]) +
-                    ly * ((1.f - lx) * p[y1 * w + x0] + lx * p[y1 * w + x1]);
-    y[i] = v;
+    y[i] = bilerp(p[y0 * w + x0], p[y0 * w + x1], p[y1 * w + x0], p[y1 * w + x1], lx, ly);
   }
 }
 
 // W % 4 == 0: four consecutive output pixels per thread, one 16-byte store (the scalar form above wrote 4 bytes per lane and did its
-// index arithmetic in 64 bits: 21.7 us for the 16.8 MB of 4 x 1024^2 masks).  Same expression per pixel as the scalar form: bit-identical.
+// index arithmetic in 64 bits: 21.7 us for the 16.8 MB of 4 x 1024^2 masks).  Same function per pixel as the scalar form (bilerp): bit-identical.
 __global__ void bilinear4_kernel(const float* __restrict__ x, float* __restrict__ y, int P, int h, int w, int H, int W) {
   const float sy = (float)h / H, sx = (float)w / W;
   const int W4 = W >> 2;
@@ -490,7 +501,7 @@ __global__ void bilinear4_kernel(const float* __restrict__ x, float* __restrict_
       const float fx = fmaxf((X + 0.5f) * sx - 0.5f, 0.f);
       const int x0 = (int)fx, x1 = min(x0 + 1, w - 1);
       const float lx = fx - x0;
-      o[e] = (1.f - ly) * ((1.f - lx) * p0[x0] + lx * p0[x1]) + ly * ((1.f - lx) * p1[x0] + lx * p1[x1]);
+      o[e] = bilerp(p0[x0], p0[x1], p1[x0], p1[x1], lx, ly);
     }
     *reinterpret_cast<f32x4*>(y + ((int64_t)pl * H + Y) * W + X4 * 4) = o;
   }
@@ -690,7 +701,9 @@ __global__ void image_prep_kernel(const uint8_t* __restrict__ img, float* __rest
     const int y0 = min((int)fy, H - 1), x0 = min((int)fx, W - 1);
     const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
     const float ly = fy - y0, lx = fx - x0;
-    auto px = [&](int y, int x) { return (float)img[((int64_t)y * W + x) * 3 + c] * (1.0f / 255.0f); };
+    // a division, as ToTensor does it: x * (1 / 255) differs from x / 255 in the last bit for 126 of the 256 pixel values
+    // (tests/test_pointwise_variants_gpu.py::test_image_prep, the identity case)
+    auto px = [&](int y, int x) { return (float)img[((int64_t)y * W + x) * 3 + c] / 255.0f; };
     const float v = (1.f - ly) * ((1.f - lx) * px(y0, x0) + lx * px(y0, x1)) + ly * ((1.f - lx) * px(y1, x0) + lx * px(y1, x1));
     const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
     out[i] = (v - mean) / sd;

@@ -521,6 +521,10 @@ def im2col3x3s2(x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
 def conv3x3s2_ln_gelu(x: torch.Tensor, B: int, H: int, W: int, weight, bias, ln_w, ln_b, mask_mode: int = 0,
                       mask_scale: float = 0.0, mask_bias: float = 0.0) -> torch.Tensor:
     cout, cin = weight.shape[0], weight.shape[1]
+    _req(x.dtype == (F32 if cin == 1 else OP16) and x.is_contiguous() and x.numel() == B * H * W * cin,
+         "conv3x3s2_ln_gelu: contiguous NHWC [B*H*W, cin], fp32 for cin = 1, 16-bit otherwise")
+    _req(all(t.dtype == F32 and t.is_contiguous() for t in (weight, bias, ln_w, ln_b)) and tuple(weight.shape[2:]) == (3, 3)
+         and bias.numel() == cout and ln_w.numel() == cout and ln_b.numel() == cout, "conv3x3s2_ln_gelu: fp32 contiguous [cout, cin, 3, 3] weight, [cout] vectors")
     y = torch.empty(B * (H // 2) * (W // 2), cout, dtype=OP16, device=x.device)
     check(lib().msam2_conv3x3s2_ln_gelu(_p(x), _is_bf16(x), _p(weight), _p(bias), _p(ln_w), _p(ln_b), _p(y), B, H, W, cin, cout,
                                         mask_mode, mask_scale, mask_bias, _stream()))
@@ -561,6 +565,8 @@ def convt2x2_shuffle_shared(g: torch.Tensor, bias, skip: torch.Tensor, ln_w, ln_
 
 def hyper_masks(hyper: torch.Tensor, up: torch.Tensor, n: int, P: int) -> torch.Tensor:
     K, C = hyper.shape[1], hyper.shape[2]
+    _req(hyper.dtype == F32 and hyper.shape[0] == n, "hyper_masks: hyper must be fp32 [n, K, C]")
+    _req(up.dtype == OP16 and up.is_contiguous() and up.numel() == n * P * C, "hyper_masks: up must be 16-bit contiguous [n*P, C]")
     masks = torch.empty(n, K, P, dtype=F32, device=up.device)
     check(lib().msam2_hyper_masks(_p(hyper.contiguous()), _p(up), _p(masks), n, K, P, C, _stream()))
     return masks
@@ -595,6 +601,9 @@ def gather_rows(x: torch.Tensor, sel: Optional[torch.Tensor], offset: int = 0) -
 
 
 def obj_ptr_mix_(ptr: torch.Tensor, obj: torch.Tensor, no_obj_ptr: torch.Tensor) -> torch.Tensor:
+    _req(ptr.dim() == 2 and ptr.dtype == F32 and ptr.is_contiguous(), "obj_ptr_mix: ptr must be fp32 contiguous [n, C]")
+    _req(obj.dtype == F32 and obj.is_contiguous() and obj.numel() == ptr.shape[0], "obj_ptr_mix: obj must be fp32 contiguous [n]")
+    _req(no_obj_ptr.dtype == F32 and no_obj_ptr.is_contiguous() and no_obj_ptr.numel() == ptr.shape[1], "obj_ptr_mix: no_obj_ptr must be fp32 contiguous [C]")
     check(lib().msam2_obj_ptr_mix(_p(ptr), _p(obj), _p(no_obj_ptr), ptr.shape[0], ptr.shape[1], _stream()))
     return ptr
 
@@ -664,6 +673,7 @@ class HipGraph:
 def space_to_depth(x: torch.Tensor, B: int, H: int, W: int, k: int) -> torch.Tensor:
     """NHWC [B*H*W, C] -> bf16 [B*(H/k)*(W/k), ld] patches with columns (ky,kx,c), ld = k*k*C rounded up to 8."""
     C = x.shape[-1]
+    _req(x.dtype in (F32, OP16) and x.is_contiguous() and x.numel() == B * H * W * C, "space_to_depth: fp32 / 16-bit contiguous NHWC [B*H*W, C]")
     ld = (k * k * C + 7) // 8 * 8
     out = torch.empty(B * (H // k) * (W // k), ld, dtype=OP16, device=x.device)
     check(lib().msam2_space_to_depth(_p(x), _is_bf16(x), _p(out), B, H, W, C, k, ld, _stream()))

@@ -130,9 +130,37 @@ def all_gather_flat(flat: torch.Tensor, world: int):
 SENT16, SENT32 = 0x7E5A, 0x7FC0DEAD            # bit patterns no kernel writes in these tests: the canaries around every output view
 
 
+# Itanium manglings of the builtin types a kernel of this library is templated on -> their demangled spelling, white space removed
+_MANGLED_TYPES = (("DF16_", "_Float16"), ("DF16b", "__bf16"), ("u6__bf16", "__bf16"), ("Dh", "__fp16"), ("f", "float"), ("d", "double"), ("i", "int"),
+                  ("j", "unsignedint"), ("l", "long"), ("m", "unsignedlong"), ("s", "short"), ("t", "unsignedshort"), ("a", "signedchar"),
+                  ("h", "unsignedchar"), ("c", "char"), ("b", "bool"))
+
+
+def _mangled_template_args(rest: str):
+    """the top-level template arguments of 'I<args>E...': integer / bool literals (Li128E, Lb1E, Lin3E) and the element types of
+    _MANGLED_TYPES, in order; parsing stops at the closing E or at the first argument of another kind"""
+    out, i = [], 1
+    while i < len(rest) and rest[i] != "E":
+        m = re.match(r"L([a-z])(n?)(\d+)E", rest[i:])
+        if m:
+            t, neg, v = m.groups()
+            out.append(("true" if v == "1" else "false") if t == "b" else ("-" if neg else "") + v)
+            i += m.end()
+            continue
+        for code, spelled in _MANGLED_TYPES:
+            if rest.startswith(code, i):
+                out.append(spelled)
+                i += len(code)
+                break
+        else:
+            break
+    return out
+
+
 def kernel_key(name: str) -> str:
     """'void gemm_kernel<128, 32, 4, 1>(GemmParams)' or its mangled form '_Z11gemm_kernelILi128ELi32ELi4ELi1EEv10GemmParams' ->
-    'gemm_kernel<128,32,4,1>'"""
+    'gemm_kernel<128,32,4,1>'; type arguments keep their demangled spelling: 'void layernorm_kernel<float, _Float16, 2>(...)' and
+    '_Z16layernorm_kernelIfDF16_Li2EEv...' -> 'layernorm_kernel<float,_Float16,2>' (__bf16 in the bf16 build)"""
     m = re.match(r"_Z(\d+)", name)
     if m:
         n = int(m.group(1))
@@ -140,10 +168,15 @@ def kernel_key(name: str) -> str:
         rest = name[m.end() + n:]
         if not rest.startswith("I"):
             return base
-        args = re.findall(r"L([ib])(\d+)E", rest[:rest.find("EE") + 1] if "EE" in rest else rest)
-        return base + "<" + ",".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args) + ">"
-    name = re.sub(r"^void ", "", name.strip())
-    return re.sub(r"\s+", "", name.split("(")[0])
+        return base + "<" + ",".join(_mangled_template_args(rest)) + ">"
+    name = re.sub(r"^void ", "", name.strip()).split("(")[0]
+    if "_Accum" in name:
+        # A C++ runtime whose demangler predates the bf16 mangling reads 'DF16b' plus the NEXT character as a fixed-point type and prints
+        # 'bool _Accum'.  Most such names then fail to demangle and arrive mangled (handled above); the ones that get through lost
+        # exactly that character: the 'f' of a following float argument, or the 'L' of a following literal 1 ('Li1E' -> 'int, E',
+        # 'Lb1E' -> 'bool, E').  Undo that.
+        name = name.replace("bool _Accum, int, E", "__bf16, 1").replace("bool _Accum, bool, E", "__bf16, true").replace("bool _Accum", "__bf16, float")
+    return re.sub(r"\s+", "", name)
 
 
 def kernels_launched(fn, prefix: str):
@@ -185,3 +218,39 @@ class Canvas:
 
     def bits(self):
         return self.buf.view(self.itype).clone()
+
+
+class Flat:
+    """a contiguous output of `shape` inside a sentinel-filled 1-D buffer (64 guard elements on either side); `offset` moves the view that
+    many elements off its 128-byte boundary (misaligned-output paths)"""
+    G = 64
+
+    def __init__(self, shape, dtype, offset=0, device="cuda"):
+        n = 1
+        for s in shape:
+            n *= s
+        es = dtype.itemsize
+        self.itype = torch.int16 if es == 2 else torch.int32
+        self.sent = SENT16 if es == 2 else SENT32
+        self.buf = torch.empty(2 * self.G + offset + n, dtype=dtype, device=device)
+        self.buf.view(self.itype).fill_(self.sent)
+        self.lo, self.hi = self.G + offset, self.G + offset + n
+        self.view = self.buf[self.lo:self.hi].view(*shape)
+
+    def sentinels_intact(self):
+        b = self.buf.view(self.itype)
+        return bool((b[:self.lo] == self.sent).all()) and bool((b[self.hi:] == self.sent).all())
+
+
+def nan_guarded(src, offset=0, guard=64):
+    """a contiguous copy of src inside a 1-D buffer with `guard` NaN elements (0xFF bytes for integer types) on either side, `offset` elements
+    off the buffer's alignment: a kernel that reads past either end of the tensor returns NaN"""
+    n = src.numel()
+    buf = torch.empty(2 * guard + offset + n, dtype=src.dtype, device=src.device)
+    if src.dtype.is_floating_point:
+        buf.fill_(float("nan"))
+    else:
+        buf.view(torch.uint8).fill_(0xFF)
+    v = buf[guard + offset:guard + offset + n].view(src.shape)
+    v.copy_(src)
+    return v

@@ -1,0 +1,67 @@
+"""Argument contracts of the pointwise and conv-tail entries without a GPU: the C entries refuse tensors that their vector accesses cannot take
+(fake pointers: a refused call launches nothing), and the Python wrappers that pass raw pointers refuse strided or wrong-typed tensors."""
+import ctypes
+
+import pytest
+import torch
+
+
+def test_alignment_refusals_of_the_c_entries():
+    """msam2_dwconv7x7_ln loads f32x4 from x, weight and bias and stores four 16-bit values; msam2_hyper_masks loads eight 16-bit values;
+    msam2_im2col3x3s2 loads and stores four: none of them checked the alignment of what it was given"""
+    from medical_sam2_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(4096)
+    ptr = (ctypes.addressof(buf) + 15) & ~15
+    cases = {
+        "dwconv7x7_ln: x": lambda: L.msam2_dwconv7x7_ln(ptr + 4, ptr, ptr, ptr, ptr, ptr, 1, 2, 2, 256, None),
+        "dwconv7x7_ln: weight": lambda: L.msam2_dwconv7x7_ln(ptr, ptr + 8, ptr, ptr, ptr, ptr, 1, 2, 2, 256, None),
+        "dwconv7x7_ln: bias": lambda: L.msam2_dwconv7x7_ln(ptr, ptr, ptr + 4, ptr, ptr, ptr, 1, 2, 2, 256, None),
+        "dwconv7x7_ln: y": lambda: L.msam2_dwconv7x7_ln(ptr, ptr, ptr, ptr, ptr, ptr + 2, 1, 2, 2, 256, None),
+        "dwconv7x7_ln: C": lambda: L.msam2_dwconv7x7_ln(ptr, ptr, ptr, ptr, ptr, ptr, 1, 2, 2, 128, None),
+        "dwconv7x7_ln: shape": lambda: L.msam2_dwconv7x7_ln(ptr, ptr, ptr, ptr, ptr, ptr, 1, 0, 2, 256, None),
+        "hyper_masks: up": lambda: L.msam2_hyper_masks(ptr, ptr + 8, ptr, 1, 4, 16, 32, None),
+        "hyper_masks: up by one element": lambda: L.msam2_hyper_masks(ptr, ptr + 2, ptr, 1, 4, 16, 32, None),
+        "hyper_masks: C": lambda: L.msam2_hyper_masks(ptr, ptr, ptr, 1, 4, 16, 64, None),
+        "im2col3x3s2: x": lambda: L.msam2_im2col3x3s2(ptr + 4, ptr, 1, 2, 2, 4, 40, None),
+        "im2col3x3s2: out": lambda: L.msam2_im2col3x3s2(ptr, ptr + 2, 1, 2, 2, 4, 40, None),
+        "im2col3x3s2: ld": lambda: L.msam2_im2col3x3s2(ptr, ptr, 1, 2, 2, 4, 36, None),
+    }
+    for what, call in cases.items():
+        rc = call()
+        msg = L.msam2_last_error().decode()
+        assert rc < 0, (what, rc)
+        assert what.split(":")[0] in msg, (what, msg)
+
+
+def test_wrappers_refuse_strided_and_wrong_typed_tensors():
+    """conv3x3s2_ln_gelu, space_to_depth, obj_ptr_mix_ and hyper_masks hand raw pointers to the library: a strided view or another dtype must
+    raise before the call (host tensors: nothing is launched)"""
+    import medical_sam2_amd.ops as ops
+    op16 = ops.OP16
+    w1, v4 = torch.zeros(4, 1, 3, 3), torch.zeros(4)
+    w4, v16 = torch.zeros(16, 4, 3, 3), torch.zeros(16)
+    bad = {
+        "conv: strided x": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 2)[:, :1], 1, 4, 4, w1, v4, v4, v4),
+        "conv: 16-bit x for cin = 1": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 1, dtype=op16), 1, 4, 4, w1, v4, v4, v4),
+        "conv: fp32 x for cin = 4": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 4), 1, 4, 4, w4, v16, v16, v16),
+        "conv: float64 x": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 1, dtype=torch.float64), 1, 4, 4, w1, v4, v4, v4),
+        "conv: wrong size": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(15, 1), 1, 4, 4, w1, v4, v4, v4),
+        "conv: strided weight": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 1), 1, 4, 4, torch.zeros(4, 1, 3, 6)[..., ::2], v4, v4, v4),
+        "conv: 16-bit bias": lambda: ops.conv3x3s2_ln_gelu(torch.zeros(16, 1), 1, 4, 4, w1, v4.to(op16), v4, v4),
+        "space_to_depth: strided": lambda: ops.space_to_depth(torch.zeros(16, 2)[:, :1], 1, 4, 4, 2),
+        "space_to_depth: float64": lambda: ops.space_to_depth(torch.zeros(16, 1, dtype=torch.float64), 1, 4, 4, 2),
+        "space_to_depth: wrong size": lambda: ops.space_to_depth(torch.zeros(12, 1), 1, 4, 4, 2),
+        "obj_ptr_mix: strided ptr": lambda: ops.obj_ptr_mix_(torch.zeros(2, 8)[:, ::2], torch.zeros(2), torch.zeros(4)),
+        "obj_ptr_mix: float64 obj": lambda: ops.obj_ptr_mix_(torch.zeros(2, 4), torch.zeros(2, dtype=torch.float64), torch.zeros(4)),
+        "obj_ptr_mix: strided obj": lambda: ops.obj_ptr_mix_(torch.zeros(2, 4), torch.zeros(4)[::2], torch.zeros(4)),
+        "obj_ptr_mix: short no_obj_ptr": lambda: ops.obj_ptr_mix_(torch.zeros(2, 4), torch.zeros(2), torch.zeros(3)),
+        "obj_ptr_mix: 16-bit ptr": lambda: ops.obj_ptr_mix_(torch.zeros(2, 4, dtype=op16), torch.zeros(2), torch.zeros(4)),
+        "hyper_masks: fp32 up": lambda: ops.hyper_masks(torch.zeros(1, 4, 32), torch.zeros(16, 32), 1, 16),
+        "hyper_masks: strided up": lambda: ops.hyper_masks(torch.zeros(1, 4, 32), torch.zeros(16, 64, dtype=op16)[:, :32], 1, 16),
+        "hyper_masks: 16-bit hyper": lambda: ops.hyper_masks(torch.zeros(1, 4, 32, dtype=op16), torch.zeros(16, 32, dtype=op16), 1, 16),
+        "hyper_masks: wrong size": lambda: ops.hyper_masks(torch.zeros(1, 4, 32), torch.zeros(15, 32, dtype=op16), 1, 16),
+    }
+    for what, call in bad.items():
+        with pytest.raises((ValueError, TypeError)):
+            call()
