@@ -45,6 +45,7 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
 def act_backward(pre: torch.Tensor, dy: torch.Tensor, act: int) -> torch.Tensor:
     """16-bit dy * act'(pre); act = ops.ACT_GELU | ops.ACT_RELU."""
     _req(pre.shape == dy.shape and pre.is_contiguous() and dy.is_contiguous(), "act_backward: contiguous tensors of one shape")
+    _req(pre.dtype in (OP16, F32) and dy.dtype in (OP16, F32), "act_backward: pre and dy must be 16-bit operands or fp32")
     out = torch.empty(pre.shape, dtype=OP16, device=pre.device)
     check(lib().msam2_act_bwd(_p(pre), _is_bf16(pre), _p(dy), _is_bf16(dy), _p(out), pre.numel(), act, _stream()))
     return out
@@ -57,6 +58,8 @@ def layernorm_backward(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, e
     _req(x.dim() == 2 and x.dtype == F32 and x.stride(1) == 1 and dy.shape == x.shape and dy.stride(1) == 1, "layernorm_backward shapes")
     _req(add is None or (add.dtype == F32 and add.shape == x.shape and add.stride(1) == 1), "layernorm_backward: add must be fp32 [rows, C]")
     rows, C = x.shape
+    _req(gamma.dtype == F32 and gamma.shape == (C,) and gamma.is_contiguous(), "layernorm_backward: gamma must be fp32, contiguous, [C]")
+    _req(dy.dtype in (OP16, F32), "layernorm_backward: dy must be a 16-bit operand or fp32")
     dx = torch.empty(rows, C, dtype=F32, device=x.device)
     dgb = torch.zeros(2, C, dtype=F32, device=x.device)
     check(lib().msam2_layernorm_bwd(_p(x), x.stride(0), _p(dy), _is_bf16(dy), dy.stride(0), _p(gamma), _p(dx), dx.stride(0), _p(dgb[0]), _p(dgb[1]),
@@ -794,6 +797,8 @@ def dwconv7x7(x: torch.Tensor, taps: torch.Tensor, bias: Optional[torch.Tensor],
     """fp32 NHWC tokens [n*H*W, C] -> depthwise 7x7 (pad 3) with taps [49, C]; flip=True: the adjoint (input gradient)."""
     C = x.shape[1]
     _req(x.dtype == F32 and x.is_contiguous() and taps.shape == (49, C), "dwconv7x7: fp32 contiguous tokens, taps [49, C]")
+    _req(taps.dtype == F32 and taps.is_contiguous(), "dwconv7x7: taps must be fp32 and contiguous")
+    _req(bias is None or (bias.dtype == F32 and bias.shape == (C,) and bias.is_contiguous()), "dwconv7x7: bias must be fp32, contiguous, [C]")
     y = torch.empty_like(x)
     check(lib().msam2_dwconv7x7(_p(x), _p(taps), _p(bias), _p(y), n, H, W, C, 1 if flip else 0, _stream()))
     return y

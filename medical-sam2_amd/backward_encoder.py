@@ -30,7 +30,11 @@ from .ops import _is_bf16, _p, _stream
 # ---------------------------------------------------------------------------------------------------------------------
 def maxpool2x2_backward(x: torch.Tensor, dy: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
     """x [B*H*W, C] (row stride may exceed C; the pool's input), dy fp32 [B*(H/2)*(W/2), C] -> dx fp32 [B*H*W, C]."""
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[0] != B * H * W:
+        raise ValueError("maxpool2x2_backward: x must be [B*H*W, C] rows with unit column stride")
     C = x.shape[1]
+    if dy.shape != (B * (H // 2) * (W // 2), C):
+        raise ValueError("maxpool2x2_backward: dy must be [B*(H/2)*(W/2), C]")
     dy = dy.to(F32)
     dy = dy if dy.stride(1) == 1 else dy.contiguous()
     dx = torch.empty(B * H * W, C, dtype=F32, device=x.device)

@@ -254,3 +254,64 @@ def nan_guarded(src, offset=0, guard=64):
     v = buf[guard + offset:guard + offset + n].view(src.shape)
     v.copy_(src)
     return v
+
+
+def K(key: str) -> str:
+    """kernel key of a table entry: T16 stands for the library's 16-bit operand type as the demangler spells it"""
+    return key.replace("T16", "_Float16" if op16_is_fp16() else "__bf16")
+
+
+def reached(L, key, prefix, launches):
+    """run the launches (callables returning the C entry's code) under the profiler: all succeed, and exactly `key` ran among the kernels
+    whose name starts with `prefix` (key None: none)"""
+    def go():
+        for fn in launches:
+            rc = fn()
+            assert rc == 0, L.msam2_last_error().decode()
+    got = kernels_launched(go, prefix)
+    want = set() if key is None else {K(key)}
+    assert got == want, f"expected {sorted(want)}, launched {sorted(got)}"
+
+
+def within(got, ref, bound, what):
+    d = (got.double() - ref).abs()
+    bad = ~(d <= bound)                                   # a NaN anywhere fails
+    if bool(bad.any()):
+        i = int((d - bound).masked_fill(~bad, -1).argmax()) if not bool(torch.isnan(d).any()) else int(torch.isnan(d).flatten().nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements outside the bound; worst |err| {float(d.flatten()[i]):.3e} "
+                             f"against {float(bound.expand_as(d).flatten()[i]):.3e} at flat index {i}")
+
+
+def same_bits(a, b, what):
+    it = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[a.dtype.itemsize]
+    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
+    ne = a.contiguous().view(it) != b.contiguous().view(it)
+    assert not bool(ne.any()), f"{what}: {int(ne.sum())} of {ne.numel()} elements differ in their bits"
+
+
+def strided_nan(src, ld, off=0):
+    """src [rows, C] as a view with row stride ld inside a NaN-filled buffer, starting `off` elements into it"""
+    rows, C = src.shape
+    buf = torch.full((off + (rows + 5) * ld + 16,), float("nan"), dtype=src.dtype, device="cuda")
+    v = torch.as_strided(buf, (rows, C), (ld, 1), off)
+    v.copy_(src)
+    return v
+
+
+class Canvas2:
+    """[M, N] output view with row stride ld inside a sentinel-filled buffer, three rows before and after and `left` columns before it
+    (left * itemsize is the view's byte offset from a 16-byte boundary when ld * itemsize is a multiple of 16)"""
+
+    def __init__(self, M, N, dtype, ld, left):
+        assert ld >= left + N
+        es = dtype.itemsize
+        self.itype = torch.int16 if es == 2 else torch.int32
+        self.sent = SENT16 if es == 2 else SENT32
+        self.buf = torch.empty(M + 6, ld, dtype=dtype, device="cuda")
+        self.buf.view(self.itype).fill_(self.sent)
+        self.view = self.buf[3:3 + M, left:left + N]
+        self.inside = torch.zeros(self.buf.shape, dtype=torch.bool, device="cuda")
+        self.inside[3:3 + M, left:left + N] = True
+
+    def sentinels_intact(self):
+        return bool((self.buf.view(self.itype)[~self.inside] == self.sent).all())

@@ -31,11 +31,9 @@ def gelu64(x):
     return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
 
-def ln_tail(a, da, w, b, eps):
-    """LayerNorm over the last dim of float64 `a` whose fp32 counterpart carries the absolute error `da` (tensor or 0.0): returns
-    (pre, dpre) = the float64 result d * rstd * w + b and its bound.  Steps: mean (C - 1 additions and a division of values of mean size
-    mean|a|), d = a - mean, var (C + 3 operations on d^2, first-order in the error of d), rstd = 1 / sqrt(var + eps) (three more
-    roundings; relative error r / 2 / (1 - r) with r = dvar / (var + eps), infinite if r >= 0.5), the affine (three roundings)."""
+def ln_stats(a, da, eps):
+    """the statistics of ln_tail and their errors: (d, rstd, dd, rel) = a - mean, 1 / sqrt(var + eps), the absolute error of d and the
+    relative error of rstd (see ln_tail for the steps)"""
     C = a.shape[-1]
     da = torch.as_tensor(da, dtype=a.dtype, device=a.device).expand_as(a)
     mean = a.mean(-1, keepdim=True)
@@ -47,6 +45,15 @@ def ln_tail(a, da, w, b, eps):
     dvar = (2 * d.abs() * dd + dd * dd).mean(-1, keepdim=True) + (C + 3) * U * var
     r = dvar / (var + eps)
     rel = torch.where(r < 0.5, 0.5 * r / (1.0 - r.clamp(max=0.5)), torch.full_like(r, float("inf"))) + 3 * U
+    return d, rstd, dd, rel
+
+
+def ln_tail(a, da, w, b, eps):
+    """LayerNorm over the last dim of float64 `a` whose fp32 counterpart carries the absolute error `da` (tensor or 0.0): returns
+    (pre, dpre) = the float64 result d * rstd * w + b and its bound.  Steps: mean (C - 1 additions and a division of values of mean size
+    mean|a|), d = a - mean, var (C + 3 operations on d^2, first-order in the error of d), rstd = 1 / sqrt(var + eps) (three more
+    roundings; relative error r / 2 / (1 - r) with r = dvar / (var + eps), infinite if r >= 0.5), the affine (three roundings)."""
+    d, rstd, dd, rel = ln_stats(a, da, eps)
     pre = d * rstd * w + b
     dpre = w.abs() * rstd * (dd + d.abs() * rel) * (1.0 + rel) + 3 * U * (d * rstd * w).abs() + U * pre.abs()
     return pre, dpre

@@ -34,6 +34,83 @@ def test_alignment_refusals_of_the_c_entries():
         assert what.split(":")[0] in msg, (what, msg)
 
 
+def test_refusals_of_the_backward_entries():
+    """msam2_dwconv7x7 loads and stores f32x4 on x, taps, bias and y; msam2_hiera_pos_embed_bwd divides by window; window_move /
+    window_unpartition_cvt move 16-byte chunks; layernorm_bwd holds at most 1024 columns"""
+    from medical_sam2_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(4096)
+    ptr = (ctypes.addressof(buf) + 15) & ~15
+    pos = lambda C=4, bh=2, bw=2, h=8, w=8, window=8: L.msam2_hiera_pos_embed_bwd(ptr, ptr, ptr, C, bh, bw, h, w, window, ptr, 1 << 20, None)
+    wm = lambda img=ptr, ld=8, win=ptr, fill=None, D=8, es=2: L.msam2_window_move(img, ld, win, fill, 1, 2, 2, 1, D, 2, es, 1, None)
+    cvt = lambda img=ptr, ld=8, win=ptr, D=8: L.msam2_window_unpartition_cvt(img, ld, win, 1, 2, 2, 1, D, 2, None)
+    cases = {
+        "dwconv7x7: x": lambda: L.msam2_dwconv7x7(ptr + 4, ptr, ptr, ptr, 1, 2, 2, 4, 0, None),
+        "dwconv7x7: w_tap_major": lambda: L.msam2_dwconv7x7(ptr, ptr + 8, ptr, ptr, 1, 2, 2, 4, 0, None),
+        "dwconv7x7: bias": lambda: L.msam2_dwconv7x7(ptr, ptr, ptr + 4, ptr, 1, 2, 2, 4, 1, None),
+        "dwconv7x7: y": lambda: L.msam2_dwconv7x7(ptr, ptr, None, ptr + 12, 1, 2, 2, 4, 0, None),
+        "dwconv7x7: C": lambda: L.msam2_dwconv7x7(ptr, ptr, ptr, ptr, 1, 2, 2, 6, 0, None),
+        "hiera_pos_embed_bwd: window = 0": lambda: pos(window=0),
+        "hiera_pos_embed_bwd: window < 0": lambda: pos(window=-8),
+        "hiera_pos_embed_bwd: C": lambda: pos(C=0),
+        "hiera_pos_embed_bwd: bh": lambda: pos(bh=0),
+        "hiera_pos_embed_bwd: bw": lambda: pos(bw=-1),
+        "hiera_pos_embed_bwd: h": lambda: pos(h=0),
+        "hiera_pos_embed_bwd: w": lambda: pos(w=0),
+        "hiera_pos_embed_bwd: h % window": lambda: pos(h=12),
+        "window_move: img": lambda: wm(img=ptr + 8),
+        "window_move: win": lambda: wm(win=ptr + 4),
+        "window_move: fill": lambda: wm(fill=ptr + 2),
+        "window_move: row stride": lambda: wm(ld=12),
+        "window_move: D": lambda: wm(D=4),
+        "window_move: element size": lambda: wm(es=3),
+        "window_unpartition_cvt: img": lambda: cvt(img=ptr + 8),
+        "window_unpartition_cvt: win": lambda: cvt(win=ptr + 4),
+        "window_unpartition_cvt: row stride": lambda: cvt(ld=12),
+        "window_unpartition_cvt: D": lambda: cvt(D=4),
+        "layernorm_bwd: C": lambda: L.msam2_layernorm_bwd(ptr, 1028, ptr, 0, 1028, ptr, ptr, 1028, ptr, ptr, 1, 1025, 1e-6, None, 0, None),
+        "layernorm_bwd: rows": lambda: L.msam2_layernorm_bwd(ptr, 8, ptr, 0, 8, ptr, ptr, 8, ptr, ptr, 0, 8, 1e-6, None, 0, None),
+    }
+    for what, call in cases.items():
+        rc = call()
+        msg = L.msam2_last_error().decode()
+        assert rc < 0, (what, rc)
+        assert what.split(":")[0] in msg, (what, msg)
+
+
+def test_backward_wrappers_refuse_strided_and_wrong_typed_tensors():
+    """backward.act_backward, layernorm_backward, dwconv7x7 and backward_encoder.maxpool2x2_backward hand raw pointers to the library (host
+    tensors: nothing is launched)"""
+    import medical_sam2_amd.backward as bwd
+    import medical_sam2_amd.backward_encoder as be
+    import medical_sam2_amd.ops as ops
+    op16, f64 = ops.OP16, torch.float64
+    x, g = torch.zeros(4, 8), torch.zeros(8)
+    taps = torch.zeros(49, 8)
+    bad = {
+        "act_backward: float64 pre": lambda: bwd.act_backward(torch.zeros(8, dtype=f64), torch.zeros(8), 1),
+        "act_backward: float64 dy": lambda: bwd.act_backward(torch.zeros(8), torch.zeros(8, dtype=f64), 1),
+        "act_backward: int dy": lambda: bwd.act_backward(torch.zeros(8, dtype=op16), torch.zeros(8, dtype=torch.int16), 2),
+        "act_backward: strided": lambda: bwd.act_backward(torch.zeros(8, 2)[:, 0], torch.zeros(8), 1),
+        "layernorm_backward: 16-bit gamma": lambda: bwd.layernorm_backward(x, g.to(op16), x, 1e-6),
+        "layernorm_backward: strided gamma": lambda: bwd.layernorm_backward(x, torch.zeros(16)[::2], x, 1e-6),
+        "layernorm_backward: short gamma": lambda: bwd.layernorm_backward(x, torch.zeros(4), x, 1e-6),
+        "layernorm_backward: 2-d gamma": lambda: bwd.layernorm_backward(x, torch.zeros(1, 8), x, 1e-6),
+        "layernorm_backward: float64 dy": lambda: bwd.layernorm_backward(x, g, x.double(), 1e-6),
+        "dwconv7x7: 16-bit taps": lambda: bwd.dwconv7x7(x, taps.to(op16), None, 1, 2, 2),
+        "dwconv7x7: strided taps": lambda: bwd.dwconv7x7(x, torch.zeros(8, 49).t(), None, 1, 2, 2),
+        "dwconv7x7: 16-bit bias": lambda: bwd.dwconv7x7(x, taps, g.to(op16), 1, 2, 2),
+        "dwconv7x7: strided bias": lambda: bwd.dwconv7x7(x, taps, torch.zeros(16)[::2], 1, 2, 2),
+        "dwconv7x7: short bias": lambda: bwd.dwconv7x7(x, taps, torch.zeros(4), 1, 2, 2),
+        "maxpool2x2_backward: column-strided x": lambda: be.maxpool2x2_backward(torch.zeros(4, 16)[:, ::2], torch.zeros(1, 8), 1, 2, 2),
+        "maxpool2x2_backward: x rows": lambda: be.maxpool2x2_backward(torch.zeros(5, 8), torch.zeros(1, 8), 1, 2, 2),
+        "maxpool2x2_backward: dy rows": lambda: be.maxpool2x2_backward(x, torch.zeros(2, 8), 1, 2, 2),
+    }
+    for what, call in bad.items():
+        with pytest.raises((ValueError, TypeError)):
+            call()
+
+
 def test_wrappers_refuse_strided_and_wrong_typed_tensors():
     """conv3x3s2_ln_gelu, space_to_depth, obj_ptr_mix_ and hyper_masks hand raw pointers to the library: a strided view or another dtype must
     raise before the call (host tensors: nothing is launched)"""
