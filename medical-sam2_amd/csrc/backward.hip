@@ -51,6 +51,45 @@ struct GemmTTParams {
 constexpr int TT_PITCH = 320;                 // bytes per LDS row (128 op16 + 64 B pad)
 constexpr int TT_SLAB = 32 * TT_PITCH;        // one operand, one stage
 
+// The two ends that gemm_tt_kernel and gemm_tt_dma_kernel share, as MACROS over the kernels' locals (as __forceinline__ functions the listings of
+// both kernels change: the store loop grows by 190 lines, the reduction is scheduled in another order).
+// Column sums of A (the bias gradient): thread (tid & 15) holds the sums of columns 8 (tid & 15) .. +8 over its rows; the 16 row groups are
+// reduced through LDS ([16][128] floats) and leave as one atomic per column
+#define GEMM_TT_REDUCE_COLSUM() \
+  do { \
+    float* red = reinterpret_cast<float*>(lds); \
+    _Pragma("unroll") \
+    for (int e = 0; e < 8; ++e) red[(tid >> 4) * 128 + (tid & 15) * 8 + e] = cs[e]; \
+    __syncthreads(); \
+    if (tid < 128 && m0 + tid < p.M) { \
+      float t = 0.f; \
+      _Pragma("unroll") \
+      for (int g = 0; g < 16; ++g) t += red[g * 128 + tid]; \
+      atomicAdd(p.a_colsum + m0 + tid, t); \
+    } \
+  } while (0)
+// C tile from the 32x32 accumulator layout (register e = row (e & 3) + 8 (e >> 2) + 4 h, lane = column): plain stores, or fp32 atomics when
+// the reduction is split over gridDim.z or the call accumulates
+#define GEMM_TT_STORE_C() \
+  do { \
+    const bool atomic = gridDim.z > 1 || p.accumulate; \
+    _Pragma("unroll") \
+    for (int j = 0; j < 2; ++j) { \
+      const int n = n0 + wn * 64 + j * 32 + r; \
+      if (n >= p.N) continue; \
+      _Pragma("unroll") \
+      for (int i = 0; i < 2; ++i) \
+        _Pragma("unroll") \
+        for (int e = 0; e < 16; ++e) { \
+          const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h; \
+          if (m < p.M) { \
+            if (atomic) atomicAdd(p.C + (int64_t)m * p.ldc + n, acc[i][j][e]); \
+            else p.C[(int64_t)m * p.ldc + n] = acc[i][j][e]; \
+          } \
+        } \
+    } \
+  } while (0)
+
 __global__ __launch_bounds__(256) void gemm_tt_kernel(GemmTTParams p) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[4 * TT_SLAB];   // [stage][A | B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -126,34 +165,9 @@ __global__ __launch_bounds__(256) void gemm_tt_kernel(GemmTTParams p) {
     cur ^= 1;
   }
   if (want_cs) {
-    // thread (tid & 15) holds the sums of columns 8 (tid & 15) .. +8 over its rows: reduce the 16 row groups through LDS
-    float* red = reinterpret_cast<float*>(lds);          // [16][128]; every wave is past its last fragment read (loop-end barrier)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[(tid >> 4) * 128 + (tid & 15) * 8 + e] = cs[e];
-    __syncthreads();
-    if (tid < 128 && m0 + tid < p.M) {
-      float t = 0.f;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) t += red[g * 128 + tid];
-      atomicAdd(p.a_colsum + m0 + tid, t);
-    }
+    GEMM_TT_REDUCE_COLSUM();                             // (every wave is past its last fragment read: loop-end barrier)
   }
-  const bool atomic = gridDim.z > 1 || p.accumulate;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn * 64 + j * 32 + r;
-    if (n >= p.N) continue;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (m < p.M) {
-          if (atomic) atomicAdd(p.C + (int64_t)m * p.ldc + n, acc[i][j][e]);
-          else p.C[(int64_t)m * p.ldc + n] = acc[i][j][e];
-        }
-      }
-  }
+  GEMM_TT_STORE_C();
 }
 
 // LDS-DMA form of gemm_tt_kernel (round 3): the register-staged kernel above runs 8 MFMAs per wave and barrier behind a global-load
@@ -252,33 +266,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tt_dma_kernel(GemmTTParams p) {
   }
   if (want_cs) {
     __builtin_amdgcn_s_barrier();                        // every wave is past its last fragment read
-    float* red = reinterpret_cast<float*>(lds);          // [16][128]
-#pragma unroll
-    for (int e = 0; e < 8; ++e) red[(tid >> 4) * 128 + (tid & 15) * 8 + e] = cs[e];
-    __syncthreads();
-    if (tid < 128 && m0 + tid < p.M) {
-      float t = 0.f;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) t += red[g * 128 + tid];
-      atomicAdd(p.a_colsum + m0 + tid, t);
-    }
+    GEMM_TT_REDUCE_COLSUM();
   }
-  const bool atomic = gridDim.z > 1 || p.accumulate;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn * 64 + j * 32 + r;
-    if (n >= p.N) continue;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (m < p.M) {
-          if (atomic) atomicAdd(p.C + (int64_t)m * p.ldc + n, acc[i][j][e]);
-          else p.C[(int64_t)m * p.ldc + n] = acc[i][j][e];
-        }
-      }
-  }
+  GEMM_TT_STORE_C();
 }
 
 __global__ __launch_bounds__(256) void gemm_tt_zero_kernel(float* __restrict__ C, int64_t ldc, int M, int N, float* __restrict__ colsum, int zero_c) {
@@ -291,7 +281,7 @@ __global__ __launch_bounds__(256) void gemm_tt_zero_kernel(float* __restrict__ C
 static int gemm_tt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, float* a_colsum, int64_t M, int64_t N,
                         int64_t K, int accumulate, void* stream) {
   MSAM2_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "gemm_tt: bad arguments");
-  MSAM2_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0,
+  MSAM2_REQUIRE(M % 8 == 0 && N % 8 == 0 && vec_ok(8, 2, lda, ldb, A, B),
                 "gemm_tt: M, N, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
   MSAM2_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) && lda >= M && ldb >= N && ldc >= N, "gemm_tt: bad sizes");
   GemmTTParams p;
@@ -313,7 +303,7 @@ static int gemm_tt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
   splits = cdiv(nk, p.ktiles_per_split);
   hipStream_t s = (hipStream_t)stream;
   if (!accumulate && (splits > 1 || a_colsum))
-    hipLaunchKernelGGL(gemm_tt_zero_kernel, dim3((unsigned)min((int64_t)1024, (M * N + 255) / 256)), dim3(256), 0, s, C, ldc, (int)M, (int)N, a_colsum,
+    hipLaunchKernelGGL(gemm_tt_zero_kernel, dim3(grid1d(M * N, 1024)), dim3(256), 0, s, C, ldc, (int)M, (int)N, a_colsum,
                        splits > 1 ? 1 : 0);
   if (dma) hipLaunchKernelGGL(gemm_tt_dma_kernel, dim3(cdiv(N, 128), cdiv(M, 128), (unsigned)splits), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(gemm_tt_kernel, dim3(cdiv(N, 128), cdiv(M, 128), (unsigned)splits), dim3(256), 0, s, p);
@@ -350,10 +340,11 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
 
 extern "C" int msam2_colsum(const void* x, int x_is_16bit, int64_t ldx, float* out, int64_t rows, int64_t cols, void* stream) {
   MSAM2_REQUIRE(x && out && rows > 0 && cols > 0, "colsum: bad arguments");
-  const unsigned slabs = (unsigned)min((int64_t)256, cdiv(rows, 256));
-  dim3 grid(cdiv(cols, 64), slabs);
-  if (x_is_16bit) hipLaunchKernelGGL((colsum_kernel<op16>), grid, dim3(256), 0, (hipStream_t)stream, (const op16*)x, ldx, out, rows, (int)cols);
-  else hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, ldx, out, rows, (int)cols);
+  dim3 grid(cdiv(cols, 64), grid1d(rows, 256));
+  with_type(x_is_16bit, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colsum_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, out, rows, (int)cols);
+  });
   return msam2_check_launch("colsum");
 }
 
@@ -404,21 +395,7 @@ __global__ __launch_bounds__(256) void act_bwd_vec_kernel(const TP* __restrict__
     for (int e = 0; e < 8; ++e) {
       float d;
       if (act == 1) {
-#ifndef MSAM2_GELU_AS
-        const float xc = __builtin_amdgcn_fmed3f(x[e], -MSAM2_GELU_X, MSAM2_GELU_X), u = xc * xc;
-        float q = __builtin_fmaf(u, MSAM2_GELU_Q8, MSAM2_GELU_Q7);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q6);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q5);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q4);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q3);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q2);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q1);
-        q = __builtin_fmaf(q, u, MSAM2_GELU_Q0);
-        const float cdf = __builtin_fmaf(xc, q, 0.5f);
-#else
-        const float cdf = 0.5f * (1.f + fast_erf(x[e] * 0.70710678118654752f));
-#endif
-        d = cdf + x[e] * 0.3989422804014327f * __builtin_amdgcn_exp2f(x[e] * x[e] * -0.72134752044448170368f);   // + x phi(x)
+        d = gelu_phi(x[e]) + x[e] * 0.3989422804014327f * __builtin_amdgcn_exp2f(x[e] * x[e] * -0.72134752044448170368f);   // + x phi(x)
       } else {
         d = x[e] > 0.f ? 1.f : 0.f;
       }
@@ -430,22 +407,18 @@ __global__ __launch_bounds__(256) void act_bwd_vec_kernel(const TP* __restrict__
 
 extern "C" int msam2_act_bwd(const void* pre, int pre_is_16bit, const void* dy, int dy_is_16bit, void* out, int64_t n, int act, void* stream) {
   MSAM2_REQUIRE(pre && dy && out && n > 0 && (act == 1 || act == 2), "act_bwd: bad arguments");
-  dim3 grid((unsigned)min((int64_t)16384, cdiv(n, 256))), block(256);
   hipStream_t s = (hipStream_t)stream;
   static const bool v1 = getenv("MSAM2_ACT_BWD_V1") != nullptr;
-  if (!v1 && n % 8 == 0 && ((uintptr_t)pre & 15) == 0 && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)out & 15) == 0) {
-    const int64_t n8 = n / 8;
-    dim3 g8((unsigned)min((int64_t)8192, cdiv(n8, 256)));
-    if (pre_is_16bit && dy_is_16bit) hipLaunchKernelGGL((act_bwd_vec_kernel<op16, op16>), g8, block, 0, s, (const op16*)pre, (const op16*)dy, (op16*)out, n8, act);
-    else if (pre_is_16bit) hipLaunchKernelGGL((act_bwd_vec_kernel<op16, float>), g8, block, 0, s, (const op16*)pre, (const float*)dy, (op16*)out, n8, act);
-    else if (dy_is_16bit) hipLaunchKernelGGL((act_bwd_vec_kernel<float, op16>), g8, block, 0, s, (const float*)pre, (const op16*)dy, (op16*)out, n8, act);
-    else hipLaunchKernelGGL((act_bwd_vec_kernel<float, float>), g8, block, 0, s, (const float*)pre, (const float*)dy, (op16*)out, n8, act);
-    return msam2_check_launch("act_bwd");
-  }
-  if (pre_is_16bit && dy_is_16bit) hipLaunchKernelGGL((act_bwd_kernel<op16, op16>), grid, block, 0, s, (const op16*)pre, (const op16*)dy, (op16*)out, n, act);
-  else if (pre_is_16bit) hipLaunchKernelGGL((act_bwd_kernel<op16, float>), grid, block, 0, s, (const op16*)pre, (const float*)dy, (op16*)out, n, act);
-  else if (dy_is_16bit) hipLaunchKernelGGL((act_bwd_kernel<float, op16>), grid, block, 0, s, (const float*)pre, (const op16*)dy, (op16*)out, n, act);
-  else hipLaunchKernelGGL((act_bwd_kernel<float, float>), grid, block, 0, s, (const float*)pre, (const float*)dy, (op16*)out, n, act);
+  // the vector kernel moves eight elements per thread: pre and dy are tested for 16 bytes whatever their type (an fp32 operand is read as two f32x4)
+  const bool vec = !v1 && n % 8 == 0 && vec_ok(8, 2, pre, dy, out);
+  with_type(pre_is_16bit, [&](auto tp) {
+    with_type(dy_is_16bit, [&](auto td) {
+      using TP = decltype(tp);
+      using TD = decltype(td);
+      if (vec) hipLaunchKernelGGL((act_bwd_vec_kernel<TP, TD>), dim3(grid1d(n / 8, 8192)), dim3(256), 0, s, (const TP*)pre, (const TD*)dy, (op16*)out, n / 8, act);
+      else hipLaunchKernelGGL((act_bwd_kernel<TP, TD>), dim3(grid1d(n, 16384)), dim3(256), 0, s, (const TP*)pre, (const TD*)dy, (op16*)out, n, act);
+    });
+  });
   return msam2_check_launch("act_bwd");
 }
 
@@ -549,11 +522,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
     ag[j] = ab[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const float inv_c = 1.f / (float)C;
-  auto sum16 = [](float v) {
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
   for (int64_t row = r_begin + grp; row < r_end; row += 16) {
     const float* xr = x + row * ldx;
     const TD* dr = dy + row * ldd;
@@ -580,7 +548,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
     for (int j = 0; j < CHUNKS; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) s += xv[j][e];
-    const float mean = sum16(s) * inv_c;
+    const float mean = group16_sum(s) * inv_c;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < CHUNKS; ++j)
@@ -591,7 +559,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
           q += d * d;
         }
       }
-    const float rstd = 1.f / sqrtf(sum16(q) * inv_c + eps);
+    const float rstd = 1.f / sqrtf(group16_sum(q) * inv_c + eps);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < CHUNKS; ++j) {
@@ -607,7 +575,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const float* __r
         gv[j][e] = g;
       }
     }
-    const float m1 = sum16(s1) * inv_c, m2 = sum16(s2) * inv_c;
+    const float m1 = group16_sum(s1) * inv_c, m2 = group16_sum(s2) * inv_c;
     float* o = dx + row * ldo;
 #pragma unroll
     for (int j = 0; j < CHUNKS; ++j) {
@@ -646,12 +614,11 @@ static void layernorm_bwd_launch(const float* x, int64_t ldx, const TD* dy, int6
   static const int64_t env_grid = getenv("MSAM2_LNB_GRID") ? atoll(getenv("MSAM2_LNB_GRID")) : 0;
   // every workgroup ends with one atomic per column on the SAME 2 C addresses: at 1024 workgroups that serialisation is the kernel
   // (16384 x 384: 45 us at 1024, 33 at 512, 30 at 256, 37 at 128; 262144 x 96: 90 / 85 / 107 / 187) -> 256 for the short maps, 512 beyond
-  const dim3 grid((unsigned)min(env_grid > 0 ? env_grid : (int64_t)(rows <= 32768 ? 256 : 512), cdiv(rows, 16))), block(256);
+  const dim3 grid(grid1d(rows, env_grid > 0 ? env_grid : (rows <= 32768 ? 256 : 512), 16)), block(256);
   {
     static const bool v1 = getenv("MSAM2_LN_BWD_V1") != nullptr;
-    const bool vec = !v1 && C % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && ldd % 4 == 0 && (!add || lda % 4 == 0) && ((uintptr_t)x & 15) == 0 &&
-                     ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dy & (sizeof(TD) == 4 ? 15 : 7)) == 0 && (!add || ((uintptr_t)add & 15) == 0) &&
-                     ((uintptr_t)gamma & 15) == 0 && C <= 384;   // <= 6 chunks per lane: beyond that the six per-lane arrays cost the second wave per SIMD
+    const bool vec = !v1 && C % 4 == 0 && vec_ok(4, 4, ldx, x, ldo, dx, gamma) && vec_ok(4, sizeof(TD), ldd, dy) && (!add || vec_ok(4, 4, lda, add)) &&
+                     C <= 384;   // <= 6 chunks per lane: beyond that the six per-lane arrays cost the second wave per SIMD
     if (vec) {
       const int chunks = cdiv(C / 4, 16);
 #define LNV(CH) hipLaunchKernelGGL((layernorm_bwd_vec_kernel<TD, CH>), grid, block, 0, s, x, ldx, dy, ldd, gamma, dx, ldo, dgamma, dbeta, rows, C, eps, add, lda)
@@ -682,8 +649,9 @@ extern "C" int msam2_layernorm_bwd(const float* x, int64_t ldx, const void* dy, 
   MSAM2_REQUIRE(x && dy && gamma && dx && dgamma && dbeta, "layernorm_bwd: null tensor");
   MSAM2_REQUIRE(rows > 0 && C > 0 && C <= 1024, "layernorm_bwd: C <= 1024");
   hipStream_t s = (hipStream_t)stream;
-  if (dy_is_16bit) layernorm_bwd_launch<op16>(x, ldx, (const op16*)dy, ldd, gamma, dx, ldo, dgamma, dbeta, rows, (int)C, eps, add, ld_add, s);
-  else layernorm_bwd_launch<float>(x, ldx, (const float*)dy, ldd, gamma, dx, ldo, dgamma, dbeta, rows, (int)C, eps, add, ld_add, s);
+  with_type(dy_is_16bit, [&](auto td) {
+    layernorm_bwd_launch(x, ldx, (const decltype(td)*)dy, ldd, gamma, dx, ldo, dgamma, dbeta, rows, (int)C, eps, add, ld_add, s);
+  });
   return msam2_check_launch("layernorm_bwd");
 }
 
@@ -755,11 +723,9 @@ __global__ void convt2x2_gather_kernel(const op16* __restrict__ g, const float* 
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = i % C;
     const int64_t pix = i / C;
-    const int X = pix % W, Y = (pix / W) % H;
-    const int64_t b = pix / ((int64_t)W * H);
-    const int64_t tok = (b * h + Y / 2) * w + X / 2;
-    const int sub = (Y & 1) * 2 + (X & 1);
-    z[i] = op2f(g[tok * 4 * C + sub * C + c]) + bias[c] + (skip ? op2f(skip[i]) : 0.f);
+    const PixelIndex px(pix, H, W);
+    const ConvT2x2Index t(px.b, px.y, px.x, h, w);
+    z[i] = op2f(g[t.tok * 4 * C + t.sub * C + c]) + bias[c] + (skip ? op2f(skip[i]) : 0.f);
   }
 }
 
@@ -767,7 +733,7 @@ extern "C" int msam2_convt2x2_gather(const void* gemm_out, const float* bias, co
                                      int64_t C, void* stream) {
   MSAM2_REQUIRE(gemm_out && bias && z && B > 0 && h > 0 && w > 0 && C > 0, "convt2x2_gather: bad arguments");
   const int64_t total = B * 4 * h * w * C;
-  hipLaunchKernelGGL(convt2x2_gather_kernel, dim3((unsigned)min((int64_t)16384, cdiv(total, 256))), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(convt2x2_gather_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream,
                      (const op16*)gemm_out, bias, (const op16*)skip, z, (int)B, (int)h, (int)w, (int)C);
   return msam2_check_launch("convt2x2_gather");
 }
@@ -779,20 +745,20 @@ __global__ void convt2x2_scatter_grad_kernel(const T* __restrict__ dz, op16* __r
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = i % C;
     const int64_t pix = i / C;
-    const int X = pix % W, Y = (pix / W) % H;
-    const int64_t b = pix / ((int64_t)W * H);
-    const int64_t tok = (b * h + Y / 2) * w + X / 2;
-    const int sub = (Y & 1) * 2 + (X & 1);
-    dg[tok * 4 * C + sub * C + c] = f2op((float)dz[i]);
+    const PixelIndex px(pix, H, W);
+    const ConvT2x2Index t(px.b, px.y, px.x, h, w);
+    dg[t.tok * 4 * C + t.sub * C + c] = f2op((float)dz[i]);
   }
 }
 
 extern "C" int msam2_convt2x2_scatter_grad(const void* dz, int dz_is_16bit, void* dg, int64_t B, int64_t h, int64_t w, int64_t C, void* stream) {
   MSAM2_REQUIRE(dz && dg && B > 0 && h > 0 && w > 0 && C > 0, "convt2x2_scatter_grad: bad arguments");
   const int64_t total = B * 4 * h * w * C;
-  dim3 grid((unsigned)min((int64_t)16384, cdiv(total, 256))), block(256);
-  if (dz_is_16bit) hipLaunchKernelGGL((convt2x2_scatter_grad_kernel<op16>), grid, block, 0, (hipStream_t)stream, (const op16*)dz, (op16*)dg, (int)B, (int)h, (int)w, (int)C);
-  else hipLaunchKernelGGL((convt2x2_scatter_grad_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)dz, (op16*)dg, (int)B, (int)h, (int)w, (int)C);
+  with_type(dz_is_16bit, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((convt2x2_scatter_grad_kernel<T>), dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const T*)dz, (op16*)dg, (int)B, (int)h,
+                       (int)w, (int)C);
+  });
   return msam2_check_launch("convt2x2_scatter_grad");
 }
 
@@ -811,8 +777,8 @@ __global__ __launch_bounds__(256) void dwconv7x7_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c = (int)(i % C4) * 4;
     const int64_t pix = i / C4;
-    const int px = (int)(pix % W), py = (int)((pix / W) % H);
-    const int64_t b = pix / ((int64_t)W * H);
+    const PixelIndex pi(pix, H, W);
+    const int px = pi.x, py = pi.y;
     f32x4 acc = bias ? *reinterpret_cast<const f32x4*>(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     for (int ky = 0; ky < 7; ++ky) {
       const int yy = py + ky - 3;
@@ -821,7 +787,7 @@ __global__ __launch_bounds__(256) void dwconv7x7_kernel(const float* __restrict_
         const int xx = px + kx - 3;
         if (xx < 0 || xx >= W) continue;
         const int tap = flip ? (6 - ky) * 7 + (6 - kx) : ky * 7 + kx;
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + ((b * H + yy) * W + xx) * C + c);
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + ((pi.b * H + yy) * W + xx) * C + c);
         const f32x4 wv = *reinterpret_cast<const f32x4*>(w + tap * C + c);
         acc += xv * wv;
       }
@@ -833,10 +799,10 @@ __global__ __launch_bounds__(256) void dwconv7x7_kernel(const float* __restrict_
 extern "C" int msam2_dwconv7x7(const float* x, const float* w_tap_major, const float* bias, float* y, int64_t B, int64_t H, int64_t W, int64_t C,
                                int flip, void* stream) {
   MSAM2_REQUIRE(x && w_tap_major && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "dwconv7x7: bad arguments");
-  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)w_tap_major | (uintptr_t)bias | (uintptr_t)y) & 15) == 0,
+  MSAM2_REQUIRE(vec_ok(4, 4, x, w_tap_major, bias, y),
                 "dwconv7x7: x, w_tap_major, bias and y must be 16-byte aligned (four-channel fp32 accesses)");
   const int64_t total = B * H * W * (C / 4);
-  hipLaunchKernelGGL(dwconv7x7_kernel, dim3((unsigned)min((int64_t)16384, cdiv(total, (int64_t)256))), dim3(256), 0, (hipStream_t)stream, x, w_tap_major,
+  hipLaunchKernelGGL(dwconv7x7_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream, x, w_tap_major,
                      bias, y, (int)B, (int)H, (int)W, (int)(C / 4), flip);
   return msam2_check_launch("dwconv7x7");
 }
@@ -852,8 +818,8 @@ __global__ __launch_bounds__(64) void dwconv7x7_wgrad_kernel(const float* __rest
 #pragma unroll
   for (int t = 0; t < 49; ++t) acc[t] = 0.f;
   for (int64_t pix = p0; pix < p1; ++pix) {
-    const int px = (int)(pix % W), py = (int)((pix / W) % H);
-    const int64_t b = pix / ((int64_t)W * H);
+    const PixelIndex pi(pix, H, W);
+    const int px = pi.x, py = pi.y;
     const float g = dy[pix * C + c];
 #pragma unroll
     for (int ky = 0; ky < 7; ++ky) {
@@ -861,7 +827,7 @@ __global__ __launch_bounds__(64) void dwconv7x7_wgrad_kernel(const float* __rest
 #pragma unroll
       for (int kx = 0; kx < 7; ++kx) {
         const int xx = px + kx - 3;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) acc[ky * 7 + kx] += g * x[((b * H + yy) * W + xx) * C + c];
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) acc[ky * 7 + kx] += g * x[((pi.b * H + yy) * W + xx) * C + c];
       }
     }
   }
@@ -873,7 +839,7 @@ extern "C" int msam2_dwconv7x7_wgrad(const float* x, const float* dy, float* dw_
                                      void* stream) {
   MSAM2_REQUIRE(x && dy && dw_tap_major && B > 0 && H > 0 && W > 0 && C > 0, "dwconv7x7_wgrad: bad arguments");
   const int64_t npix = B * H * W;
-  dim3 grid((unsigned)cdiv(C, (int64_t)64), (unsigned)min((int64_t)512, cdiv(npix, (int64_t)32)));
+  dim3 grid((unsigned)cdiv(C, (int64_t)64), grid1d(npix, 512, 32));
   hipLaunchKernelGGL(dwconv7x7_wgrad_kernel, grid, dim3(64), 0, (hipStream_t)stream, x, dy, dw_tap_major, (int)B, (int)H, (int)W, (int)C);
   return msam2_check_launch("dwconv7x7_wgrad");
 }
@@ -885,8 +851,8 @@ __global__ __launch_bounds__(256) void col2im3x3s2_kernel(const float* __restric
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int c = (int)(i % C);
     const int64_t pix = i / C;
-    const int px = (int)(pix % W), py = (int)((pix / W) % H);
-    const int64_t b = pix / ((int64_t)W * H);
+    const PixelIndex pi(pix, H, W);
+    const int px = pi.x, py = pi.y;
     float acc = 0.f;
     // output (oy, ox) reads input (2 oy + ky - 1, 2 ox + kx - 1)
 #pragma unroll
@@ -897,7 +863,7 @@ __global__ __launch_bounds__(256) void col2im3x3s2_kernel(const float* __restric
       for (int kx = 0; kx < 3; ++kx) {
         const int u = px + 1 - kx;
         if (u < 0 || (u & 1) || (u >> 1) >= Wo) continue;
-        acc += dcols[((b * Ho + (t >> 1)) * Wo + (u >> 1)) * ld + (ky * 3 + kx) * C + c];
+        acc += dcols[((pi.b * Ho + (t >> 1)) * Wo + (u >> 1)) * ld + (ky * 3 + kx) * C + c];
       }
     }
     dx[i] = acc;
@@ -907,7 +873,7 @@ __global__ __launch_bounds__(256) void col2im3x3s2_kernel(const float* __restric
 extern "C" int msam2_col2im3x3s2(const float* dcols, int64_t ld, float* dx, int64_t B, int64_t H, int64_t W, int64_t C, void* stream) {
   MSAM2_REQUIRE(dcols && dx && B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0 && ld >= 9 * C, "col2im3x3s2: bad arguments");
   const int64_t total = B * H * W * C;
-  hipLaunchKernelGGL(col2im3x3s2_kernel, dim3((unsigned)min((int64_t)16384, cdiv(total, (int64_t)256))), dim3(256), 0, (hipStream_t)stream, dcols, ld, dx,
+  hipLaunchKernelGGL(col2im3x3s2_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream, dcols, ld, dx,
                      (int)B, (int)H, (int)W, (int)C);
   return msam2_check_launch("col2im3x3s2");
 }
@@ -933,16 +899,16 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
     const float* g = dy + pl * (int64_t)H * W;
     float acc = 0.f;
     for (int Y = Y0; Y <= Y1; ++Y) {
-      const float fy = fmaxf((Y + 0.5f) * sy - 0.5f, 0.f);
-      const int y0 = (int)fy, y1 = min(y0 + 1, h - 1);
-      const float ly = fy - y0;
+      const BilinearTap ty(Y, sy, h);
+      const int y0 = ty.i0, y1 = ty.i1;
+      const float ly = ty.l;
       const float wy = (y0 == y ? 1.f - ly : 0.f) + (y1 == y ? ly : 0.f);
       if (wy == 0.f) continue;
       float row = 0.f;
       for (int X = X0; X <= X1; ++X) {
-        const float fx = fmaxf((X + 0.5f) * sx - 0.5f, 0.f);
-        const int x0 = (int)fx, x1 = min(x0 + 1, w - 1);
-        const float lx = fx - x0;
+        const BilinearTap tx(X, sx, w);
+        const int x0 = tx.i0, x1 = tx.i1;
+        const float lx = tx.l;
         const float wx = (x0 == x ? 1.f - lx : 0.f) + (x1 == x ? lx : 0.f);
         row += wx * g[(int64_t)Y * W + X];
       }
@@ -955,7 +921,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
 extern "C" int msam2_bilinear_upsample_bwd(const float* dy, float* dx, int64_t planes, int64_t h, int64_t w, int64_t H, int64_t W, void* stream) {
   MSAM2_REQUIRE(dy && dx && planes > 0 && h > 0 && w > 0 && H >= h && W >= w, "bilinear_upsample_bwd: bad arguments (up-sampling only)");
   const int64_t total = planes * h * w;
-  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, dx,
+  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream, dy, dx,
                      (int)planes, (int)h, (int)w, (int)H, (int)W);
   return msam2_check_launch("bilinear_upsample_bwd");
 }
@@ -986,7 +952,7 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict
 extern "C" int msam2_bce_logits(const float* logits, const float* target, float* dlogits, float* loss, int64_t n, float pos_weight,
                                 void* stream) {
   MSAM2_REQUIRE(logits && target && dlogits && loss && n > 0, "bce_logits: bad arguments");
-  hipLaunchKernelGGL(bce_logits_kernel, dim3((unsigned)min((int64_t)1024, cdiv(n, 256))), dim3(256), 0, (hipStream_t)stream, logits, target,
+  hipLaunchKernelGGL(bce_logits_kernel, dim3(grid1d(n, 1024)), dim3(256), 0, (hipStream_t)stream, logits, target,
                      dlogits, loss, n, pos_weight);
   return msam2_check_launch("bce_logits");
 }
@@ -1007,7 +973,7 @@ extern "C" int msam2_adam_step(float* param, const float* grad, float* exp_avg, 
                                float eps, int64_t step, void* stream) {
   MSAM2_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "adam_step: bad arguments");
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)min((int64_t)4096, cdiv(n, 256))), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+  hipLaunchKernelGGL(adam_step_kernel, dim3(grid1d(n, 4096)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_sq, n, lr, beta1, beta2, eps, bc1, bc2);
   return msam2_check_launch("adam_step");
 }
@@ -1081,7 +1047,7 @@ extern "C" int msam2_adam_step_multi(void* const* params, const void* const* gra
       tb.n[i] = numel[j];
       nmax = max(nmax, numel[j]);
     }
-    dim3 grid((unsigned)min((int64_t)128, cdiv(nmax, 256)), (unsigned)nt);
+    dim3 grid(grid1d(nmax, 128), (unsigned)nt);
     hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, (hipStream_t)stream, tb, lr, beta1, beta2, eps, bc1, bc2, grad_scale,
                        1.f - lr * weight_decay, (const int*)step_counter, (int*)skipped_counter);
   }
@@ -1303,7 +1269,7 @@ extern "C" int msam2_attention_small_bwd(const void* q, int64_t q_bs, int64_t q_
   hipStream_t s = (hipStream_t)stream;
   // (zero fill by kernel, not hipMemsetAsync: see gemm_zero_kernel in gemm.hip)
   const int64_t short_n = B * (small_q ? Lq : Lk) * H * D;
-  const dim3 zgrid((unsigned)min((int64_t)1024, cdiv(short_n, (int64_t)256)));
+  const dim3 zgrid(grid1d(short_n, 1024));
   if (small_q) hipLaunchKernelGGL(zero2_kernel, zgrid, dim3(256), 0, s, dq, (float*)nullptr, short_n);
   else hipLaunchKernelGGL(zero2_kernel, zgrid, dim3(256), 0, s, dk, dv, short_n);
 #define ASB(DD, SQ)                                                                                                                      \
@@ -1328,12 +1294,8 @@ __global__ void maxpool2x2_bwd_kernel(const TI* __restrict__ x, int64_t ldx, con
   const int Ho = H / 2, Wo = W / 2;
   const int64_t total = (int64_t)B * Ho * Wo * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = i % C;
-    int64_t t = i / C;
-    const int xo = t % Wo;
-    t /= Wo;
-    const int yo = t % Ho;
-    const int b = t / Ho;
+    const Pool2x2Index ix(i, C, Ho, Wo);
+    const int c = ix.c, xo = ix.xo, yo = ix.yo, b = ix.b;
     const int64_t base = ((int64_t)b * H + 2 * yo) * W + 2 * xo;
     const int64_t pos[4] = {base, base + 1, base + W, base + W + 1};
     int arg = 0;
@@ -1353,9 +1315,11 @@ extern "C" int msam2_maxpool2x2_bwd(const void* x, int x_is_16bit, int64_t ldx, 
                                     int64_t B, int64_t H, int64_t W, int64_t C, void* stream) {
   MSAM2_REQUIRE(x && dy && dx && B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2_bwd: bad arguments");
   const int64_t total = B * (H / 2) * (W / 2) * C;
-  dim3 grid((unsigned)min((int64_t)8192, (total + 255) / 256)), block(256);
-  if (x_is_16bit) hipLaunchKernelGGL((maxpool2x2_bwd_kernel<op16>), grid, block, 0, (hipStream_t)stream, (const op16*)x, ldx, dy, lddy, dx, lddx, (int)B, (int)H, (int)W, (int)C);
-  else hipLaunchKernelGGL((maxpool2x2_bwd_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, ldx, dy, lddy, dx, lddx, (int)B, (int)H, (int)W, (int)C);
+  with_type(x_is_16bit, [&](auto ti) {
+    using TI = decltype(ti);
+    hipLaunchKernelGGL((maxpool2x2_bwd_kernel<TI>), dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, (const TI*)x, ldx, dy, lddy, dx, lddx, (int)B,
+                       (int)H, (int)W, (int)C);
+  });
   return msam2_check_launch("maxpool2x2_bwd");
 }
 
@@ -1422,12 +1386,11 @@ __global__ void window_move_kernel(unsigned char* __restrict__ img, int64_t ld_i
 extern "C" int msam2_window_move(void* img, int64_t ld_img, void* win, const void* fill, int64_t B, int64_t H, int64_t W, int64_t heads, int64_t D,
                                  int64_t ws, int elem_bytes, int to_windows, void* stream) {
   MSAM2_REQUIRE(img && win && B > 0 && H > 0 && W > 0 && heads > 0 && D > 0 && ws > 0, "window_move: bad arguments");
-  MSAM2_REQUIRE((elem_bytes == 2 || elem_bytes == 4) && (D * elem_bytes) % 16 == 0 && (ld_img * elem_bytes) % 16 == 0 &&
-                    (((uintptr_t)img | (uintptr_t)win | (uintptr_t)fill) & 15) == 0,
+  MSAM2_REQUIRE((elem_bytes == 2 || elem_bytes == 4) && (D * elem_bytes) % 16 == 0 && vec_ok(16 / elem_bytes, elem_bytes, ld_img, img, win, fill),
                 "window_move: 16-byte chunks (D * element size, row stride and pointers must be multiples of 16 bytes)");
   const int nwy = (int)((H + ws - 1) / ws), nwx = (int)((W + ws - 1) / ws), cpd = (int)(D * elem_bytes / 16);
   const int64_t total = to_windows ? B * nwy * nwx * heads * ws * ws * cpd : B * H * W * heads * cpd;
-  dim3 grid((unsigned)min((int64_t)16384, (total + 255) / 256)), block(256);
+  dim3 grid(grid1d(total, 16384)), block(256);
 #define WMOVE(TW, IDX)                                                                                                                        \
   hipLaunchKernelGGL((window_move_kernel<TW, IDX>), grid, block, 0, (hipStream_t)stream, (unsigned char*)img, ld_img * elem_bytes, (unsigned char*)win, \
                      (const unsigned char*)fill, (int)B, (int)H, (int)W, (int)heads, cpd, (int)ws, nwy, nwx)
@@ -1469,12 +1432,12 @@ __global__ void window_unpartition_cvt_kernel(op16* __restrict__ img, int64_t ld
 extern "C" int msam2_window_unpartition_cvt(void* img16, int64_t ld_img, const float* win, int64_t B, int64_t H, int64_t W, int64_t heads, int64_t D,
                                             int64_t ws, void* stream) {
   MSAM2_REQUIRE(img16 && win && B > 0 && H > 0 && W > 0 && heads > 0 && D > 0 && ws > 0, "window_unpartition_cvt: bad arguments");
-  MSAM2_REQUIRE(D % 8 == 0 && ld_img % 8 == 0 && (((uintptr_t)img16 | (uintptr_t)win) & 15) == 0,
+  MSAM2_REQUIRE(D % 8 == 0 && vec_ok(8, 2, ld_img, img16) && vec_ok(4, 4, win),
                 "window_unpartition_cvt: D and the row stride must be multiples of 8 elements, pointers 16-byte aligned");
   const int64_t total = B * H * W * heads * (D / 8);
   MSAM2_REQUIRE(total + 16384ll * 256 < (1ll << 32), "window_unpartition_cvt: volume beyond 32-bit chunk indices");
   const int nwy = (int)((H + ws - 1) / ws), nwx = (int)((W + ws - 1) / ws);
-  hipLaunchKernelGGL(window_unpartition_cvt_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(window_unpartition_cvt_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream,
                      (op16*)img16, ld_img, win, (int)B, (int)H, (int)W, (int)heads, (int)(D / 8), (int)ws, nwy, nwx);
   return msam2_check_launch("window_unpartition_cvt");
 }
@@ -1526,12 +1489,8 @@ __global__ void sumpool2x2_kernel(const float* __restrict__ dy, float* __restric
   const int Ho = H / 2, Wo = W / 2;
   const int64_t total = (int64_t)B * Ho * Wo * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = i % C;
-    int64_t t = i / C;
-    const int xo = t % Wo;
-    t /= Wo;
-    const int yo = t % Ho;
-    const int b = t / Ho;
+    const Pool2x2Index ix(i, C, Ho, Wo);
+    const int c = ix.c, xo = ix.xo, yo = ix.yo, b = ix.b;
     const int64_t base = (((int64_t)b * H + 2 * yo) * W + 2 * xo) * C + c;
     out[i] = dy[base] + dy[base + C] + dy[base + (int64_t)W * C] + dy[base + (int64_t)W * C + C];
   }
@@ -1540,7 +1499,7 @@ __global__ void sumpool2x2_kernel(const float* __restrict__ dy, float* __restric
 extern "C" int msam2_sumpool2x2(const float* dy, float* out, int64_t B, int64_t H, int64_t W, int64_t C, void* stream) {
   MSAM2_REQUIRE(dy && out && B > 0 && C > 0 && H % 2 == 0 && W % 2 == 0, "sumpool2x2: bad arguments");
   const int64_t total = B * (H / 2) * (W / 2) * C;
-  hipLaunchKernelGGL(sumpool2x2_kernel, dim3((unsigned)min((int64_t)8192, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dy, out,
+  hipLaunchKernelGGL(sumpool2x2_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, dy, out,
                      (int)B, (int)H, (int)W, (int)C);
   return msam2_check_launch("sumpool2x2");
 }
@@ -1549,9 +1508,6 @@ extern "C" int msam2_sumpool2x2(const float* dy, float* out, int64_t B, int64_t 
 // tokens, already summed over the batch) -> d pos_embed [C, bh, bw] through the transposed bicubic resize (same tap weights and border
 // clamping as the forward: the resize is separable, so the weight of source row y for output row yy is a 1-D table) and
 // d pos_embed_window [C, wsz, wsz] (sum over the tiling).
-__device__ __forceinline__ float cubic1_b(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2_b(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
-
 // Two passes, both gather form (no atomics: the gradients are run-to-run reproducible):
 //   rows pass   one workgroup per output row yy, one thread per channel: the row's w x C gradients are read once (coalesced over the
 //               channels) and reduced over xx into bw column sums weighted by the bicubic column weights of each source column plus
@@ -1565,7 +1521,7 @@ __device__ __forceinline__ float pos_bwd_weight(int o, int n_out, int n_src, int
   const float f = (o + 0.5f) * ((float)n_src / n_out) - 0.5f;
   const int i0 = (int)floorf(f);
   const float t = f - i0;
-  const float tap[4] = {cubic2_b(t + 1.f, A), cubic1_b(t, A), cubic1_b(1.f - t, A), cubic2_b(2.f - t, A)};
+  const float tap[4] = {cubic2(t + 1.f, A), cubic1(t, A), cubic1(1.f - t, A), cubic2(2.f - t, A)};
   float acc = 0.f;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -1684,14 +1640,14 @@ extern "C" int msam2_dropout(const void* x, int x_is_16bit, int64_t ldx, const f
   MSAM2_REQUIRE(x && y && rows > 0 && cols > 0 && p >= 0.f && p < 1.f, "dropout: bad arguments");
   const unsigned thr = (unsigned)fmin(4294967295.0, (double)p * 4294967296.0);
   const float inv_keep = 1.f / (1.f - p);
-  dim3 grid((unsigned)min((int64_t)8192, cdiv(rows * cols, 256))), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define DR(TI, TO) hipLaunchKernelGGL((dropout_kernel<TI, TO>), grid, block, 0, s, (const TI*)x, ldx, residual, ldr, (TO*)y, ldy, rows, cols, thr, inv_keep, seed, offset, (const uint64_t*)seed_dev)
-  if (x_is_16bit && y_is_16bit) DR(op16, op16);
-  else if (x_is_16bit) DR(op16, float);
-  else if (y_is_16bit) DR(float, op16);
-  else DR(float, float);
-#undef DR
+  with_type(x_is_16bit, [&](auto ti) {
+    with_type(y_is_16bit, [&](auto to) {
+      using TI = decltype(ti);
+      using TO = decltype(to);
+      hipLaunchKernelGGL((dropout_kernel<TI, TO>), dim3(grid1d(rows * cols, 8192)), dim3(256), 0, (hipStream_t)stream, (const TI*)x, ldx, residual, ldr, (TO*)y,
+                         ldy, rows, cols, thr, inv_keep, seed, offset, (const uint64_t*)seed_dev);
+    });
+  });
   return msam2_check_launch("dropout");
 }
 

@@ -266,7 +266,8 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
   const f32x2 phi = __builtin_elementwise_fma(xc, q, bc(0.5f));
   return x * phi;
 }
-__device__ __forceinline__ float gelu_erf(float x) {
+// Phi(x) itself: the factor of the GELU and the first term of its derivative Phi(x) + x phi(x) (act_bwd_vec_kernel)
+__device__ __forceinline__ float gelu_phi(float x) {
   const float xc = __builtin_amdgcn_fmed3f(x, -MSAM2_GELU_X, MSAM2_GELU_X);
   const float u = xc * xc;
   float q = __builtin_fmaf(u, MSAM2_GELU_Q8, MSAM2_GELU_Q7);
@@ -277,8 +278,9 @@ __device__ __forceinline__ float gelu_erf(float x) {
   q = __builtin_fmaf(q, u, MSAM2_GELU_Q2);
   q = __builtin_fmaf(q, u, MSAM2_GELU_Q1);
   q = __builtin_fmaf(q, u, MSAM2_GELU_Q0);
-  return x * __builtin_fmaf(xc, q, 0.5f);
+  return __builtin_fmaf(xc, q, 0.5f);
 }
+__device__ __forceinline__ float gelu_erf(float x) { return x * gelu_phi(x); }
 #endif
 // The same function with erf by Abramowitz-Stegun 7.1.26 (|abs error| <= 1.5e-7: at fp32 round-off):  erf(a) = sign(a) (1 - P(t) e^{-a^2}),
 // t = 1 / (1 + p |a|);  gelu(x) = max(x, 0) - 0.5 |x| P(t) e^{-a^2}   (both signs; no 1 - (1 - ..) cancellation on the negative side).
@@ -305,6 +307,9 @@ __device__ __forceinline__ float fast_erf(float x) {
   const float e = 1.0f - poly * __expf(-ax * ax);
   return copysignf(e, x);
 }
+#ifdef MSAM2_GELU_AS
+__device__ __forceinline__ float gelu_phi(float x) { return 0.5f * (1.f + fast_erf(x * 0.70710678118654752f)); }
+#endif
 
 // Counter-based dropout mask shared by the element-wise dropout kernel (backward.hip) and the flash attention kernels (attention.hip,
 // attention_bwd.hip): element idx of stream seed is KEPT iff the upper half of splitmix64(seed + idx * golden) is >= thr = p * 2^32.
@@ -336,3 +341,79 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- building blocks of the pointwise and row kernels (elementwise.hip, conv.hip, backward.hip): one definition each ----
+
+// sum over the 16 lanes that share a row in the 16-lanes-per-row LayerNorm kernels (lanes l ^ 1, 2, 4, 8: four shuffles), in place
+// (layernorm_kernel: with the value form two of its instances are scheduled in another order) and as a value
+__device__ __forceinline__ void group16_add(float& v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+}
+__device__ __forceinline__ float group16_sum(float v) {
+  group16_add(v);
+  return v;
+}
+
+// the two pieces of the bicubic convolution kernel (A = -0.75 in torch): |x| <= 1 and 1 < |x| < 2 -- the position-table resize and its adjoint
+__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
+__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
+
+// element i of a [B, H/2, W/2, C] map (the output of a 2x2 / stride-2 pool over [B, H, W, C]) -> channel, output pixel, batch element
+struct Pool2x2Index {
+  int c, xo, yo, b;
+  __device__ __forceinline__ Pool2x2Index(int64_t i, int C, int Ho, int Wo) {
+    c = i % C;
+    int64_t t = i / C;
+    xo = t % Wo;
+    t /= Wo;
+    yo = t % Ho;
+    b = t / Ho;
+  }
+};
+
+// bilinear resize, align_corners = False: output o of a resize by scale = n_src / n_out reads sources i0 and i1 with weights 1 - l and l
+struct BilinearTap {
+  int i0, i1;
+  float l;
+  template <typename I>
+  __device__ __forceinline__ BilinearTap(I o, float scale, int n_src) {
+    const float f = fmaxf((o + 0.5f) * scale - 0.5f, 0.f);
+    i0 = (int)f;
+    i1 = min(i0 + 1, n_src - 1);
+    l = f - i0;
+  }
+};
+
+// pixel index of a [B, H, W] raster -> (x, y, b)
+struct PixelIndex {
+  int x, y;
+  int64_t b;
+  __device__ __forceinline__ PixelIndex(int64_t pix, int H, int W) : x((int)(pix % W)), y((int)((pix / W) % H)), b(pix / ((int64_t)W * H)) {}
+};
+
+// output pixel (b, Y, X) of a ConvTranspose2d(k2, s2) on the 2h x 2w grid -> its source token and which of the token's four outputs it is
+struct ConvT2x2Index {
+  int64_t tok;
+  int sub;
+  __device__ __forceinline__ ConvT2x2Index(int64_t b, int Y, int X, int h, int w) : tok((b * h + Y / 2) * w + X / 2), sub((Y & 1) * 2 + (X & 1)) {}
+};
+
+// Host side of those entries: the type ladder, the grid clamp and the "may I take the vector kernel" test, one statement each.
+// An is_16bit flag of the ABI as a type: f(T{}) with T = op16 or float; nested for two or three flags.
+template <typename F>
+static inline void with_type(int is_16bit, F&& f) {
+  if (is_16bit) f(op16{});
+  else f(float{});
+}
+
+// workgroups of a grid-stride launch: one per `threads` elements, at most `cap` (the expression every site had: `min` takes its int overload
+// here, so a total beyond 2^39 elements -- more than the device's memory holds -- would not be clamped)
+static inline unsigned grid1d(int64_t total, int64_t cap, int64_t threads = 256) { return (unsigned)min(cap, (total + threads - 1) / threads); }
+
+// Can every one of `a` take an access of N elements of S bytes?  A pointer: its address is a multiple of N S bytes (null passes: an
+// optional tensor that is absent).  A stride in elements: every row it leads to keeps that alignment, i.e. it is a multiple of N.
+static inline bool vec_ok1(const void* p, int64_t n, int64_t s) { return (uintptr_t)p % (uintptr_t)(n * s) == 0; }
+static inline bool vec_ok1(int64_t ld, int64_t n, int64_t s) { return (ld * s) % (n * s) == 0; }
+template <typename... A>
+static inline bool vec_ok(int n, int s, A... a) { return (vec_ok1(a, n, s) && ...); }

@@ -35,9 +35,9 @@ __global__ void im2col_patch_kernel(const float* __restrict__ img, op16* __restr
 
 extern "C" int msam2_im2col_patch7x7s4(const float* img, void* out, int64_t B, int64_t S, void* stream) {
   MSAM2_REQUIRE(img && out && B > 0 && S > 0 && S % 4 == 0, "im2col_patch: bad arguments");
-  MSAM2_REQUIRE(((uintptr_t)out & 15) == 0, "im2col_patch: output must be 16-byte aligned");
+  MSAM2_REQUIRE(vec_ok(8, 2, out), "im2col_patch: output must be 16-byte aligned");
   const int64_t total = B * (S / 4) * (S / 4) * 20;
-  hipLaunchKernelGGL(im2col_patch_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(im2col_patch_kernel, dim3(grid1d(total, 16384)), dim3(256), 0,
                      (hipStream_t)stream, img, (op16*)out, (int)B, (int)S);
   return msam2_check_launch("im2col_patch7x7s4");
 }
@@ -191,7 +191,7 @@ extern "C" int msam2_patch_embed7x7s4(const float* img, const void* w_perm, cons
                                       int64_t S, int64_t E, void* stream) {
   MSAM2_REQUIRE(img && w_perm && bias && out && B > 0 && S > 0 && E > 0, "patch_embed: bad arguments");
   MSAM2_REQUIRE(S % 4 == 0 && (S / 4) % 32 == 0 && E <= 128, "patch_embed: needs (S / 4) %% 32 == 0 and E <= 128 (S=%lld E=%lld)", (long long)S, (long long)E);
-  MSAM2_REQUIRE((((uintptr_t)img | (uintptr_t)w_perm) & 15) == 0, "patch_embed: image and weights must be 16-byte aligned");
+  MSAM2_REQUIRE(vec_ok(4, 4, img) && vec_ok(8, 2, w_perm), "patch_embed: image and weights must be 16-byte aligned");
   MSAM2_REQUIRE(B * (S / 4) * (S / 4) * E < (1ll << 40), "patch_embed: problem too large");
   const int So = (int)(S / 4);
   const int nt = So % 128 == 0 ? 128 : (So % 64 == 0 ? 64 : 32);     // tokens per segment: whole segments per token row
@@ -248,8 +248,8 @@ extern "C" int msam2_im2col3x3s2(const void* x, void* out, int64_t B, int64_t H,
                 "im2col3x3s2: bad arguments");
   const int64_t total = B * (H / 2) * (W / 2) * (ld / 4);
   MSAM2_REQUIRE(total < (1ll << 31), "im2col3x3s2: more than 2^31 output groups");
-  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 7) == 0, "im2col3x3s2: x and out must be 8-byte aligned (4-channel groups)");
-  hipLaunchKernelGGL(im2col3x3s2_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0,
+  MSAM2_REQUIRE(vec_ok(4, 2, x, out), "im2col3x3s2: x and out must be 8-byte aligned (4-channel groups)");
+  hipLaunchKernelGGL(im2col3x3s2_kernel, dim3(grid1d(total, 16384)), dim3(256), 0,
                      (hipStream_t)stream, (const op16*)x, (op16*)out, (int)B, (int)H, (int)W, (int)C, (int)ld);
   return msam2_check_launch("im2col3x3s2");
 }
@@ -327,8 +327,9 @@ extern "C" int msam2_conv3x3s2_ln_gelu(const void* x, int in_is_16bit, const flo
   MSAM2_REQUIRE(mask_mode == 0 || (Cin == 1 && !in_is_16bit), "conv3x3s2_ln_gelu: mask transform needs the fp32 1-channel input");
   MSAM2_REQUIRE(Cin == 1 ? !in_is_16bit : in_is_16bit, "conv3x3s2_ln_gelu: layer 1 takes fp32, later layers op16");
   const int64_t total = B * (H / 2) * (W / 2);
-  dim3 grid((unsigned)min((int64_t)8192, (total + 127) / 128)), block(128);
+  const dim3 grid(grid1d(total, 8192, 128)), block(128);
   hipStream_t s = (hipStream_t)stream;
+  // Cin alone picks the instance (the checks above tie the input type and the mask transform to it): not a with_type ladder
   if (Cin == 1)
     hipLaunchKernelGGL((conv3x3s2_ln_gelu_kernel<1, 4, float>), grid, block, 0, s, (const float*)x, weight, bias, ln_w, ln_b,
                        (op16*)y, (int)B, (int)H, (int)W, mask_mode, mask_scale, mask_bias);
@@ -402,7 +403,7 @@ extern "C" int msam2_dwconv7x7_ln(const float* x, const float* weight_tap_major,
   MSAM2_REQUIRE(x && weight_tap_major && bias && ln_w && ln_b && y, "dwconv7x7_ln: null tensor");
   MSAM2_REQUIRE(C == 256, "dwconv7x7_ln: built for C=256 (one wave per pixel group, 4 channels per lane)");
   MSAM2_REQUIRE(B > 0 && H > 0 && W > 0, "dwconv7x7_ln: bad shape");
-  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)weight_tap_major | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y & 7) == 0,
+  MSAM2_REQUIRE(vec_ok(4, 4, x, weight_tap_major, bias) && vec_ok(4, 2, y),
                 "dwconv7x7_ln: x, weight and bias must be 16-byte aligned, y 8-byte aligned (4-channel groups)");
   const int64_t groups = B * H * ((W + DW_PIX - 1) / DW_PIX);
   hipLaunchKernelGGL(dwconv7x7_ln_kernel, dim3(cdiv(groups * 64, 256)), dim3(256), 0, (hipStream_t)stream, x, weight_tap_major, bias,
@@ -426,13 +427,10 @@ __global__ void pixel_shuffle_kernel(const op16* __restrict__ g, const float* __
   const int ch = ppw > 1 ? lane % C : lane;
   const int64_t pix = wv * ppw + sub_px;
   if (pix >= (int64_t)B * H * W) return;
-  const int X = pix % W;
-  const int Y = (pix / W) % H;
-  const int b = pix / ((int64_t)W * H);
-  const int64_t tok = ((int64_t)b * h + Y / 2) * w + X / 2;
-  const int sub = (Y & 1) * 2 + (X & 1);
+  const PixelIndex px(pix, H, W);
+  const ConvT2x2Index t((int)px.b, px.y, px.x, h, w);
   float v = 0.f;
-  if (ch < C) v = op2f(g[tok * 4 * C + sub * C + ch]) + bias[ch] + op2f(skip[pix * C + ch]);
+  if (ch < C) v = op2f(g[t.tok * 4 * C + t.sub * C + ch]) + bias[ch] + op2f(skip[pix * C + ch]);
   if (ln_w) {
     const float mean = wave_sum(ch < C ? v : 0.f) / C;
     const float d = ch < C ? v - mean : 0.f;
@@ -456,12 +454,10 @@ __global__ void pixel_shuffle8_kernel(const op16* __restrict__ g, const float* _
   const int c0 = (int)(gid % G) * 8;
   const bool live = pix < (int64_t)B * H * W;
   const int64_t pp = live ? pix : 0;
-  const int X = pp % W;
-  const int Y = (pp / W) % H;
-  const int b = pp / ((int64_t)W * H);
-  const int64_t tok = ((int64_t)b * h + Y / 2) * w + X / 2;
-  const int sub = (Y & 1) * 2 + (X & 1);
-  const op16x8 gv = *reinterpret_cast<const op16x8*>(g + tok * 4 * C + sub * C + c0);
+  const PixelIndex px(pp, H, W);
+  const int b = (int)px.b;
+  const ConvT2x2Index t(b, px.y, px.x, h, w);
+  const op16x8 gv = *reinterpret_cast<const op16x8*>(g + t.tok * 4 * C + t.sub * C + c0);
   // SHARED_SKIP: one skip map serves every batch element (N prompt sets on one image: batch stride 0)
   const int64_t sp = SHARED_SKIP ? pp - (int64_t)b * H * W : pp;
   float sk[8];
@@ -506,21 +502,20 @@ __global__ void pixel_shuffle8_kernel(const op16* __restrict__ g, const float* _
   *reinterpret_cast<op16x8*>(y + pix * C + c0) = o;
 }
 
+// pixel_shuffle8_kernel's 16-byte accesses: eight 16-bit values (skip in fp32: twice four), four fp32 of bias / ln_w / ln_b (which may be absent)
+static bool pixel_shuffle8_aligned(const void* gemm_out, const void* skip, const void* y, const float* bias, const float* ln_w, const float* ln_b) {
+  return vec_ok(8, 2, gemm_out, skip, y) && vec_ok(4, 4, bias, ln_w, ln_b);
+}
+
 template <typename TS>
 static int convt2x2_shuffle_launch(const void* gemm_out, const float* bias, const TS* skip, const float* ln_w, const float* ln_b, void* y,
                                    int64_t B, int64_t h, int64_t w, int64_t C, void* stream) {
   MSAM2_REQUIRE(gemm_out && bias && skip && y, "convt2x2_shuffle: null tensor");
   MSAM2_REQUIRE(C > 0 && C <= 64, "convt2x2_shuffle: C must be <= 64");
   const int64_t pix = B * 4 * h * w;
-  const bool al = (((uintptr_t)gemm_out | (uintptr_t)skip | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)ln_w | (uintptr_t)ln_b) & 15) == 0;
-  if (al && (C == 64 || C == 32)) {
-    const int64_t threads = pix * (C / 8);
-    if (C == 64)
-      hipLaunchKernelGGL((pixel_shuffle8_kernel<64, TS>), dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, (const op16*)gemm_out, bias,
-                         skip, ln_w, ln_b, (op16*)y, (int)B, (int)h, (int)w);
-    else
-      hipLaunchKernelGGL((pixel_shuffle8_kernel<32, TS>), dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, (const op16*)gemm_out, bias,
-                         skip, ln_w, ln_b, (op16*)y, (int)B, (int)h, (int)w);
+  if (pixel_shuffle8_aligned(gemm_out, skip, y, bias, ln_w, ln_b) && (C == 64 || C == 32)) {
+    hipLaunchKernelGGL((C == 64 ? pixel_shuffle8_kernel<64, TS> : pixel_shuffle8_kernel<32, TS>), dim3(cdiv(pix * (C / 8), 256)), dim3(256), 0,
+                       (hipStream_t)stream, (const op16*)gemm_out, bias, skip, ln_w, ln_b, (op16*)y, (int)B, (int)h, (int)w);
     return msam2_check_launch("convt2x2_shuffle");
   }
   MSAM2_REQUIRE(sizeof(TS) == 2, "convt2x2_shuffle: the fp32-skip form needs C = 32 / 64 and 16-byte aligned tensors");
@@ -552,22 +547,17 @@ extern "C" int msam2_convt2x2_shuffle_shared(const void* gemm_out, const float* 
   MSAM2_REQUIRE(B > 0 && h > 0 && w > 0 && (C == 32 || C == 64), "convt2x2_shuffle_shared: C must be 32 or 64");
   MSAM2_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "convt2x2_shuffle_shared: ln_w and ln_b go together");
   MSAM2_REQUIRE(skip_batch_stride == 0 || skip_batch_stride == 4 * h * w * C, "convt2x2_shuffle_shared: skip_batch_stride must be 0 or 4*h*w*C");
-  const bool al = (((uintptr_t)gemm_out | (uintptr_t)skip | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)ln_w | (uintptr_t)ln_b) & 15) == 0;
-  MSAM2_REQUIRE(al, "convt2x2_shuffle_shared: tensors must be 16-byte aligned");
+  MSAM2_REQUIRE(pixel_shuffle8_aligned(gemm_out, skip, y, bias, ln_w, ln_b), "convt2x2_shuffle_shared: tensors must be 16-byte aligned");
   if (skip_batch_stride != 0)
     return skip_is_16bit ? msam2_convt2x2_shuffle(gemm_out, bias, skip, ln_w, ln_b, y, B, h, w, C, stream)
                          : msam2_convt2x2_shuffle_f32skip(gemm_out, bias, (const float*)skip, ln_w, ln_b, y, B, h, w, C, stream);
   const int64_t threads = B * 4 * h * w * (C / 8);
   const dim3 grid(cdiv(threads, 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define PS8(CC, TS) hipLaunchKernelGGL((pixel_shuffle8_kernel<CC, TS, true>), grid, block, 0, s, (const op16*)gemm_out, bias, (const TS*)skip, ln_w, \
-                                       ln_b, (op16*)y, (int)B, (int)h, (int)w)
-  if (C == 64) {
-    if (skip_is_16bit) PS8(64, op16); else PS8(64, float);
-  } else {
-    if (skip_is_16bit) PS8(32, op16); else PS8(32, float);
-  }
-#undef PS8
+  with_type(skip_is_16bit, [&](auto ts) {
+    using TS = decltype(ts);
+    hipLaunchKernelGGL((C == 64 ? pixel_shuffle8_kernel<64, TS, true> : pixel_shuffle8_kernel<32, TS, true>), grid, block, 0, (hipStream_t)stream,
+                       (const op16*)gemm_out, bias, (const TS*)skip, ln_w, ln_b, (op16*)y, (int)B, (int)h, (int)w);
+  });
   return msam2_check_launch("convt2x2_shuffle_shared");
 }
 
@@ -600,7 +590,7 @@ extern "C" int msam2_hyper_masks(const float* hyper, const void* upscaled, float
                                  void* stream) {
   MSAM2_REQUIRE(hyper && upscaled && masks, "hyper_masks: null tensor");
   MSAM2_REQUIRE(C == 32 && K > 0 && K <= 8 && n > 0 && P > 0, "hyper_masks: built for C=32, K<=8");
-  MSAM2_REQUIRE(((uintptr_t)upscaled & 15) == 0, "hyper_masks: the up-scaled features must be 16-byte aligned (8-channel loads)");
+  MSAM2_REQUIRE(vec_ok(8, 2, upscaled), "hyper_masks: the up-scaled features must be 16-byte aligned (8-channel loads)");
   hipLaunchKernelGGL(hyper_masks_kernel, dim3(cdiv(P, 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, hyper,
                      (const op16*)upscaled, masks, (int)n, (int)K, (int)P, (int)C);
   return msam2_check_launch("hyper_masks");
@@ -723,7 +713,7 @@ extern "C" int msam2_select_mask(const float* masks, const float* ious, const fl
                                  float* iou_sel, int64_t n, int64_t P, int multimask, int dynamic_stability, float delta,
                                  float thresh, void* stream) {
   MSAM2_REQUIRE(masks && ious && obj_scores && low_res && sel && iou_sel && n > 0 && P > 0, "select_mask: bad arguments");
-  MSAM2_REQUIRE(P % 4 == 0 && ((uintptr_t)masks & 15) == 0, "select_mask: masks must be 16-byte aligned with H*W %% 4 == 0");
+  MSAM2_REQUIRE(P % 4 == 0 && vec_ok(4, 4, masks), "select_mask: masks must be 16-byte aligned with H*W %% 4 == 0");
   hipLaunchKernelGGL(select_mask_kernel, dim3((unsigned)n, SELECT_SPLIT), dim3(256), 0, (hipStream_t)stream, masks, ious, obj_scores,
                      low_res, sel, iou_sel, (int)P, multimask, dynamic_stability, delta, thresh);
   return msam2_check_launch("select_mask");
@@ -789,13 +779,11 @@ extern "C" int msam2_space_to_depth(const void* x, int in_is_16bit, void* out, i
   MSAM2_REQUIRE(x && out && B > 0 && C > 0 && k > 0 && H % k == 0 && W % k == 0 && ld >= k * k * C && ld % 8 == 0,
                 "space_to_depth: bad arguments");
   const int64_t total = B * (H / k) * (W / k) * ld;
-  dim3 grid((unsigned)min((int64_t)8192, (total + 255) / 256)), block(256);
-  if (in_is_16bit)
-    hipLaunchKernelGGL((space_to_depth_kernel<op16>), grid, block, 0, (hipStream_t)stream, (const op16*)x, (op16*)out, (int)B, (int)H,
+  with_type(in_is_16bit, [&](auto ti) {
+    using TI = decltype(ti);
+    hipLaunchKernelGGL((space_to_depth_kernel<TI>), dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, (const TI*)x, (op16*)out, (int)B, (int)H,
                        (int)W, (int)C, (int)k, (int)ld);
-  else
-    hipLaunchKernelGGL((space_to_depth_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)x, (op16*)out, (int)B, (int)H,
-                       (int)W, (int)C, (int)k, (int)ld);
+  });
   return msam2_check_launch("space_to_depth");
 }
 

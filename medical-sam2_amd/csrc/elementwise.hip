@@ -1,6 +1,7 @@
 // HBM-bound row / elementwise kernels of the per-slice forward (gfx950): LayerNorm, strided add+cast, 2x2 max-pool,
 // nearest-2x add, axial RoPE, bilinear up-sampling, and the input-independent position tables.
 #include "common.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------------------------
 // LayerNorm over the last dim (nn.LayerNorm / LayerNorm2d on NHWC tokens): hieradet.py:138,166; memory_attention.py:
@@ -63,8 +64,7 @@ __global__ void layernorm_kernel(const TI* __restrict__ x, int64_t ldx, const fl
       s += v[j][e];
     }
   }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  group16_add(s);
   const float mean = s / C;
   float q = 0.f;
 #pragma unroll
@@ -76,8 +76,7 @@ __global__ void layernorm_kernel(const TI* __restrict__ x, int64_t ldx, const fl
       q += d * d;
     }
   }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  group16_add(q);
   const float rstd = 1.0f / sqrtf(q / C + eps);
   if (!live) return;
   TO* yr = y + row * ldy;
@@ -149,6 +148,22 @@ __global__ void layernorm_scalar_kernel(const TI* __restrict__ x, int64_t ldx, c
   }
 }
 
+// the CHUNKS instance of layernorm_kernel for a row of C elements (16 lanes x 4 elements per chunk): 2 / 4 / 6 / 12 / 16
+template <typename TI, typename TO>
+static void layernorm_vec_launch(const TI* x, int64_t ldx, const float* w, const float* b, TO* y, int64_t ldy, int64_t rows, int C, float eps, int act,
+                                 op16* y2, int64_t ldy2, hipStream_t s) {
+  const dim3 grid(cdiv(rows * 16, 256)), block(256);
+  const int chunks = (C / 4 + 15) / 16;
+  auto launch = [&](auto ch) {
+    hipLaunchKernelGGL((layernorm_kernel<TI, TO, decltype(ch)::value>), grid, block, 0, s, x, ldx, w, b, y, ldy, rows, C, eps, act, y2, ldy2);
+  };
+  if (chunks <= 2) launch(std::integral_constant<int, 2>{});
+  else if (chunks <= 4) launch(std::integral_constant<int, 4>{});
+  else if (chunks <= 6) launch(std::integral_constant<int, 6>{});
+  else if (chunks <= 12) launch(std::integral_constant<int, 12>{});
+  else launch(std::integral_constant<int, 16>{});
+}
+
 extern "C" int msam2_layernorm(const void* x, int in_is_16bit, int64_t ldx, const float* weight, const float* bias, void* y,
                                int out_is_16bit, int64_t ldy, int64_t rows, int64_t C, float eps, int act, void* stream) {
   MSAM2_REQUIRE(x && y && weight && bias, "layernorm: null tensor");
@@ -156,38 +171,19 @@ extern "C" int msam2_layernorm(const void* x, int in_is_16bit, int64_t ldx, cons
   hipStream_t s = (hipStream_t)stream;
   // the vector kernel moves four elements per access: 16 bytes of fp32, 8 bytes of the 16-bit type -- x and y must be aligned to the width
   // of their own access (an fp32 y that is only 8-byte aligned takes the scalar kernel: tests/test_pointwise_variants_gpu.py::test_layernorm_scalar_paths)
-  const uintptr_t xmask = in_is_16bit ? 7 : 15, ymask = out_is_16bit ? 7 : 15;
-  const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)x & xmask) == 0) && (((uintptr_t)y & ymask) == 0) &&
-                   (((uintptr_t)weight & 15) == 0) && (((uintptr_t)bias & 15) == 0);
-  if (vec) {
-    dim3 grid(cdiv(rows * 16, 256)), block(256);
-    const int chunks = (int)((C / 4 + 15) / 16);
-#define LN_V(TI, TO, CH) \
-  hipLaunchKernelGGL((layernorm_kernel<TI, TO, CH>), grid, block, 0, s, (const TI*)x, ldx, weight, bias, (TO*)y, ldy, rows, (int)C, eps, act)
-#define LN_VC(TI, TO)                                     \
-  do {                                                    \
-    if (chunks <= 2) LN_V(TI, TO, 2);                     \
-    else if (chunks <= 4) LN_V(TI, TO, 4);                \
-    else if (chunks <= 6) LN_V(TI, TO, 6);                \
-    else if (chunks <= 12) LN_V(TI, TO, 12);              \
-    else LN_V(TI, TO, 16);                                \
-  } while (0)
-    if (in_is_16bit && out_is_16bit) LN_VC(op16, op16);
-    else if (in_is_16bit) LN_VC(op16, float);
-    else if (out_is_16bit) LN_VC(float, op16);
-    else LN_VC(float, float);
-#undef LN_VC
-#undef LN_V
-  } else {
-    dim3 grid(cdiv(rows * 64, 256)), block(256);
-#define LN_LAUNCH(TI, TO) \
-  hipLaunchKernelGGL((layernorm_scalar_kernel<TI, TO>), grid, block, 0, s, (const TI*)x, ldx, weight, bias, (TO*)y, ldy, rows, (int)C, eps, act)
-    if (in_is_16bit && out_is_16bit) LN_LAUNCH(op16, op16);
-    else if (in_is_16bit) LN_LAUNCH(op16, float);
-    else if (out_is_16bit) LN_LAUNCH(float, op16);
-    else LN_LAUNCH(float, float);
-#undef LN_LAUNCH
-  }
+  const bool vec = (C % 4 == 0) && vec_ok(4, in_is_16bit ? 2 : 4, ldx, x) && vec_ok(4, out_is_16bit ? 2 : 4, ldy, y) && vec_ok(4, 4, weight, bias);
+  with_type(in_is_16bit, [&](auto ti) {
+    with_type(out_is_16bit, [&](auto to) {
+      using TI = decltype(ti);
+      using TO = decltype(to);
+      if (vec) {
+        layernorm_vec_launch((const TI*)x, ldx, weight, bias, (TO*)y, ldy, rows, (int)C, eps, act, nullptr, 0, s);
+      } else {
+        hipLaunchKernelGGL((layernorm_scalar_kernel<TI, TO>), dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, (const TI*)x, ldx, weight, bias, (TO*)y, ldy,
+                           rows, (int)C, eps, act);
+      }
+    });
+  });
   return msam2_check_launch("layernorm");
 }
 
@@ -196,20 +192,10 @@ extern "C" int msam2_layernorm(const void* x, int in_is_16bit, int64_t ldx, cons
 extern "C" int msam2_layernorm_dual(const float* x, int64_t ldx, const float* weight, const float* bias, float* y, int64_t ldy, void* y16,
                                     int64_t ldy16, int64_t rows, int64_t C, float eps, void* stream) {
   MSAM2_REQUIRE(x && y && y16 && weight && bias, "layernorm_dual: null tensor");
-  MSAM2_REQUIRE(rows > 0 && C > 0 && C <= 1024 && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldy16 % 4 == 0,
+  MSAM2_REQUIRE(rows > 0 && C > 0 && C <= 1024 && C % 4 == 0 && vec_ok(4, 4, ldx, ldy) && vec_ok(4, 2, ldy16),
                 "layernorm_dual: rows=%lld C=%lld unsupported (C <= 1024, multiples of 4)", (long long)rows, (long long)C);
-  MSAM2_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)weight | (uintptr_t)bias) & 15) == 0 && ((uintptr_t)y16 & 7) == 0, "layernorm_dual: alignment");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(cdiv(rows * 16, 256)), block(256);
-  const int chunks = (int)((C / 4 + 15) / 16);
-#define LN_D(CH) \
-  hipLaunchKernelGGL((layernorm_kernel<float, float, CH>), grid, block, 0, s, x, ldx, weight, bias, y, ldy, rows, (int)C, eps, 0, (op16*)y16, ldy16)
-  if (chunks <= 2) LN_D(2);
-  else if (chunks <= 4) LN_D(4);
-  else if (chunks <= 6) LN_D(6);
-  else if (chunks <= 12) LN_D(12);
-  else LN_D(16);
-#undef LN_D
+  MSAM2_REQUIRE(vec_ok(4, 4, x, y, weight, bias) && vec_ok(4, 2, y16), "layernorm_dual: alignment");
+  layernorm_vec_launch(x, ldx, weight, bias, y, ldy, rows, (int)C, eps, 0, (op16*)y16, ldy16, (hipStream_t)stream);
   return msam2_check_launch("layernorm_dual");
 }
 
@@ -268,44 +254,23 @@ extern "C" int msam2_add_cast(const void* a, int a_is_16bit, int64_t a_s0, int64
   MSAM2_REQUIRE(D0 > 0 && D1 > 0 && C > 0, "add_cast: empty volume");
   const int64_t total = D0 * D1 * C;
   hipStream_t s = (hipStream_t)stream;
-  const int key = (a_is_16bit ? 4 : 0) | (b_is_16bit ? 2 : 0) | (out_is_16bit ? 1 : 0);
-  const int asz = a_is_16bit ? 2 : 4, bsz = b_is_16bit ? 2 : 4, osz = out_is_16bit ? 2 : 4;
-  const bool vec = (C % 4 == 0) && total / 4 < (1ll << 31) && (a_s0 % 4 == 0) && (a_s1 % 4 == 0) && (((uintptr_t)a % (4 * asz)) == 0) &&
-                   (((uintptr_t)out % (4 * osz)) == 0) &&
-                   (!b || ((b_s0 % 4 == 0) && (b_s1 % 4 == 0) && (((uintptr_t)b % (4 * bsz)) == 0)));
-  if (vec) {
-    dim3 grid((unsigned)min((int64_t)16384, (total / 4 + 255) / 256)), block(256);
-#define ACV(TA, TB, TO)                                                                                                          \
-  hipLaunchKernelGGL((add_cast_vec_kernel<TA, TB, TO>), grid, block, 0, s, (const TA*)a, a_s0, a_s1, (const TB*)b, b_s0, b_s1, alpha, \
-                     (TO*)out, (unsigned)D0, (unsigned)D1, (unsigned)(C / 4))
-    switch (key) {
-      case 0: ACV(float, float, float); break;
-      case 1: ACV(float, float, op16); break;
-      case 2: ACV(float, op16, float); break;
-      case 3: ACV(float, op16, op16); break;
-      case 4: ACV(op16, float, float); break;
-      case 5: ACV(op16, float, op16); break;
-      case 6: ACV(op16, op16, float); break;
-      default: ACV(op16, op16, op16); break;
-    }
-#undef ACV
-    return msam2_check_launch("add_cast");
-  }
-  dim3 grid((unsigned)min((int64_t)8192, (total + 255) / 256)), block(256);
-#define AC(TA, TB, TO)                                                                                                   \
-  hipLaunchKernelGGL((add_cast_kernel<TA, TB, TO>), grid, block, 0, s, (const TA*)a, a_s0, a_s1, (const TB*)b, b_s0, b_s1, \
-                     alpha, (TO*)out, D0, D1, (int)C)
-  switch (key) {
-    case 0: AC(float, float, float); break;
-    case 1: AC(float, float, op16); break;
-    case 2: AC(float, op16, float); break;
-    case 3: AC(float, op16, op16); break;
-    case 4: AC(op16, float, float); break;
-    case 5: AC(op16, float, op16); break;
-    case 6: AC(op16, op16, float); break;
-    default: AC(op16, op16, op16); break;
-  }
-#undef AC
+  const bool vec = (C % 4 == 0) && total / 4 < (1ll << 31) && vec_ok(4, a_is_16bit ? 2 : 4, a_s0, a_s1, a) && vec_ok(4, out_is_16bit ? 2 : 4, out) &&
+                   (!b || vec_ok(4, b_is_16bit ? 2 : 4, b_s0, b_s1, b));
+  with_type(a_is_16bit, [&](auto ta) {
+    with_type(b_is_16bit, [&](auto tb) {
+      with_type(out_is_16bit, [&](auto to) {
+        using TA = decltype(ta);
+        using TB = decltype(tb);
+        using TO = decltype(to);
+        if (vec)
+          hipLaunchKernelGGL((add_cast_vec_kernel<TA, TB, TO>), dim3(grid1d(total / 4, 16384)), dim3(256), 0, s, (const TA*)a, a_s0, a_s1, (const TB*)b,
+                             b_s0, b_s1, alpha, (TO*)out, (unsigned)D0, (unsigned)D1, (unsigned)(C / 4));
+        else
+          hipLaunchKernelGGL((add_cast_kernel<TA, TB, TO>), dim3(grid1d(total, 8192)), dim3(256), 0, s, (const TA*)a, a_s0, a_s1, (const TB*)b, b_s0,
+                             b_s1, alpha, (TO*)out, D0, D1, (int)C);
+      });
+    });
+  });
   return msam2_check_launch("add_cast");
 }
 
@@ -318,6 +283,7 @@ __global__ void maxpool2x2_kernel(const TI* __restrict__ x, int64_t ldx, TO* __r
   const int Ho = H / 2, Wo = W / 2;
   const int64_t total = (int64_t)B * Ho * Wo * C;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    // (Pool2x2Index, common.h, in its own text: all four instances are scheduled in another order with the helper)
     const int c = i % C;
     int64_t t = i / C;
     const int xo = t % Wo;
@@ -336,15 +302,14 @@ extern "C" int msam2_maxpool2x2(const void* x, int in_is_16bit, int64_t ldx, voi
   MSAM2_REQUIRE(x && y, "maxpool2x2: null tensor");
   MSAM2_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "maxpool2x2: H, W must be even");
   const int64_t total = B * (H / 2) * (W / 2) * C;
-  dim3 grid((unsigned)min((int64_t)8192, (total + 255) / 256)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define MP(TI, TO) \
-  hipLaunchKernelGGL((maxpool2x2_kernel<TI, TO>), grid, block, 0, s, (const TI*)x, ldx, (TO*)y, ldy, (int)B, (int)H, (int)W, (int)C)
-  if (in_is_16bit && out_is_16bit) MP(op16, op16);
-  else if (in_is_16bit) MP(op16, float);
-  else if (out_is_16bit) MP(float, op16);
-  else MP(float, float);
-#undef MP
+  with_type(in_is_16bit, [&](auto ti) {
+    with_type(out_is_16bit, [&](auto to) {
+      using TI = decltype(ti);
+      using TO = decltype(to);
+      hipLaunchKernelGGL((maxpool2x2_kernel<TI, TO>), dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, (const TI*)x, ldx, (TO*)y, ldy, (int)B,
+                         (int)H, (int)W, (int)C);
+    });
+  });
   return msam2_check_launch("maxpool2x2");
 }
 
@@ -382,12 +347,12 @@ extern "C" int msam2_upsample2x_add(void* y, const void* top, int64_t B, int64_t
   MSAM2_REQUIRE(y && top, "upsample2x_add: null tensor");
   MSAM2_REQUIRE(H % 2 == 0 && W % 2 == 0 && B > 0 && C > 0, "upsample2x_add: bad shape");
   const int64_t total = B * H * W * C;
-  if (C % 4 == 0 && total / 4 < (1ll << 31) && (((uintptr_t)y | (uintptr_t)top) & 15) == 0) {
-    hipLaunchKernelGGL(upsample2x_add4_kernel, dim3((unsigned)min((int64_t)16384, (total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  if (C % 4 == 0 && total / 4 < (1ll << 31) && vec_ok(4, 4, y, top)) {
+    hipLaunchKernelGGL(upsample2x_add4_kernel, dim3(grid1d(total / 4, 16384)), dim3(256), 0, (hipStream_t)stream,
                        (float*)y, (const float*)top, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)(C / 4));
     return msam2_check_launch("upsample2x_add");
   }
-  hipLaunchKernelGGL(upsample2x_add_kernel, dim3((unsigned)min((int64_t)8192, (total + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid1d(total, 8192)), dim3(256), 0,
                      (hipStream_t)stream, (float*)y, (const float*)top, (int)B, (int)H, (int)W, (int)C);
   return msam2_check_launch("upsample2x_add");
 }
@@ -445,7 +410,7 @@ extern "C" int msam2_rope_inplace(void* x, int64_t batch_stride, int64_t ld, int
   MSAM2_REQUIRE(D % 4 == 0 && ld % 2 == 0 && batch_stride % 2 == 0 && n_rope >= 0 && n_rope <= L && n_pos > 0, "rope: bad shape");
   if (n_rope == 0) return MSAM2_OK;
   const int64_t total = B * n_rope * (D / 2);
-  hipLaunchKernelGGL(rope_inplace_kernel, dim3((unsigned)min((int64_t)8192, (total + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(rope_inplace_kernel, dim3(grid1d(total, 8192)), dim3(256), 0,
                      (hipStream_t)stream, (op16*)x, batch_stride, ld, (int)B, (int)L, (int)n_rope, (int)n_pos, (int)D, cos_t, sin_t);
   return msam2_check_launch("rope_inplace");
 }
@@ -471,6 +436,7 @@ __global__ void bilinear_kernel(const float* __restrict__ x, float* __restrict__
     int64_t t = i / W;
     const int Y = t % H;
     const int pl = t / H;
+    // (BilinearTap, common.h, in its own text: the y and x taps are computed interleaved here, and the listing changes with the helper)
     float fy = fmaxf((Y + 0.5f) * sy - 0.5f, 0.f), fx = fmaxf((X + 0.5f) * sx - 0.5f, 0.f);
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
@@ -489,18 +455,18 @@ __global__ void bilinear4_kernel(const float* __restrict__ x, float* __restrict_
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const unsigned X4 = i % (unsigned)W4, t = i / (unsigned)W4;
     const unsigned Y = t % (unsigned)H, pl = t / (unsigned)H;
-    const float fy = fmaxf((Y + 0.5f) * sy - 0.5f, 0.f);
-    const int y0 = (int)fy, y1 = min(y0 + 1, h - 1);
-    const float ly = fy - y0;
+    const BilinearTap ty(Y, sy, h);
+    const int y0 = ty.i0, y1 = ty.i1;
+    const float ly = ty.l;
     const float* p0 = x + ((int64_t)pl * h + y0) * w;
     const float* p1 = x + ((int64_t)pl * h + y1) * w;
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int X = (int)X4 * 4 + e;
-      const float fx = fmaxf((X + 0.5f) * sx - 0.5f, 0.f);
-      const int x0 = (int)fx, x1 = min(x0 + 1, w - 1);
-      const float lx = fx - x0;
+      const BilinearTap tx(X, sx, w);
+      const int x0 = tx.i0, x1 = tx.i1;
+      const float lx = tx.l;
       o[e] = bilerp(p0[x0], p0[x1], p1[x0], p1[x1], lx, ly);
     }
     *reinterpret_cast<f32x4*>(y + ((int64_t)pl * H + Y) * W + X4 * 4) = o;
@@ -511,12 +477,12 @@ extern "C" int msam2_bilinear_upsample(const float* x, float* y, int64_t planes,
                                        void* stream) {
   MSAM2_REQUIRE(x && y && planes > 0 && h > 0 && w > 0 && H > 0 && W > 0, "bilinear: bad arguments");
   const int64_t total = planes * H * W;
-  if (W % 4 == 0 && ((uintptr_t)y & 15) == 0 && total / 4 < (1ll << 31)) {
-    hipLaunchKernelGGL(bilinear4_kernel, dim3((unsigned)min((int64_t)16384, (total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  if (W % 4 == 0 && vec_ok(4, 4, y) && total / 4 < (1ll << 31)) {
+    hipLaunchKernelGGL(bilinear4_kernel, dim3(grid1d(total / 4, 16384)), dim3(256), 0, (hipStream_t)stream,
                        x, y, (int)planes, (int)h, (int)w, (int)H, (int)W);
     return msam2_check_launch("bilinear_upsample");
   }
-  hipLaunchKernelGGL(bilinear_kernel, dim3((unsigned)min((int64_t)16384, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bilinear_kernel, dim3(grid1d(total, 16384)), dim3(256), 0, (hipStream_t)stream,
                      x, y, (int)planes, (int)h, (int)w, (int)H, (int)W);
   return msam2_check_launch("bilinear_upsample");
 }
@@ -570,9 +536,6 @@ extern "C" int msam2_fourier_pe_grid(float* out, const float* gauss, int64_t h, 
   hipLaunchKernelGGL(fourier_grid_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, out, gauss, (int)h, (int)w, (int)C);
   return msam2_check_launch("fourier_pe_grid");
 }
-
-__device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
 
 __global__ void hiera_pos_kernel(float* __restrict__ out, const float* __restrict__ bkg, const float* __restrict__ win, int C,
                                  int bh, int bw, int h, int w, int wsz) {
@@ -649,7 +612,7 @@ extern "C" int msam2_aa_downsample(const float* x, float* y, int64_t planes, int
                                    float in_bias, void* stream) {
   MSAM2_REQUIRE(x && y && planes > 0 && factor >= 1 && H % factor == 0 && W % factor == 0, "aa_downsample: bad arguments");
   const int64_t total = planes * (H / factor) * (W / factor);
-  hipLaunchKernelGGL(aa_downsample_kernel, dim3((unsigned)min((int64_t)8192, (total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
+  hipLaunchKernelGGL(aa_downsample_kernel, dim3(grid1d(total, 8192)), dim3(256), 0, (hipStream_t)stream, x,
                      y, (int)planes, (int)H, (int)W, (int)factor, in_scale, in_bias);
   return msam2_check_launch("aa_downsample");
 }
@@ -664,7 +627,7 @@ __global__ void gate_rows_kernel(float* __restrict__ x, const float* __restrict_
 
 extern "C" int msam2_gate_rows(float* x, const float* score, float value, int64_t B, int64_t row_len, void* stream) {
   MSAM2_REQUIRE(x && score && B > 0 && row_len > 0, "gate_rows: bad arguments");
-  hipLaunchKernelGGL(gate_rows_kernel, dim3((unsigned)min((int64_t)1024, (row_len + 255) / 256), (unsigned)B), dim3(256), 0,
+  hipLaunchKernelGGL(gate_rows_kernel, dim3(grid1d(row_len, 1024), (unsigned)B), dim3(256), 0,
                      (hipStream_t)stream, x, score, value, row_len);
   return msam2_check_launch("gate_rows");
 }
@@ -713,7 +676,7 @@ __global__ void image_prep_kernel(const uint8_t* __restrict__ img, float* __rest
 extern "C" int msam2_image_prep(const uint8_t* img_hwc, float* out_chw, int64_t H, int64_t W, int64_t S, const float* mean3,
                                 const float* std3, void* stream) {
   MSAM2_REQUIRE(img_hwc && out_chw && mean3 && std3 && H > 0 && W > 0 && S > 0, "image_prep: bad arguments (mean3/std3 are HOST pointers)");
-  hipLaunchKernelGGL(image_prep_kernel, dim3((unsigned)min((int64_t)8192, (3 * S * S + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(image_prep_kernel, dim3(grid1d(3 * S * S, 8192)), dim3(256), 0, (hipStream_t)stream,
                      img_hwc, out_chw, (int)H, (int)W, (int)S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
   return msam2_check_launch("image_prep");
 }
@@ -739,7 +702,7 @@ __global__ void non_overlap_kernel(const float* __restrict__ x, float* __restric
 
 extern "C" int msam2_non_overlap(const float* masks, float* out, int64_t n_obj, int64_t pixels, void* stream) {
   MSAM2_REQUIRE(masks && out && n_obj > 0 && pixels > 0, "non_overlap: bad arguments");
-  hipLaunchKernelGGL(non_overlap_kernel, dim3((unsigned)min((int64_t)8192, (pixels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, masks,
+  hipLaunchKernelGGL(non_overlap_kernel, dim3(grid1d(pixels, 8192)), dim3(256), 0, (hipStream_t)stream, masks,
                      out, (int)n_obj, pixels);
   return msam2_check_launch("non_overlap");
 }
@@ -789,7 +752,7 @@ extern "C" int msam2_seg_counts(const float* pred, const float* gt, const float*
                                 int64_t pixels, int* counts, void* stream) {
   MSAM2_REQUIRE(pred && gt && thresholds && counts, "seg_counts: null tensor");
   MSAM2_REQUIRE(n_thresholds >= 1 && n_thresholds <= 8 && planes > 0 && planes < 65536 && pixels > 0, "seg_counts: 1..8 thresholds per launch");
-  const unsigned gx = (unsigned)min((int64_t)64, (pixels + 255) / 256);
+  const unsigned gx = grid1d(pixels, 64);
   hipLaunchKernelGGL(seg_counts_kernel, dim3(gx, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, pred, gt, thresholds,
                      (int)n_thresholds, pixels, counts, (int)planes);
   return msam2_check_launch("seg_counts");

@@ -115,16 +115,18 @@ class LnbJob:
     """one msam2_layernorm_bwd call: ldx, ldd, ldo, lda all different from C and from each other (multiples of four unless `odd`); x_off /
     dy_off move a base by that many elements; ldo overrides the output stride"""
 
-    def __init__(self, ops, L, td, C, rows, with_add, *, odd=False, x_off=0, dy_off=0, ldo=None, seed=0):
+    def __init__(self, ops, L, td, C, rows, with_add, *, odd=False, x_off=0, dy_off=0, ldo=None, seed=0, ldx=None, ldd=None, lda=None, dx_left=0,
+                 add_off=0, gamma_off=0):
         self.L, self.td, self.C, self.rows = L, td, C, rows
-        self.what = f"layernorm_bwd dy={tn(td)} C={C} rows={rows} add={with_add} odd={odd} x_off={x_off} dy_off={dy_off} ldo={ldo}"
+        self.what = (f"layernorm_bwd dy={tn(td)} C={C} rows={rows} add={with_add} odd={odd} x_off={x_off} dy_off={dy_off} ldo={ldo} ldx={ldx} "
+                     f"ldd={ldd} lda={lda} dx_left={dx_left} add_off={add_off} gamma_off={gamma_off}")
         x, gamma, dy, add, self.g0, self.b0 = lnb_data(ops, rows, C, td, seed)
         p = (3, 5, 7, 9) if odd else (4, 8, 12, 16)
-        self.x = strided_nan(x, C + p[0], x_off)
-        self.dy = strided_nan(dy, C + p[1], dy_off)
-        self.gamma = nan_guarded(gamma)
-        self.add = strided_nan(add, C + p[3]) if with_add else None
-        self.dx = Canvas2(rows, C, F32, ldo if ldo is not None else C + p[2], 0)
+        self.x = strided_nan(x, ldx if ldx is not None else C + p[0], x_off)
+        self.dy = strided_nan(dy, ldd if ldd is not None else C + p[1], dy_off)
+        self.gamma = nan_guarded(gamma, gamma_off)
+        self.add = strided_nan(add, lda if lda is not None else C + p[3], add_off) if with_add else None
+        self.dx = Canvas2(rows, C, F32, ldo if ldo is not None else C + p[2], dx_left)
         self.dg, self.db = flat_with(self.g0), flat_with(self.b0)
 
     def launch(self):
@@ -167,6 +169,22 @@ def test_layernorm_bwd_vector(ops, L, td, ch):
     if td == 16:
         jobs.append(LnbJob(ops, L, td, LNB_VEC_C[ch][-1], 17, True, dy_off=4, seed=5))
     run_lnb(L, f"layernorm_bwd_vec_kernel<{tn(td)},{ch}>", jobs)
+
+
+@pytest.mark.parametrize("td", [32, 16])
+def test_layernorm_bwd_scalar_by_one_term_each(ops, L, td):
+    """rows = 17, every stride a multiple of four and every base aligned except ONE term of the vector test (the terms
+    test_layernorm_bwd_scalar does not flip on their own: its odd strides break ldx, ldd, ldo and lda together with C % 4 and C <= 384).
+    C = 128 (NI = 2): ldx, ldd, lda off by one; dx, dy, add, gamma one element off; an fp32 dy that is only 8-byte aligned (the dy test goes
+    by element size: a 16-bit dy there stays on the vector kernel, test_layernorm_bwd_vector).  C = 126: C % 4 alone.  C = 388 (NI = 8):
+    C <= 384 alone."""
+    rows = 17
+    one = [dict(ldx=133), dict(ldd=137), dict(lda=145), dict(dx_left=1), dict(dy_off=1), dict(add_off=1), dict(gamma_off=1)]
+    if td == 32:
+        one.append(dict(dy_off=2))
+    run_lnb(L, f"layernorm_bwd_kernel<{tn(td)},2>", [LnbJob(ops, L, td, 128, rows, True, seed=10 + i, **kw) for i, kw in enumerate(one)] +
+            [LnbJob(ops, L, td, 126, rows, True, ldx=132, ldd=136, ldo=140, lda=144, seed=20)])
+    run_lnb(L, f"layernorm_bwd_kernel<{tn(td)},8>", [LnbJob(ops, L, td, 388, rows, True, seed=21)])
 
 
 @pytest.mark.parametrize("td,rows", [(32, 4097), (16, 32769)])

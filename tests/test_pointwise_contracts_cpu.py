@@ -78,6 +78,41 @@ def test_refusals_of_the_backward_entries():
         assert what.split(":")[0] in msg, (what, msg)
 
 
+def test_alignment_refusals_of_the_remaining_entries():
+    """the alignment refusals of csrc/elementwise.hip, conv.hip and backward.hip that the two tests above do not reach: every call is valid
+    but for ONE pointer or stride, so the refusal is that term's.  The code must be MSAM2_ERR_ARG (-1): a call that got past its argument
+    checks fails too on a machine without a GPU, with MSAM2_ERR_LAUNCH (-2) and the entry's name in front of the launch error"""
+    from medical_sam2_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(4096)
+    ptr = (ctypes.addressof(buf) + 15) & ~15
+    dual = lambda x=ptr, ldx=8, w=ptr, b=ptr, y=ptr, ldy=8, y16=ptr, ldy16=8: L.msam2_layernorm_dual(x, ldx, w, b, y, ldy, y16, ldy16, 1, 8, 1e-6, None)
+    shared = lambda g=ptr, bias=ptr, skip=ptr, ln_w=ptr, ln_b=ptr, y=ptr, s16=1: L.msam2_convt2x2_shuffle_shared(g, bias, skip, s16, ln_w, ln_b, y, 1, 1, 1,
+                                                                                                                 32, 0, None)
+    tt = lambda A=ptr, lda=8, B=ptr, ldb=8: L.msam2_gemm_tt(A, lda, B, ldb, ptr, 8, None, 8, 8, 64, None)
+    cases = {
+        "layernorm_dual: x": lambda: dual(x=ptr + 8), "layernorm_dual: weight": lambda: dual(w=ptr + 4), "layernorm_dual: bias": lambda: dual(b=ptr + 8),
+        "layernorm_dual: y": lambda: dual(y=ptr + 4), "layernorm_dual: y16": lambda: dual(y16=ptr + 4), "layernorm_dual: y16 by one element": lambda: dual(y16=ptr + 2),
+        "layernorm_dual: ldx": lambda: dual(ldx=10), "layernorm_dual: ldy": lambda: dual(ldy=9), "layernorm_dual: ldy16": lambda: dual(ldy16=10),
+        "convt2x2_shuffle_shared: gemm_out": lambda: shared(g=ptr + 8), "convt2x2_shuffle_shared: bias": lambda: shared(bias=ptr + 4),
+        "convt2x2_shuffle_shared: skip": lambda: shared(skip=ptr + 8), "convt2x2_shuffle_shared: fp32 skip": lambda: shared(skip=ptr + 8, s16=0),
+        "convt2x2_shuffle_shared: ln_w": lambda: shared(ln_w=ptr + 8), "convt2x2_shuffle_shared: ln_b": lambda: shared(ln_b=ptr + 4),
+        "convt2x2_shuffle_shared: y": lambda: shared(y=ptr + 8),
+        "convt2x2_shuffle: fp32 skip, gemm_out": lambda: L.msam2_convt2x2_shuffle_f32skip(ptr + 8, ptr, ptr, ptr, ptr, ptr, 1, 1, 1, 32, None),
+        "convt2x2_shuffle: fp32 skip, skip": lambda: L.msam2_convt2x2_shuffle_f32skip(ptr, ptr, ptr + 8, ptr, ptr, ptr, 1, 1, 1, 32, None),
+        "patch_embed: img": lambda: L.msam2_patch_embed7x7s4(ptr + 4, ptr, ptr, None, ptr, 1, 128, 32, None),
+        "patch_embed: w_perm": lambda: L.msam2_patch_embed7x7s4(ptr, ptr + 8, ptr, None, ptr, 1, 128, 32, None),
+        "im2col_patch: out": lambda: L.msam2_im2col_patch7x7s4(ptr, ptr + 8, 1, 4, None),
+        "select_mask: masks": lambda: L.msam2_select_mask(ptr + 8, ptr, ptr, ptr, ptr, ptr, 1, 4, 1, 0, 1.0, 0.95, None),
+        "gemm_tt: A": lambda: tt(A=ptr + 8), "gemm_tt: B": lambda: tt(B=ptr + 2), "gemm_tt: lda": lambda: tt(lda=12), "gemm_tt: ldb": lambda: tt(ldb=12),
+    }
+    for what, call in cases.items():
+        rc = call()
+        msg = L.msam2_last_error().decode()
+        assert rc == -1, (what, rc, msg)
+        assert what.split(":")[0] in msg, (what, msg)
+
+
 def test_backward_wrappers_refuse_strided_and_wrong_typed_tensors():
     """backward.act_backward, layernorm_backward, dwconv7x7 and backward_encoder.maxpool2x2_backward hand raw pointers to the library (host
     tensors: nothing is launched)"""

@@ -95,10 +95,14 @@ def ln_data(ops, rows, C, ti, seed):
 
 
 class LnJob:
-    def __init__(self, ops, L, ti, to, C, rows, act, *, ldx=None, x_off=0, ycanvas=None, seed=0):
+    def __init__(self, ops, L, ti, to, C, rows, act, *, ldx=None, x_off=0, ycanvas=None, seed=0, w_off=0, b_off=0):
         self.ops, self.L, self.to, self.act, self.C, self.rows = ops, L, to, act, C, rows
-        self.what = f"layernorm {tn(ti)}->{tn(to)} C={C} rows={rows} act={act} ldx={ldx} x_off={x_off}"
+        self.what = f"layernorm {tn(ti)}->{tn(to)} C={C} rows={rows} act={act} ldx={ldx} x_off={x_off} w_off={w_off} b_off={b_off}"
         x, self.w, self.b = ln_data(ops, rows, C, ti, seed)
+        if w_off:
+            self.w = nan_guarded(self.w, w_off)
+        if b_off:
+            self.b = nan_guarded(self.b, b_off)
         self.x = strided_nan(x, ldx if ldx is not None else C + 4, x_off)
         self.cv = ycanvas if ycanvas is not None else Canvas(rows, C, dt(ops, to), aligned=True)
         self.ti = ti
@@ -150,6 +154,27 @@ def test_layernorm_scalar_paths(ops, L, ti, to):
     jobs.append(LnJob(ops, L, ti, to, 128, 33, 1, x_off=1))
     if to == 32:
         jobs.append(LnJob(ops, L, ti, to, 128, rows, 0, ycanvas=Canvas2(rows, 128, F32, 136, 2)))
+    reached(L, f"layernorm_scalar_kernel<{tn(ti)},{tn(to)}>", "layernorm_", [j.launch for j in jobs])
+    for j in jobs:
+        j.check()
+
+
+@pytest.mark.parametrize("ti,to", LN_TYPES)
+def test_layernorm_scalar_by_one_term_each(ops, L, ti, to):
+    """C = 128, rows = 17, and ONE term of msam2_layernorm's vector test false while every other holds (the terms test_layernorm_scalar_paths
+    does not flip on their own): ldy % 4 != 0 under an aligned y (the view starts 3 * 130 + 2 = 392 elements into its buffer); weight, then
+    bias, one float off; a 16-bit y one element off; an fp32 x that is only 8-byte aligned (the mask goes by element size on the x side too)"""
+    C, rows = 128, 17
+    jobs = [LnJob(ops, L, ti, to, C, rows, 1, ycanvas=Canvas2(rows, C, dt(ops, to), 130, 2), seed=1),
+            LnJob(ops, L, ti, to, C, rows, 0, w_off=1, seed=2), LnJob(ops, L, ti, to, C, rows, 1, b_off=1, seed=3)]
+    if to == 16:
+        jobs.append(LnJob(ops, L, ti, to, C, rows, 0, ycanvas=Canvas2(rows, C, dt(ops, to), 136, 1), seed=4))
+    if ti == 32:
+        jobs.append(LnJob(ops, L, ti, to, C, rows, 0, x_off=2, seed=5))
+    for j in jobs[:1]:
+        assert j.cv.view.data_ptr() % 16 == 0 and j.cv.view.stride(0) % 4 != 0
+    for j in jobs[1:3]:
+        assert (j.w.data_ptr() % 16 != 0) != (j.b.data_ptr() % 16 != 0) and j.x.data_ptr() % 16 == 0 and j.cv.view.data_ptr() % 16 == 0
     reached(L, f"layernorm_scalar_kernel<{tn(ti)},{tn(to)}>", "layernorm_", [j.launch for j in jobs])
     for j in jobs:
         j.check()
@@ -242,6 +267,32 @@ def test_add_cast_scalar(ops, L, ta, tb, to):
         ac_check(ops, jobs)
 
 
+def ac_strided(src, s0, s1, off):
+    """src [D0, D1, C] as a view with element strides (s0, s1, 1) inside a NaN-filled buffer, `off` elements into it"""
+    D0, D1, C = src.shape
+    buf = torch.full((off + D0 * s0 + D1 * s1 + C + 8,), float("nan"), dtype=src.dtype, device=DEV)
+    v = torch.as_strided(buf, (D0, D1, C), (s0, s1, 1), off)
+    v.copy_(src)
+    return v
+
+
+@pytest.mark.parametrize("ta,tb,to", AC_TYPES)
+def test_add_cast_scalar_by_one_term_each(ops, L, ta, tb, to):
+    """a [2, 3, 8] volume with strides (24, 8), and ONE term of msam2_add_cast's vector test false while every other holds (the terms
+    test_add_cast_scalar does not flip on their own: its 'pad5' layout breaks a_s0 and a_s1 together, b and out are always aligned):
+    a_s0 = 26; a_s1 = 9; out one element off; b_s0 = 26; b_s1 = 9; b one element off.  (total / 4 < 2^31 needs 2^33 elements: not flipped.)"""
+    D0, D1, C = 2, 3, 8
+    cases = [("a_s0", (26, 8, 0), (24, 8, 0), 0), ("a_s1", (28, 9, 0), (24, 8, 0), 0), ("out", (24, 8, 0), (24, 8, 0), 1),
+             ("b_s0", (24, 8, 0), (26, 8, 0), 0), ("b_s1", (24, 8, 0), (28, 9, 0), 0), ("b", (24, 8, 0), (24, 8, 1), 0)]
+    jobs = []
+    for i, (term, sa, sb, out_off) in enumerate(cases):
+        a = ac_strided(randn(D0, D1, C, seed=20 + i).to(dt(ops, ta)), *sa)
+        b = ac_strided(randn(D0, D1, C, seed=40 + i).to(dt(ops, tb)), *sb)
+        jobs.append((a, b, 0.75, Flat((D0, D1, C), dt(ops, to), offset=out_off), f"add_cast {tn(ta)},{tn(tb)}->{tn(to)} only {term} off"))
+    reached(L, f"add_cast_kernel<{tn(ta)},{tn(tb)},{tn(to)}>", "add_cast_", [lambda j=j: ac_launch(L, j[0], j[1], j[2], j[3].view, D0, D1, C, ops) for j in jobs])
+    ac_check(ops, jobs)
+
+
 @pytest.mark.parametrize("key,shape", [("add_cast_kernel<float,float,float>", (2, 1025, 1026)), ("add_cast_vec_kernel<float,float,float>", (4, 1025, 4100))])
 def test_add_cast_grid_stride_wraps(ops, L, key, shape):
     """more elements (groups of four) than the capped grid has threads; alpha = 1, so a + b is one fp32 addition: bit-exact"""
@@ -326,6 +377,18 @@ def test_upsample2x_add(ops, L, key, B, H, W, C, off):
     out.view.copy_(y0)
     reached(L, key, "upsample2x_add", [lambda: L.msam2_upsample2x_add(out.view.data_ptr(), top.data_ptr(), B, H, W, C, stream())])
     same_bits(out.view, up_ref(y0, top, B, H, W), f"upsample2x_add {B}x{H}x{W}x{C}")
+    assert out.sentinels_intact()
+
+
+def test_upsample2x_add_top_misaligned(ops, L):
+    """C % 4 == 0 and an aligned y, but top one float off its alignment: the one-element kernel (UP_CASES moves only y)"""
+    B, H, W, C = 2, 4, 6, 4
+    y0, top = randn(B, H, W, C, seed=1), nan_guarded(randn(B, H // 2, W // 2, C, seed=2), 1)
+    out = Flat((B, H, W, C), F32)
+    out.view.copy_(y0)
+    assert out.view.data_ptr() % 16 == 0 and top.data_ptr() % 16 == 4
+    reached(L, "upsample2x_add_kernel", "upsample2x_add", [lambda: L.msam2_upsample2x_add(out.view.data_ptr(), top.data_ptr(), B, H, W, C, stream())])
+    same_bits(out.view, up_ref(y0, top, B, H, W), "upsample2x_add with top off its alignment")
     assert out.sentinels_intact()
 
 

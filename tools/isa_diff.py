@@ -2,9 +2,11 @@
 `-S --cuda-device-only`, normalises the listings (comments, .file / .loc / .ident, debug sections and the per-translation-unit
 __hip_cuid_<hash> symbol dropped) and compares them line for line: every instruction, every .amdhsa_ field, the set of kernel symbols.
 A listing is kept beside its source (isa/ or isa_bf16/, ignored by git) and reused while no source or header is newer.
-Three verdicts per source file: `identical`; `operand order only` (same line counts, and the listings become equal once the two source
-operands of every instruction in COMMUTATIVE are put in one order -- the kernels it concerns are named); DIFFERS with the first
-differing kernel.  Exit status 0 iff no file DIFFERS.
+Four verdicts per source file: `identical`; `operand order only` (same line counts, and the listings become equal once the two source
+operands of every instruction in COMMUTATIVE are put in one order -- the kernels it concerns are named); `instance order only` (the
+sources in INSTANCE_ORDER: the compiler emitted the same kernels in another order -- every kernel body is equal once the function number
+in its .LBB<n>_<m> labels is dropped, and so is the text outside the bodies when it is compared per kernel symbol and not by position);
+DIFFERS with the first differing kernel.  Exit status 0 iff no file DIFFERS.
 usage: python tools/isa_diff.py <parent-tree> <new-tree> [--bf16]"""
 import os
 import re
@@ -20,6 +22,11 @@ CSRC = os.path.join("medical-sam2_amd", "csrc")
 # which moving code into a helper can change).  Extend only with such opcodes, and only as they show up.  Caveat:
 # v_mul_f32 of two NaNs propagates the payload of one source -- which one depends on the order.
 COMMUTATIVE = ("s_add_i32", "s_mul_i32", "v_mul_f32_e32")
+# Sources whose host dispatch instantiates its kernels from a template (common.h: with_type), which emits them in another order than the
+# if / else ladders did.  The order shows in two places only: the function number <n> of the local labels, and the position of a kernel's
+# sections, .set lines and metadata entry in the file.  Extend only with sources where that is the cause.
+INSTANCE_ORDER = ("backward.hip", "conv.hip", "elementwise.hip")
+FUNC_NUMBER_RE = re.compile(r"\.(LBB|Lfunc_end)\d+")
 COMMUTATIVE_RE = re.compile(r"^(\s*(?:%s)\s+[^,]+),\s*([^,]+),\s*([^,]+)$" % "|".join(COMMUTATIVE))
 
 
@@ -60,12 +67,41 @@ def canonical(line):
     return "%s, %s, %s" % ((m.group(1),) + tuple(sorted(m.group(2, 3)))) if m else line
 
 
-def compare(a, b):
+def by_symbol(text):
+    """(kernel bodies, text outside the bodies) of a normalised listing, function numbers dropped.  The outside text is cut into blocks at
+    every .section and at every kernel entry of the metadata; a block belongs to the first symbol it names (a list per symbol, in file
+    order), the blocks that name none keep their order under the key None."""
+    text = FUNC_NUMBER_RE.sub(r".\1", re.sub(r"^(_Z\w+):$", r"\1: ", text, flags=re.M))
+    bodies, outside, block, in_body = dict(kernels(text)), {}, [], False
+
+    def close():
+        if block:
+            m = re.search(r"_Z\w+", "\n".join(block))
+            outside.setdefault(m.group(0) if m else None, []).append(list(block))
+            block.clear()
+    for line in text.split("\n"):
+        if in_body:
+            in_body = not (line.startswith("\t.end_amdhsa_kernel") or line.startswith(".Lfunc_end"))   # (as isa_scan.kernels ends a body)
+        elif re.match(r"^_Z\w+:\s", line):
+            in_body = True
+        else:
+            if line.startswith(("\t.section", "  - .", "amdhsa.")):
+                close()
+            block.append(line)
+    close()
+    return bodies, outside
+
+
+def compare(a, b, src=""):
     if a == b:
         return "identical (%d lines)" % a.count("\n")
     ka, kb = (dict(kernels(re.sub(r"^(_Z\w+):$", r"\1: ", t, flags=re.M))) for t in (a, b))
     if set(ka) != set(kb):
         return "kernel symbols differ: only in parent %s, only in new %s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))
+    if src in INSTANCE_ORDER and by_symbol(a) == by_symbol(b):
+        moved = sum(x != y for x, y in zip(ka, kb))
+        return "instance order only (one of %s): %d of %d kernels emitted at another position, every body and every per-symbol block equal" % (
+            ", ".join(INSTANCE_ORDER), moved, len(ka))
     swapped = []
     for name in ka:
         if ka[name] != kb[name]:
@@ -90,7 +126,7 @@ def main():
         jobs = {(t, s): pool.submit(listing, t, s, bf16) for s in srcs for t in dict.fromkeys(args)}
         bad = 0
         for s in srcs:
-            verdict = compare(normalised(jobs[args[0], s].result()), normalised(jobs[args[1], s].result()))
+            verdict = compare(normalised(jobs[args[0], s].result()), normalised(jobs[args[1], s].result()), s)
             bad += verdict.startswith("DIFFERS") or verdict.startswith("kernel symbols differ")
             print("%-20s %s" % (s, verdict), flush=True)
     sys.exit(1 if bad else 0)
