@@ -14,6 +14,7 @@ c_i = ctypes.c_int
 c_l = ctypes.c_int64
 c_f = ctypes.c_float
 c_z = ctypes.c_size_t
+c_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/msam2_hip.h one to one (tests/test_abi.py checks both directions)
 SIGNATURES = {
@@ -131,6 +132,10 @@ SIGNATURES = {
     "msam2_label_clean_workspace_bytes": (c_z, [c_l]),
     "msam2_label_clean": (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, ctypes.c_uint32, c_p, c_p, c_p, c_z, c_l, c_l, c_l, c_p]),
     "msam2_label_overlap": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    "msam2_label_edt_workspace_bytes": (c_z, [c_l, c_l, c_l]),
+    "msam2_label_edt": (c_i, [c_p, c_l, c_l, c_l, c_i, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_z, c_p]),
+    "msam2_label_surface_distances_workspace_bytes": (c_z, [c_p, c_l]),
+    "msam2_label_surface_distances": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_d, c_d, c_d, c_p, c_l, c_p, c_p, c_z, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

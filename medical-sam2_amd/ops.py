@@ -1007,6 +1007,133 @@ def label_overlap(pred: torch.Tensor, gt: torch.Tensor, ids) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# after the overlap scores: exact distance transforms and surface distances of label volumes (csrc/surface.hip)
+EDT_FEATURES = {"surface": 0, "outside": 1}
+SURFACE_WORKSPACE_BYTES = 512 << 20    # an interface default, not a measured optimum
+
+
+def _spacing(what: str, spacing):
+    """(sz, sy, sx) as floats; each positive with a square that is a normal float64 and at most 2.6e297 (no product with a squared index
+    difference below 2^33 overflows, none flushes to 0): the range the library accepts"""
+    sp = tuple(float(s) for s in spacing)
+    _req(len(sp) == 3 and all(s > 0.0 and 2.2250738585072014e-308 <= s * s <= 1.7976931348623157e308 / 2.0 ** 36 for s in sp),
+         f"{what}: spacing must be three positive values (sz, sy, sx) with squares in 2.3e-308 .. 2.6e297, got {sp}")
+    return sp
+
+
+def label_edt(labels: torch.Tensor, value: int, spacing=(1.0, 1.0, 1.0), features: str = "surface", box=None) -> torch.Tensor:
+    """Exact squared Euclidean distance transform of one value of a uint8 [D, H, W] label volume (H, W >= 2) inside a box -> float64
+    [bd, bh, bw] on the device: d2 = min over the features f of ((sx^2 dx^2 + sy^2 dy^2) + sz^2 dz^2), every product and sum rounded on its
+    own -- the bits of the brute-force minimum (at unit spacing an exact integer), +inf when the box holds no feature.
+    features="surface": the voxels equal to `value` with a face neighbour that differs or lies outside the volume (6 neighbours; the 4 in
+    plane when D == 1); "outside": the voxels != value (the classic in-mask distance; beyond the volume there are no features).
+    box: host integers (z0, z1, y0, y1, x0, x1), inclusive, default the whole volume; features are taken from the box only.
+    Nothing is copied to the host."""
+    _, D, H, W, _ = _label_volume_args("label_edt", labels, None)
+    _req(H >= 2 and W >= 2, f"label_edt: H x W = {H} x {W} (at least 2 rows and columns)")
+    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_edt: {D * H * W} voxels (at most 2^31 - 2)")
+    _req(features in EDT_FEATURES, f"label_edt: features {features!r} (one of {tuple(EDT_FEATURES)})")
+    _req(0 <= int(value) <= 255, f"label_edt: value {value} (0 .. 255)")
+    sz, sy, sx = _spacing("label_edt", spacing)
+    bx = [0, D - 1, 0, H - 1, 0, W - 1] if box is None else [int(b) for b in box]
+    _req(len(bx) == 6 and 0 <= bx[0] <= bx[1] < D and 0 <= bx[2] <= bx[3] < H and 0 <= bx[4] <= bx[5] < W,
+         f"label_edt: box {bx} must be (z0, z1, y0, y1, x0, x1), inclusive, inside the {D} x {H} x {W} volume")
+    bd, bh, bw = bx[1] - bx[0] + 1, bx[3] - bx[2] + 1, bx[5] - bx[4] + 1
+    dev = labels.device
+    d2 = torch.empty(bd, bh, bw, dtype=torch.float64, device=dev)
+    nb = lib().msam2_label_edt_workspace_bytes(bd, bh, bw)
+    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().msam2_label_edt(_p(labels), D, H, W, int(value), EDT_FEATURES[features], (ctypes.c_int32 * 6)(*bx), sz, sy, sx, _p(d2), _p(ws), nb,
+                                _stream()))
+    return d2
+
+
+def _organ_extents(stats: "torch.Tensor"):
+    """label_stats' table on the host, int64 [D, n, 5] -> per organ (count, (z0, z1, y0, y1, x0, x1) or None)"""
+    D, n, _ = stats.shape
+    out = []
+    for j in range(n):
+        s = stats[:, j]
+        zs = (s[:, 0] > 0).nonzero()[0]
+        if len(zs) == 0:
+            out.append((0, None))
+            continue
+        p = s[zs]
+        out.append((int(p[:, 0].sum()), (int(zs[0]), int(zs[-1]), int(p[:, 1].min()), int(p[:, 2].max()), int(p[:, 3].min()), int(p[:, 4].max()))))
+    return out
+
+
+def label_surface_distances(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.0, 1.0), workspace_bytes: int = SURFACE_WORKSPACE_BYTES):
+    """`surface_segments` with offsets int64 [n, 2] and capacity int32 [n, 2] as device tensors beside dist and counts: everything on the
+    device (the two small tables go there in one asynchronous copy each)."""
+    dist, offs, caps, counts = surface_segments(pred, gt, ids, spacing, workspace_bytes)
+    n = len(offs)
+    dev = pred.device
+    return dist, torch.tensor(offs, dtype=torch.int64).reshape(n, 2).to(dev), torch.tensor(caps, dtype=torch.int32).reshape(n, 2).to(dev), counts
+
+
+def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.0, 1.0), workspace_bytes: int = SURFACE_WORKSPACE_BYTES):
+    """The squared surface distances behind HD95 / ASSD / NSD of two uint8 [D, H, W] label volumes (H, W >= 2) on the device ->
+    (dist float64 [total] (device), offsets [n][2] and capacity [n][2] (host lists: the caller slices with them), counts int32 [n, 2] (device)).
+    Segment (j, 0) = dist[offsets[j, 0]: offsets[j, 0] + counts[j, 0]] holds d2(q, surface of ids[j] in gt) for every voxel q on the surface of
+    ids[j] in pred, segment (j, 1) the other direction (`label_edt`'s definitions and bits); the order inside a segment is unspecified, the
+    rest of the segment up to its capacity (the organ's voxel count there) is +inf, so a sort of the whole segment puts the values first.
+    An organ absent from either volume stores nothing (capacity 0; the count of the side that has it is still reported).
+
+    The boxes and capacities come from two `label_stats` calls (z extent: the slices with count > 0; rows and columns: the stats' min / max;
+    box = the union over pred and gt; capacity = the summed count).  One device-to-host copy of those two small tables (with the ids) is the
+    only synchronisation on the way in; nothing else is copied to the host.
+    Organs are processed in groups whose workspace (20 bytes per box voxel) stays below `workspace_bytes`; an organ whose box alone needs more
+    raises with the needed size in the message."""
+    ids_d, D, H, W, n = _label_volume_args("label_surface_distances", pred, ids)
+    _req(H >= 2 and W >= 2, f"label_surface_distances: H x W = {H} x {W} (at least 2 rows and columns)")
+    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_surface_distances: {D * H * W} voxels (at most 2^31 - 2)")
+    _label_table("label_surface_distances", "gt", gt, pred, torch.uint8)
+    sz, sy, sx = _spacing("label_surface_distances", spacing)
+    dev = pred.device
+    sp, _ = label_stats(pred, ids_d)
+    sg, _ = label_stats(gt, ids_d)
+    host = torch.cat([sp.reshape(-1), sg.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")   # the one copy
+    m = D * n * 5
+    ext_p, ext_g = _organ_extents(host[:m].reshape(D, n, 5)), _organ_extents(host[m: 2 * m].reshape(D, n, 5))
+    values = host[2 * m:].tolist()
+    boxes, caps, offs, total = [], [], [], 0
+    for (cp, bp), (cg, bg) in zip(ext_p, ext_g):
+        both = bp is not None and bg is not None
+        one = bp or bg or (0, 0, 0, 0, 0, 0)
+        other = bg if both else one
+        boxes.append([min(one[0], other[0]), max(one[1], other[1]), min(one[2], other[2]), max(one[3], other[3]), min(one[4], other[4]),
+                      max(one[5], other[5])])
+        caps.append([cp if both else 0, cg if both else 0])
+        offs.append([total, total + caps[-1][0]])
+        total += sum(caps[-1])
+    dist = torch.full((max(total, 1),), float("inf"), dtype=torch.float64, device=dev)
+    counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    L = lib()
+    need = [L.msam2_label_surface_distances_workspace_bytes((ctypes.c_int32 * 6)(*b), 1) for b in boxes]
+    for j, nb in enumerate(need):
+        _req(nb <= workspace_bytes, f"label_surface_distances: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
+                                    f"workspace_bytes is {workspace_bytes}")
+    groups, cur, used = [], [], 0
+    for j, nb in enumerate(need):
+        if cur and used + nb > workspace_bytes:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(j)
+        used += nb
+    groups.append(cur)
+    ws = torch.empty((max(sum(need[j] for j in g) for g in groups) + 7) // 8, dtype=torch.int64, device=dev)
+    for g in groups:
+        k = len(g)
+        flat = lambda rows: [v for j in g for v in rows[j]]                                                 # noqa: E731
+        check(L.msam2_label_surface_distances(_p(pred), _p(gt), D, H, W, (ctypes.c_uint8 * k)(*[values[j] for j in g]),
+                                              (ctypes.c_int32 * (6 * k))(*flat(boxes)), (ctypes.c_int64 * (2 * k))(*flat(offs)),
+                                              (ctypes.c_int32 * (2 * k))(*flat(caps)), k, sz, sy, sx, _p(dist), dist.numel(),
+                                              counts[g[0]:].data_ptr(), _p(ws), ws.numel() * 8, _stream()))
+    return dist, offs, caps, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
 # arbitrary strides, read in place.
 BANK_MAX = 32          # physical slots the device tables are laid out for

@@ -145,3 +145,98 @@ def label_scores(pred: torch.Tensor, gt: torch.Tensor, obj_ids) -> dict:
     threshold left), with the path's one device-to-host copy inside it."""
     counts = ops.label_overlap(pred, gt, obj_ids)
     return volume_scores(counts[None])
+
+
+# ---- surface distances: HD95, ASSD, NSD (MONAI's conventions; DESIGN 7.12) ----------------------------------------------------------------
+def _sqrt_threshold(tau: float) -> float:
+    """the largest float64 t with sqrt(t) <= tau (correctly rounded sqrt, monotone): #{sqrt(d2) <= tau} = #{d2 <= t} without a device sqrt"""
+    tau = float(tau)
+    if not tau >= 0.0:
+        return -1.0                                                       # nothing is <= a negative (or NaN) tolerance
+    if np.isinf(tau):
+        return tau
+    t = np.float64(tau) * np.float64(tau)
+    while np.sqrt(t) > tau:
+        t = np.nextafter(t, -np.inf)
+    while np.sqrt(np.nextafter(t, np.inf)) <= tau:
+        t = np.nextafter(t, np.inf)
+    return float(t)
+
+
+def _direction_row(seg: torch.Tensor, m: torch.Tensor, q: float, thr2: torch.Tensor) -> torch.Tensor:
+    """seg: float64 [cap], ascending, its first m elements (m: 0-dim int64 tensor on seg's device) the squared distances of one direction
+    -> float64 [5 + K] = (largest d2, sum of the distances, the two neighbours of the percentile position, #{d2 <= thr2[k]}, m), torch ops
+    on seg's device only; an empty segment gives zeros and m"""
+    count = m.reshape(1).to(torch.float64)                               # exact: far below 2^53
+    if seg.numel() == 0:
+        return torch.cat([torch.zeros(4 + thr2.numel(), dtype=torch.float64, device=m.device), count])
+    d = torch.sqrt(seg)
+    valid = torch.arange(seg.numel(), device=seg.device) < m
+    last = torch.clamp(m - 1, min=0)
+    lo = torch.floor(last.to(torch.float64) * q).to(torch.int64)          # numpy's virtual index (m - 1) * (percentile / 100)
+    hi = torch.minimum(lo + 1, last)
+    total = torch.where(valid, d, torch.zeros_like(d)).sum()
+    below = (valid[:, None] & (seg[:, None] <= thr2[None, :])).sum(0).to(torch.float64)
+    return torch.cat([torch.stack([seg[last], total, d[lo], d[hi]]), below, count])
+
+
+def _scores(segments, percentile: float, tolerances) -> dict:
+    """segments: per organ ((seg, m), (seg, m)) as `_direction_row` takes them, all on one device -> the dict of `surface_scores`.  One
+    table [n, 2, 5 + K] crosses to the host: the only copy."""
+    q = float(percentile) / 100.0
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"surface scores: percentile {percentile} (0 .. 100)")
+    tol = [float(t) for t in tolerances]
+    K, n = len(tol), len(segments)
+    hd, hd95, assd, nsd = np.full(n, np.nan), np.full(n, np.nan), np.full(n, np.nan), np.full((n, K), np.nan)
+    counts = np.zeros((n, 2), dtype=np.int64)
+    if n:
+        dev = segments[0][0][1].device
+        thr2 = torch.tensor([_sqrt_threshold(t) for t in tol], dtype=torch.float64).to(dev)       # once per call
+        table = torch.stack([_direction_row(seg, m, q, thr2) for pair in segments for seg, m in pair])
+        rows = table.cpu().numpy().reshape(n, 2, 5 + K)
+        counts = rows[:, :, 4 + K].astype(np.int64)
+    for j in range(n):
+        mp, mg = int(counts[j, 0]), int(counts[j, 1])
+        if mp == 0 or mg == 0:
+            continue                                                      # absent from either volume: NaN
+        p95 = []
+        for d, m in ((0, mp), (1, mg)):
+            pos = (m - 1) * q
+            t = pos - np.floor(pos)
+            a, b = rows[j, d, 2], rows[j, d, 3]
+            p95.append(a + (b - a) * t if t < 0.5 else b - (b - a) * (1.0 - t))   # numpy's linear interpolation, both of its branches
+        hd[j] = np.sqrt(max(rows[j, 0, 0], rows[j, 1, 0]))
+        hd95[j] = max(p95)
+        assd[j] = (rows[j, 0, 1] + rows[j, 1, 1]) / (mp + mg)
+        nsd[j] = (rows[j, 0, 4: 4 + K] + rows[j, 1, 4: 4 + K]) / (mp + mg)
+    return {"hd": hd, "hd95": hd95, "assd": assd, "nsd": nsd, "surface_voxels": counts}
+
+
+def surface_scores_from_distances(lists, percentile: float = 95.0, tolerances=(1.0,)) -> dict:
+    """The scores from sorted squared-distance lists: lists[j] = (d2 of pred's surface voxels to gt's surface, d2 of gt's to pred's), each a
+    1-D ascending float64 sequence (tensor, array or list; empty where the organ is absent).  Per organ, with d = sqrt(d2):
+    hd = the largest d of both lists; hd95 = the larger of the two lists' `percentile` (numpy's default linear percentile);
+    assd = (sum d_pg + sum d_gp) / (|S_p| + |S_g|); nsd [n, K] = (#{d_pg <= tau} + #{d_gp <= tau}) / (|S_p| + |S_g|) per tolerance;
+    surface_voxels int64 [n, 2] = (|S_p|, |S_g|).  All four are NaN when either list is empty.  float64 numpy arrays."""
+    segments = []
+    for pair in lists:
+        if len(pair) != 2:
+            raise ValueError("surface scores: one (pred -> gt, gt -> pred) pair of lists per organ")
+        ts = [(x.to(torch.float64) if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, dtype=np.float64))).reshape(-1) for x in pair]
+        segments.append([(t, torch.tensor(t.numel(), device=t.device)) for t in ts])
+    return _scores(segments, percentile, tolerances)
+
+
+@torch.no_grad()
+def surface_scores(pred: torch.Tensor, gt: torch.Tensor, obj_ids, spacing=(1.0, 1.0, 1.0), percentile: float = 95.0, tolerances=(1.0,),
+                   workspace_bytes: int = ops.SURFACE_WORKSPACE_BYTES) -> dict:
+    """HD, HD95, ASSD and NSD per organ of a label volume against the ground truth, both uint8 [T, H, W] on the device, spacing (sz, sy, sx)
+    in millimetres: `ops.surface_segments` (exact squared distances of every surface voxel to the other surface), then sorting, sqrt,
+    sums, the percentile gather and the tolerance counts as torch ops on the device; one small table [n, 2, 5 + K], the surface counts in
+    it, crosses to the host at the end.  Keys and conventions: `surface_scores_from_distances`."""
+    dist, offs, caps, counts = ops.surface_segments(pred, gt, obj_ids, spacing, workspace_bytes)
+    counts64 = counts.to(torch.int64)
+    segments = [[(torch.sort(dist[offs[j][d]: offs[j][d] + caps[j][d]]).values, counts64[j, d]) for d in range(2)]   # +inf beyond the count sorts last
+                for j in range(len(offs))]
+    return _scores(segments, percentile, tolerances)
