@@ -136,6 +136,10 @@ SIGNATURES = {
     "msam2_label_edt": (c_i, [c_p, c_l, c_l, c_l, c_i, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_z, c_p]),
     "msam2_label_surface_distances_workspace_bytes": (c_z, [c_p, c_l]),
     "msam2_label_surface_distances": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_d, c_d, c_d, c_p, c_l, c_p, c_p, c_z, c_p]),
+    "msam2_volume_prep_workspace_bytes": (c_z, [c_l, c_l, c_l, c_l]),
+    "msam2_volume_prep": (c_i, [c_p, c_i, c_l, c_l, c_l, c_l, c_l, ctypes.POINTER(c_d), c_p, c_p, c_l, c_p, c_p, c_l, ctypes.POINTER(c_f),
+                                ctypes.POINTER(c_f), c_p, c_p, c_p, c_z, c_p]),
+    "msam2_label_resize": (c_i, [c_p, c_i, c_l, c_l, c_l, c_l, c_p, c_p, ctypes.POINTER(ctypes.c_uint32), c_p, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

@@ -927,6 +927,100 @@ def label_pick(labels: torch.Tensor, ids, stats: torch.Tensor, rows: torch.Tenso
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# in front of both: volume intake -- window, Pillow-exact resize, normalise; nearest resize of label maps (csrc/volume_prep.hip)
+PREP_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.float32: 2}
+LABEL_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
+
+
+def _int32_table(what: str, t: Optional[torch.Tensor], shape, dev) -> None:
+    _req(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev,
+         f"{what} must be int32 contiguous {list(shape)} on the source's device")
+
+
+def volume_prep_workspace_bytes(T: int, H0: int, W0: int, size: int) -> int:
+    """bytes of the uint8 workspace volume_prep needs for T slices of H0 x W0 -> size: 0 when the call takes the fused form"""
+    return int(lib().msam2_volume_prep_workspace_bytes(int(T), int(H0), int(W0), int(size)))
+
+
+def volume_prep(src: torch.Tensor, size: int, tables_x, tables_y, windows=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                out=True, grey=False, workspace: Optional[torch.Tensor] = None):
+    """Raw slice stack [T, Cin, H0, W0] (Cin 1 or 3; uint8, int16 or float32, contiguous, on the GPU) -> (out fp32 [T, 3, size, size] | None,
+    grey uint8 [T, 3, size, size] | None): channel c = plane c % Cin through window c (windows: three (lo, hi) pairs, needed for int16 /
+    float32), Pillow's 8-bit bicubic resize byte for byte, then ((float)g / 255 - mean) / std in fp32.  tables_x / tables_y: (coefficients
+    int32 [size, ksize], bounds int32 [size, 2]) device tensors of volume_prep.resample_tables for W0 -> size / H0 -> size, None when that
+    dimension is already `size`.  out / grey: True allocates, a tensor is filled in place, False skips it.  workspace: uint8 tensor of
+    volume_prep_workspace_bytes (allocated when needed and not given).  No host sync."""
+    _req(isinstance(src, torch.Tensor) and src.dtype in PREP_SOURCE_TYPES and src.dim() == 4 and src.is_contiguous() and src.is_cuda,
+         "volume_prep: src must be a uint8 / int16 / float32 contiguous [T, Cin, H0, W0] tensor on the GPU")
+    T, Cin, H0, W0 = src.shape
+    S, dev = int(size), src.device
+    _req(Cin in (1, 3), f"volume_prep: Cin = {Cin} (1 or 3)")
+    _req(1 <= T <= LABEL_MAX_SLICES and 1 <= H0 <= LABEL_MAX_SIDE and 1 <= W0 <= LABEL_MAX_SIDE and 1 <= S <= LABEL_MAX_SIDE,
+         f"volume_prep: sizes {T} x {H0} x {W0} -> {S} (1 .. {LABEL_MAX_SLICES} slices, sides 1 .. {LABEL_MAX_SIDE})")
+    tabs = []
+    for what, n, tab in (("tables_x", W0, tables_x), ("tables_y", H0, tables_y)):
+        if n == S:
+            _req(tab is None, f"volume_prep: {what} must be None, that pass is skipped ({n} -> {S})")
+            tabs += [None, None, 0]
+            continue
+        _req(tab is not None and len(tab) == 2 and isinstance(tab[0], torch.Tensor) and tab[0].dim() == 2, f"volume_prep: {what} = (coefficients, bounds)")
+        ks = tab[0].shape[1]
+        _int32_table(f"volume_prep: {what}[0]", tab[0], (S, ks), dev)
+        _int32_table(f"volume_prep: {what}[1]", tab[1], (S, 2), dev)
+        tabs += [tab[0], tab[1], ks]
+    win = None
+    if src.dtype != torch.uint8:
+        _req(windows is not None and len(windows) == 3 and all(len(w) == 2 for w in windows), "volume_prep: int16 / float32 sources need three (lo, hi) windows")
+        win = (ctypes.c_double * 6)(*[float(v) for w in windows for v in w])
+    res = []
+    for what, t, dt in (("out", out, F32), ("grey", grey, torch.uint8)):
+        if isinstance(t, torch.Tensor):
+            _req(t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (T, 3, S, S) and t.device == dev,
+                 f"volume_prep: {what} must be {dt} contiguous [{T}, 3, {S}, {S}] on the source's device")
+            res.append(t)
+        else:
+            res.append(torch.empty(T, 3, S, S, dtype=dt, device=dev) if t else None)
+    _req(res[0] is not None or res[1] is not None, "volume_prep: at least one of out and grey")
+    nb = volume_prep_workspace_bytes(T, H0, W0, S)
+    if nb and workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    if workspace is not None:
+        _req(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev, "volume_prep: workspace must be a uint8 tensor on the source's device")
+    m, s = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    check(lib().msam2_volume_prep(_p(src), PREP_SOURCE_TYPES[src.dtype], T, Cin, H0, W0, S, win, _p(tabs[0]), _p(tabs[1]), tabs[2], _p(tabs[3]),
+                                  _p(tabs[4]), tabs[5], m, s, _p(res[1]), _p(res[0]), _p(workspace),
+                                  0 if workspace is None else workspace.numel(), _stream()))
+    return res[0], res[1]
+
+
+def label_resize(src: torch.Tensor, size: int, ymap: torch.Tensor, xmap: torch.Tensor, obj_ids=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Label map [T, H0, W0] (uint8 / int16 / int32 / int64, contiguous, on the GPU) -> uint8 [T, size, size] label volume: a nearest
+    gather through ymap / xmap (int32 [size] device tensors of volume_prep.nearest_map); a value is kept if it is 1 .. 255 and, with
+    obj_ids given (host integers 1 .. 255), one of them; every other voxel is 0."""
+    _req(isinstance(src, torch.Tensor) and src.dtype in LABEL_SOURCE_TYPES and src.dim() == 3 and src.is_contiguous() and src.is_cuda,
+         "label_resize: src must be a uint8 / int16 / int32 / int64 contiguous [T, H0, W0] tensor on the GPU")
+    T, H0, W0 = src.shape
+    S, dev = int(size), src.device
+    _req(1 <= T <= LABEL_MAX_SLICES and 1 <= H0 <= LABEL_MAX_SIDE and 1 <= W0 <= LABEL_MAX_SIDE and 1 <= S <= LABEL_MAX_SIDE,
+         f"label_resize: sizes {T} x {H0} x {W0} -> {S} (1 .. {LABEL_MAX_SLICES} slices, sides 1 .. {LABEL_MAX_SIDE})")
+    _int32_table("label_resize: ymap", ymap, (S,), dev)
+    _int32_table("label_resize: xmap", xmap, (S,), dev)
+    keep = None
+    if obj_ids is not None:
+        vals = [int(v) for v in (obj_ids.tolist() if isinstance(obj_ids, torch.Tensor) else obj_ids)]
+        _req(all(1 <= v <= 255 for v in vals), "label_resize: obj_ids must be integers in 1 .. 255 (0 is the background)")
+        keep = (ctypes.c_uint32 * 8)()
+        for v in vals:
+            keep[v >> 5] |= 1 << (v & 31)
+    if out is None:
+        out = torch.empty(T, S, S, dtype=torch.uint8, device=dev)
+    _req(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (T, S, S) and out.device == dev,
+         f"label_resize: out must be uint8 contiguous [{T}, {S}, {S}] on the source's device")
+    check(lib().msam2_label_resize(_p(src), LABEL_SOURCE_TYPES[src.dtype], T, H0, W0, S, _p(ymap), _p(xmap), keep, _p(out), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # between the two: connected components, island removal and overlap counts of label volumes (csrc/components.hip)
 LABEL_CONNECTIVITIES = (4, 8, 6, 18, 26)
 LABEL_MAX_VOXELS = 2 ** 31 - 2

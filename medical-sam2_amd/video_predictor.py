@@ -137,6 +137,17 @@ class SAM2VideoPredictor(SAM2Base):
         images = load_video_frames_from_data(imgs_tensor, offload_video_to_cpu, async_loading_frames)
         return self._new_state(images, video_height, video_width, offload_video_to_cpu, offload_state_to_cpu)
 
+    @torch.no_grad()
+    def init_state_from_volume(self, raw, window=None, video_height=None, video_width=None, offload_state_to_cpu=False, **prepare_args):
+        """State from a raw slice stack ([T, H0, W0] or [T, Cin, H0, W0]; uint8, int16 or float32; window: see volume_prep.prepare_volume):
+        windowed, resized as Pillow does and normalised on the device, where the frames stay.  video_height / video_width default to the
+        model's input size, as in val_init_state: masks then come out on the grid of volume_prep.prepare_labels."""
+        from .volume_prep import prepare_volume
+        if video_height is None or video_width is None:
+            video_height = video_width = self.image_size
+        images = prepare_volume(raw, window, size=self.image_size, **prepare_args)
+        return self._new_state(images, video_height, video_width, False, offload_state_to_cpu)
+
     def _obj_id_to_idx(self, inference_state, obj_id):
         obj_idx = inference_state["obj_id_to_idx"].get(obj_id, None)
         if obj_idx is not None:
