@@ -23,17 +23,6 @@ __device__ __forceinline__ float bilerp_at(const float* __restrict__ p, int h, i
   return v;
 }
 
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 constexpr int STATS_THREADS = 256, STATS_PPT = 8;           // 2048 crop pixels per workgroup
 
 // Per mask: count(v > thr_hi), count(v > thr_lo), count(v > thr) and the inclusive box of v > thr over the (h, w) crop frame.
@@ -72,10 +61,10 @@ __global__ __launch_bounds__(STATS_THREADS) void mask_stats_kernel(const float* 
       ymax = max(ymax, Y);
     }
   }
-  xmin = wave_min_i(xmin);
-  ymin = wave_min_i(ymin);
-  xmax = wave_max_i(xmax);
-  ymax = wave_max_i(ymax);
+  xmin = wave_min(xmin);
+  ymin = wave_min(ymin);
+  xmax = wave_max(xmax);
+  ymax = wave_max(ymax);
   __shared__ int red[STATS_THREADS / 64][7];
   if (lane == 0) {
     red[wv][0] = c_hi;
@@ -308,6 +297,7 @@ __global__ __launch_bounds__(256) void nms_sweep_kernel(const unsigned long long
       }
       const unsigned long long valid = n == 64 ? ~0ull : ((1ull << n) - 1ull);
       const unsigned long long kept = ~cur & valid;
+      // (lanes_below spelled out: with the call this kernel's listing gains a line)
       if ((kept >> lane) & 1ull) keep[nk + __popcll(kept & ((1ull << lane) - 1ull))] = order[a];
       nk += __popcll(kept);
       if (lane == 0) kept_s = kept;
@@ -353,7 +343,7 @@ extern "C" int msam2_mask_stats(const float* logits, int64_t M, int64_t lh, int6
   if (hipMemsetAsync(counts, 0, (size_t)M * 3 * sizeof(int), s) != hipSuccess || hipMemsetAsync(workspace, 0, (size_t)M * 4 * sizeof(int), s) != hipSuccess)
     return msam2_check_launch("mask_stats (memset)");
   const int64_t per = STATS_THREADS * STATS_PPT;
-  hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)((h * w + per - 1) / per), (unsigned)M), dim3(STATS_THREADS), 0, s, logits, (int)lh,
+  hipLaunchKernelGGL(mask_stats_kernel, dim3(cdiv(h * w, per), (unsigned)M), dim3(STATS_THREADS), 0, s, logits, (int)lh,
                      (int)lw, (int)h, (int)w, thr, thr_hi, thr_lo, counts, (int*)workspace);
   hipLaunchKernelGGL(mask_box_finalize_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, (const int*)counts, (const int*)workspace, boxes, (int)M,
                      (int)h, (int)w);
@@ -379,7 +369,7 @@ extern "C" int msam2_mask_rle_runs(const float* logits, int64_t M, int64_t lh, i
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(runs, 0, (size_t)M * sizeof(int), s) != hipSuccess) return msam2_check_launch("mask_rle_runs (memset)");
   const int64_t total = H * W, per = RUNS_THREADS * RUNS_PPT;
-  hipLaunchKernelGGL(rle_runs_kernel, dim3((unsigned)((total + per - 1) / per), (unsigned)M), dim3(RUNS_THREADS), 0, s, logits, (int)lh, (int)lw,
+  hipLaunchKernelGGL(rle_runs_kernel, dim3(cdiv(total, per), (unsigned)M), dim3(RUNS_THREADS), 0, s, logits, (int)lh, (int)lw,
                      (int)h, (int)w, (int)x0, (int)y0, (int)H, total, thr, runs);
   return msam2_check_launch("mask_rle_runs");
 }
@@ -397,7 +387,7 @@ extern "C" int msam2_mask_rle(const float* logits, int64_t M, int64_t lh, int64_
 
 extern "C" size_t msam2_box_nms_workspace_bytes(int64_t K) {
   if (K <= 0) return 0;
-  const int64_t nw = (K + 63) / 64;
+  const int64_t nw = (K + 63) / 64;                         // (64-bit: this entry takes any K)
   return nms_ws_order_bytes(K) + (size_t)(K * nw) * sizeof(unsigned long long);
 }
 
@@ -414,7 +404,7 @@ extern "C" int msam2_box_nms(const float* boxes, const float* scores, int64_t K,
   MSAM2_REQUIRE(boxes && scores && keep && workspace, "box_nms: null tensor");
   MSAM2_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "box_nms: boxes and workspace must be 16-byte aligned");
   MSAM2_REQUIRE(workspace_bytes >= msam2_box_nms_workspace_bytes(K), "box_nms: workspace too small");
-  const int nw = (int)((K + 63) / 64);
+  const int nw = cdiv(K, 64);
   int* order = (int*)workspace;
   unsigned long long* mask = (unsigned long long*)((char*)workspace + nms_ws_order_bytes(K));
   hipLaunchKernelGGL(nms_rank_kernel, dim3(cdiv(K, 256)), dim3(256), 0, s, scores, (int)K, order);

@@ -21,12 +21,6 @@ struct BankOperand {
   int64_t rs, os, is;                 // element strides: row, outer, inner (the inner one is 1 on the vector paths)
 };
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---- bank_dots ------------------------------------------------------------------------------------------------------------------------
 // Out[r][c] = sum_i X[r][i] Y[c][i], xx[r] = sum_i X[r][i]^2, yy[c] = sum_i Y[c][i]^2 in one pass over the operands.
 // The K = n_outer * n_inner elements are cut into groups of V consecutive inner elements (V = 4: one global_load_dwordx4 per row and
@@ -115,11 +109,11 @@ __global__ __launch_bounds__(DOTS_THREADS) void bank_dots_kernel(BankOperand X, 
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         if (c < Cn) {
-          const float s = wave_sum_f(acc[r][c]);
+          const float s = wave_sum(acc[r][c]);
           if (lane == 0) red[wv][r * CT + c] = s;
         }
       }
-      const float s = wave_sum_f(xx[r]);
+      const float s = wave_sum(xx[r]);
       if (lane == 0) red[wv][DOTS_RT * CT + r] = s;
     }
   }
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(DOTS_THREADS) void bank_dots_kernel(BankOperand X, 
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       if (c < Cn) {
-        const float s = wave_sum_f(yy[c]);
+        const float s = wave_sum(yy[c]);
         if (lane == 0) red[wv][DOTS_RT * CT + DOTS_RT + c] = s;
       }
     }
@@ -156,7 +150,7 @@ __global__ __launch_bounds__(64) void bank_dots_reduce_kernel(const float* __res
   const int o = blockIdx.x;
   float s = 0.f;
   for (int p = threadIdx.x; p < P; p += 64) s += ws[(int64_t)p * NV + o];
-  s = wave_sum_f(s);
+  s = wave_sum(s);
   if (threadIdx.x != 0) return;
   if (o < R * Cn)
     dots[o] = s;
@@ -174,7 +168,7 @@ DotsPlan dots_plan(int64_t K, int V) {
   DotsPlan d;
   d.V = V;
   d.G = K / V;
-  const int64_t blocks = (d.G + DOTS_THREADS - 1) / DOTS_THREADS;
+  const int64_t blocks = (d.G + DOTS_THREADS - 1) / DOTS_THREADS;   // (64-bit: msam2_bank_dots_chain takes any K)
   const int64_t p0 = blocks < DOTS_MAX_WG ? blocks : DOTS_MAX_WG;
   d.its = (int)((blocks + p0 - 1) / p0);
   d.P = (int)((blocks + d.its - 1) / d.its);
@@ -414,7 +408,7 @@ bool strides_ok(const int64_t* st) { return st && st[0] >= 0 && st[1] >= 0 && st
 extern "C" int msam2_bank_dots_chain(int64_t K, int vec) {
   if (K <= 0 || (vec != 1 && vec != 4) || K % vec) return -1;
   const DotsPlan d = dots_plan(K, vec);
-  return d.its * vec + 6 + 3 + ((d.P + 63) / 64 - 1) + 6;
+  return d.its * vec + 6 + 3 + (cdiv(d.P, 64) - 1) + 6;
 }
 
 extern "C" size_t msam2_bank_dots_workspace_bytes(int64_t R, int64_t Cn) {
@@ -460,7 +454,7 @@ extern "C" int msam2_bank_dots(const float* x, const int64_t* x_strides, int64_t
   const int gi = (int)((fast == 1 ? n_ch : n_px) / V);
   const int NV = (int)(R * Cn + R + Cn);
   const int CT = Cn <= 8 ? 8 : Cn <= 16 ? 16 : Cn <= 24 ? 24 : 32;
-  const dim3 grid((unsigned)d.P, (unsigned)((R + DOTS_RT - 1) / DOTS_RT));
+  const dim3 grid((unsigned)d.P, (unsigned)cdiv(R, DOTS_RT));
   hipStream_t s = (hipStream_t)stream;
   if (V == 4)
     dots_launch<4>(CT, grid, s, mk(x, x_strides), mk(pa, sa), mk(pb, sb), (int)R, (int)rows_a, (int)Cn, d.G, gi, d.its, (float*)workspace, NV);
@@ -492,7 +486,7 @@ extern "C" int msam2_bank_gather(const float* feats, const float* pos, const int
   MSAM2_REQUIRE(feats && pos && order && indices && memory && memory_pos, "bank_gather: null tensor");
   MSAM2_REQUIRE((((uintptr_t)feats | (uintptr_t)pos | (uintptr_t)memory | (uintptr_t)memory_pos) & 15) == 0, "bank_gather: tensors must be 16-byte aligned");
   const int64_t total = S * HW * B * (C / 4);
-  hipLaunchKernelGGL(bank_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)feats,
+  hipLaunchKernelGGL(bank_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)feats,
                      (const float4*)pos, HW * C / 4, order, indices, (int)B, (int)S, (int)HW, (int)(C / 4), (int)N, (int)cap, (float4*)memory,
                      (float4*)memory_pos);
   return msam2_check_launch("bank_gather");

@@ -11,34 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ int uf_find(const int* parent, int n) {
-  int p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != n) {
-    n = p;
-    p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return n;
-}
-
-__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
-  bool done;
-  do {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a < b) {
-      const int old = atomicMin(parent + b, a);
-      done = (old == b);
-      b = old;
-    } else if (b < a) {
-      const int old = atomicMin(parent + a, b);
-      done = (old == a);
-      a = old;
-    } else {
-      done = true;
-    }
-  } while (!done);
-}
-
 __global__ void cc_init_kernel(int* __restrict__ parent, int W, int H) {
   const int col = (blockIdx.x * blockDim.x + threadIdx.x) * 2, row = (blockIdx.y * blockDim.y + threadIdx.y) * 2;
   if (row < H && col < W) {
@@ -142,7 +114,7 @@ extern "C" int msam2_cc_label(const uint8_t* img, int32_t* labels, int32_t* coun
   hipStream_t s = (hipStream_t)stream;
   int* parent = (int*)workspace;
   int* hist = parent + N * H * W;
-  hipLaunchKernelGGL(cc_zero_kernel, dim3((unsigned)min((int64_t)2048, cdiv(N * H * W, (int64_t)256))), dim3(256), 0, s, hist, N * H * W);
+  hipLaunchKernelGGL(cc_zero_kernel, dim3(grid1d(N * H * W, 2048)), dim3(256), 0, s, hist, N * H * W);
   dim3 blk(32, 8), grid(cdiv(W / 2, 32), cdiv(H / 2, 8), (unsigned)N);
   hipLaunchKernelGGL(cc_init_kernel, grid, blk, 0, s, parent, (int)W, (int)H);
   hipLaunchKernelGGL(cc_merge_kernel, grid, blk, 0, s, img, parent, (int)W, (int)H);
@@ -173,10 +145,10 @@ extern "C" int msam2_fill_components(float* mask, int64_t N, int64_t H, int64_t 
   int* counts = labels + n;
   int* ccws = counts + n;
   uint8_t* bin = (uint8_t*)(ccws + 2 * n);
-  hipLaunchKernelGGL(threshold_kernel, dim3((unsigned)min((int64_t)4096, (n + 255) / 256)), dim3(256), 0, s, mask, bin, n, threshold, above);
+  hipLaunchKernelGGL(threshold_kernel, dim3(grid1d(n, 4096)), dim3(256), 0, s, mask, bin, n, threshold, above);
   const int rc = msam2_cc_label(bin, labels, counts, N, H, W, ccws, sizeof(int) * 2 * n, stream);
   if (rc != MSAM2_OK) return rc;
-  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)min((int64_t)4096, (n + 255) / 256)), dim3(256), 0, s, mask, labels, counts, max_area, n,
+  hipLaunchKernelGGL(fill_kernel, dim3(grid1d(n, 4096)), dim3(256), 0, s, mask, labels, counts, max_area, n,
                      fill_value);
   return msam2_check_launch("fill_components");
 }

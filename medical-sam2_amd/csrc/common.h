@@ -417,3 +417,99 @@ static inline bool vec_ok1(const void* p, int64_t n, int64_t s) { return (uintpt
 static inline bool vec_ok1(int64_t ld, int64_t n, int64_t s) { return (ld * s) % (n * s) == 0; }
 template <typename... A>
 static inline bool vec_ok(int n, int s, A... a) { return (vec_ok1(a, n, s) && ...); }
+
+// ---- building blocks of the label-volume and mask post-processing kernels (amg.hip, bank.hip, cc.hip, volume_labels.hip, prompts.hip,
+// components.hip, surface.hip, volume_prep.hip): one definition each ----
+
+// integer siblings of wave_max: the result in all 64 lanes
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Lock-free union-find over int parents in global memory (cc.hip, components.hip).  A parent only ever points to a lower index, so a
+// find follows strictly decreasing indices and ends whatever other threads do; a union lowers the larger root with atomicMin and goes
+// on from the value it found there when somebody lowered that parent first.  No thread waits for another.
+__device__ __forceinline__ int uf_find(const int* parent, int n) {
+  int p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (p != n) {                                          // p < n: strictly decreasing
+    n = p;
+    p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return n;
+}
+__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
+  bool done;
+  do {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a < b) {
+      const int old = atomicMin(parent + b, a);
+      done = (old == b);                                    // else somebody lowered parent[b] first: go on from there
+      b = old;
+    } else if (b < a) {
+      const int old = atomicMin(parent + a, b);
+      done = (old == a);
+      a = old;
+    } else {
+      done = true;
+    }
+  } while (!done);
+}
+
+// number of set bits of ballot m below this lane: the lane's rank among the lanes that voted
+__device__ __forceinline__ int lanes_below(unsigned long long m, int lane) { return __popcll(m & ((1ull << lane) - 1ull)); }
+
+// length of the run that starts at this lane, from the ballot of run heads: it ends where the next one starts, or with the wave
+__device__ __forceinline__ int run_length(unsigned long long heads, int lane) {
+  const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
+  return rest ? __ffsll((long long)rest) : 64 - lane;
+}
+
+// The 256-entry LDS table label value -> index in ids[0 .. n), -1 = not listed, filled by a workgroup of 256 threads (tid = threadIdx.x).
+// The first barrier also ends whatever the caller initialised in LDS before the call; the table may be read after the second.
+// (label_stats_kernel of prompts.hip spells the same four lines out: its listing changes with the call.)
+__device__ __forceinline__ void ids_to_object_table(signed char* lut, const uint8_t* ids, int n, int tid) {
+  lut[tid] = -1;
+  __syncthreads();
+  if (tid < n) lut[ids[tid]] = (signed char)tid;
+  __syncthreads();
+}
+
+// One wave's (|P & G|, |P|, |G|) added to the workgroup's LDS counters c[0 .. 3), by one lane; a zero costs no LDS access.  A macro: as a
+// function it changes the register allocation of label_slices_kernel<1, true>.
+// ci, cp and cg are each evaluated twice: pass values or expressions without side effects.
+#define LABEL_OVERLAP_ADD(c, ci, cp, cg)  \
+  do {                                    \
+    if (ci) atomicAdd((c) + 0, ci);       \
+    if (cp) atomicAdd((c) + 1, cp);       \
+    if (cg) atomicAdd((c) + 2, cg);       \
+  } while (0)
+
+// Host side of those entries.  The limits of a label volume [D, H, W] and of the objects of one call (ops.py mirrors them by name):
+constexpr int LABEL_MAX_OBJ = 32;                           // per-object tables live in LDS and in kernel arguments
+constexpr int LABEL_MAX_SLICES = 65535;                     // slices ride in gridDim.y / gridDim.z
+constexpr int LABEL_MAX_SIDE = 8192;                        // rows and columns (a row distance fits uint16 with 0xFFFF to spare)
+constexpr int64_t LABEL_MAX_VOXELS = (1ll << 31) - 2;       // entries that hold a voxel index (+ 1) in an int32
+constexpr int64_t LABEL_NO_VOXEL_CAP = INT64_MAX;           // entries that address voxels with 64-bit offsets
+// Every entry states its own contract at the call site: the smallest H and W it takes (2 where a voxel needs an in-plane neighbour) and
+// its voxel cap, LABEL_MAX_VOXELS or LABEL_NO_VOXEL_CAP (65535 x 8192 x 8192 < 2^63: the product cannot overflow behind the side tests).
+static inline bool label_sizes_ok(int64_t D, int64_t H, int64_t W, int64_t min_side, int64_t max_voxels) {
+  return D >= 1 && D <= LABEL_MAX_SLICES && H >= min_side && H <= LABEL_MAX_SIDE && W >= min_side && W <= LABEL_MAX_SIDE &&
+         D * H * W <= max_voxels;
+}
+// The two refusals those entries share.  entry: a string literal; min_side: the literal 1 or 2 (it is printed); voxel_clause: "" or what
+// the message says about the cap.
+#define LABEL_REQUIRE_OBJECTS(entry, n) \
+  MSAM2_REQUIRE((n) >= 1 && (n) <= LABEL_MAX_OBJ, entry ": n = %lld objects (1 .. %d per call)", (long long)(n), LABEL_MAX_OBJ)
+#define LABEL_REQUIRE_SIZES(entry, D, H, W, min_side, max_voxels, voxel_clause)                                                             \
+  MSAM2_REQUIRE(label_sizes_ok(D, H, W, min_side, max_voxels),                                                                              \
+                entry ": bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of " #min_side " .. %d" voxel_clause ")", (long long)(D), LABEL_MAX_SLICES, \
+                (long long)(H), (long long)(W), LABEL_MAX_SIDE)
+#define LABEL_AT_MOST_2G_VOXELS ", at most 2^31 - 2 voxels"

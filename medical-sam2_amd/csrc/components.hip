@@ -33,37 +33,6 @@
 namespace {
 
 constexpr int CMP_THREADS = 256, CMP_ITER = 4;              // a workgroup owns CMP_ITER x 256 consecutive voxels, a wave 64 at a time
-constexpr int CMP_MAX_OBJ = 32;
-constexpr int CMP_MAX_D = 65535, CMP_MAX_HW = 8192;
-constexpr int64_t CMP_MAX_VOXELS = (1ll << 31) - 2;
-
-__device__ __forceinline__ int cmp_find(const int* parent, int n) {
-  int p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  while (p != n) {                                          // p < n: strictly decreasing
-    n = p;
-    p = __hip_atomic_load(parent + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return n;
-}
-
-__device__ __forceinline__ void cmp_union(int* parent, int a, int b) {
-  bool done;
-  do {
-    a = cmp_find(parent, a);
-    b = cmp_find(parent, b);
-    if (a < b) {
-      const int old = atomicMin(parent + b, a);
-      done = (old == b);                                    // else somebody lowered parent[b] first: go on from there
-      b = old;
-    } else if (b < a) {
-      const int old = atomicMin(parent + a, b);
-      done = (old == a);
-      a = old;
-    } else {
-      done = true;
-    }
-  } while (!done);
-}
 
 // voxel of this lane in round `it`: consecutive lanes hold consecutive voxels, a wave's 64 never straddle two rounds
 __device__ __forceinline__ int64_t cmp_voxel(int it) { return ((int64_t)blockIdx.x * CMP_ITER + it) * CMP_THREADS + threadIdx.x; }
@@ -116,7 +85,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_merge_kernel(const uint8_t* _
     int pb = __shfl_up(b, 1);
     if (lane == 0) pb = (live && col > 0) ? labels[i - 1] : 0;
     const bool left_same = col > 0 && b != 0 && pb == b;    // the voxel to the left belongs to the same run
-    if (lane == 0 && left_same) cmp_union(parent, i, i - 1);   // the run was cut at this wave's first lane
+    if (lane == 0 && left_same) uf_union(parent, i, i - 1);    // the run was cut at this wave's first lane
     // the neighbour rows' bytes first, by all lanes (wave-uniform control flow around the shuffles), the unions afterwards
     int ni[4], M[4], L[4], R[4];
 #pragma unroll
@@ -137,13 +106,13 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_merge_kernel(const uint8_t* _
       if (rows.wide[k]) {
         // M is of the neighbour run that also holds L / R when they match; the leftmost voxel of this run that sees it joins them
         if (M[k] == b) {
-          if (!left_same) cmp_union(parent, i, ni[k]);
+          if (!left_same) uf_union(parent, i, ni[k]);
         } else {
-          if (R[k] == b) cmp_union(parent, i, ni[k] + 1);   // a neighbour run that starts at col + 1: nobody further left sees it
-          if (L[k] == b && !left_same) cmp_union(parent, i, ni[k] - 1);
+          if (R[k] == b) uf_union(parent, i, ni[k] + 1);    // a neighbour run that starts at col + 1: nobody further left sees it
+          if (L[k] == b && !left_same) uf_union(parent, i, ni[k] - 1);
         }
       } else if (M[k] == b && !(left_same && L[k] == b)) {
-        cmp_union(parent, i, ni[k]);
+        uf_union(parent, i, ni[k]);
       }
     }
   }
@@ -175,7 +144,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_flatten_kernel(const uint8_t*
     unsigned long long heads;
     const int first = cmp_run_first(b, i % W, lane, &heads);
     const bool walks = b != 0 && first == lane;
-    const int root = walks ? cmp_find(parent, i) + 1 : 0;
+    const int root = walks ? uf_find(parent, i) + 1 : 0;
     const int y = __shfl(root, first);                      // a background voxel is its own run: 0
     if (live) comp[i] = y;
     const int lead = __ffsll((long long)__ballot(walks)) - 1;   // the first foreground run of the wave (there is one)
@@ -185,8 +154,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_flatten_kernel(const uint8_t*
       slot_name[it * (CMP_THREADS / 64) + wave] = y0;
       slot_count[it * (CMP_THREADS / 64) + wave] = count0;
     } else if (walks && y != y0) {
-      const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-      atomicAdd(size + y - 1, rest ? __ffsll((long long)rest) : 64 - lane);   // the run ends where the next one starts
+      atomicAdd(size + y - 1, run_length(heads, lane));
     }
   }
   __syncthreads();
@@ -205,8 +173,8 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_flatten_kernel(const uint8_t*
 
 // ---- island removal -------------------------------------------------------------------------------------------------------------------
 struct CleanTables {                                        // the workspace of msam2_label_clean; LDS partials have the same form
-  unsigned long long best[CMP_MAX_OBJ];                     // size << 32 | 0x7fffffff - canonical index of the largest component
-  int found[CMP_MAX_OBJ], found_vox[CMP_MAX_OBJ], kept[CMP_MAX_OBJ], kept_vox[CMP_MAX_OBJ];
+  unsigned long long best[LABEL_MAX_OBJ];                   // size << 32 | 0x7fffffff - canonical index of the largest component
+  int found[LABEL_MAX_OBJ], found_vox[LABEL_MAX_OBJ], kept[LABEL_MAX_OBJ], kept_vox[LABEL_MAX_OBJ];
 };
 
 __device__ __forceinline__ unsigned long long clean_key(int size, int index) {
@@ -218,24 +186,17 @@ __global__ void cmp_zero_kernel(int* __restrict__ x, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] = 0;
 }
 
-__device__ __forceinline__ void clean_lut(signed char* lut, const uint8_t* ids, int n) {
-  lut[threadIdx.x] = -1;                                    // CMP_THREADS == 256
-  __syncthreads();
-  if ((int)threadIdx.x < n) lut[ids[threadIdx.x]] = (signed char)threadIdx.x;
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(CMP_THREADS) void clean_find_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ size,
                                                                  const uint8_t* __restrict__ ids, int n, CleanTables* __restrict__ t,
                                                                  int64_t N) {
   __shared__ CleanTables s;
   __shared__ signed char lut[256];
   const int tid = threadIdx.x;
-  if (tid < CMP_MAX_OBJ) {
+  if (tid < LABEL_MAX_OBJ) {
     s.best[tid] = 0ull;
     s.found[tid] = s.found_vox[tid] = 0;
   }
-  clean_lut(lut, ids, n);
+  ids_to_object_table(lut, ids, n, tid);                     // CMP_THREADS == 256
 #pragma unroll 1
   for (int it = 0; it < CMP_ITER; ++it) {
     const int64_t gi = cmp_voxel(it);
@@ -261,16 +222,16 @@ __global__ __launch_bounds__(CMP_THREADS) void clean_apply_kernel(const uint8_t*
                                                                   const int* __restrict__ size, const uint8_t* __restrict__ ids, int n,
                                                                   const int* __restrict__ min_voxels, unsigned largest_mask, uint8_t* out,
                                                                   CleanTables* __restrict__ t, int64_t N) {
-  __shared__ int kept[CMP_MAX_OBJ], kept_vox[CMP_MAX_OBJ], need[CMP_MAX_OBJ];
-  __shared__ unsigned long long best[CMP_MAX_OBJ];
+  __shared__ int kept[LABEL_MAX_OBJ], kept_vox[LABEL_MAX_OBJ], need[LABEL_MAX_OBJ];
+  __shared__ unsigned long long best[LABEL_MAX_OBJ];
   __shared__ signed char lut[256];
   const int tid = threadIdx.x;
-  if (tid < CMP_MAX_OBJ) {
+  if (tid < LABEL_MAX_OBJ) {
     kept[tid] = kept_vox[tid] = 0;
     need[tid] = tid < n ? max(1, min_voxels ? min_voxels[tid] : 0) : 1;
     best[tid] = tid < n ? t->best[tid] : 0ull;              // final: written by the launch before this one
   }
-  clean_lut(lut, ids, n);
+  ids_to_object_table(lut, ids, n, tid);                     // CMP_THREADS == 256
 #pragma unroll 1
   for (int it = 0; it < CMP_ITER; ++it) {
     const int64_t gi = cmp_voxel(it);
@@ -315,10 +276,10 @@ __global__ void clean_info_kernel(const CleanTables* __restrict__ t, int n, int*
 // blockIdx.y = slice; a workgroup owns CMP_ITER x 256 voxels of it
 __global__ __launch_bounds__(CMP_THREADS) void overlap_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt,
                                                               const uint8_t* __restrict__ ids, int n, int HW, int* __restrict__ counts) {
-  __shared__ int cnt[CMP_MAX_OBJ * 3];
-  __shared__ int id[CMP_MAX_OBJ];
+  __shared__ int cnt[LABEL_MAX_OBJ * 3];
+  __shared__ int id[LABEL_MAX_OBJ];
   const int tid = threadIdx.x, lane = tid & 63;
-  if (tid < CMP_MAX_OBJ * 3) cnt[tid] = 0;
+  if (tid < LABEL_MAX_OBJ * 3) cnt[tid] = 0;
   if (tid < n) id[tid] = ids[tid];
   __syncthreads();
   const int64_t slice = (int64_t)blockIdx.y * HW;
@@ -330,28 +291,17 @@ __global__ __launch_bounds__(CMP_THREADS) void overlap_kernel(const uint8_t* __r
     if (__ballot((p | g) != 0) == 0ull) continue;
     for (int j = 0; j < n; ++j) {
       const unsigned long long mp = __ballot(p == id[j]), mg = __ballot(g == id[j]);
-      if (lane == 0 && (mp | mg)) {
-        const int ci = __popcll(mp & mg), cp = __popcll(mp), cg = __popcll(mg);
-        if (ci) atomicAdd(&cnt[j * 3 + 0], ci);
-        if (cp) atomicAdd(&cnt[j * 3 + 1], cp);
-        if (cg) atomicAdd(&cnt[j * 3 + 2], cg);
-      }
+      if (lane == 0 && (mp | mg)) LABEL_OVERLAP_ADD(cnt + j * 3, __popcll(mp & mg), __popcll(mp), __popcll(mg));
     }
   }
   __syncthreads();
   if (tid < n * 3 && cnt[tid]) atomicAdd(counts + (int64_t)blockIdx.y * n * 3 + tid, cnt[tid]);
 }
 
-bool cmp_sizes_ok(int64_t D, int64_t H, int64_t W) {
-  return D >= 1 && D <= CMP_MAX_D && H >= 1 && H <= CMP_MAX_HW && W >= 1 && W <= CMP_MAX_HW && D * H * W <= CMP_MAX_VOXELS;
-}
-
-unsigned cmp_blocks(int64_t N) { return (unsigned)((N + CMP_THREADS * CMP_ITER - 1) / (CMP_THREADS * CMP_ITER)); }
-
 }  // namespace
 
 extern "C" size_t msam2_label_components_workspace_bytes(int64_t D, int64_t H, int64_t W) {
-  if (!cmp_sizes_ok(D, H, W)) return 0;
+  if (!label_sizes_ok(D, H, W, 1, LABEL_MAX_VOXELS)) return 0;
   return (size_t)(D * H * W) * sizeof(int);
 }
 
@@ -360,8 +310,7 @@ extern "C" int msam2_label_components(const uint8_t* labels, int64_t D, int64_t 
   MSAM2_REQUIRE(labels && comp && size && workspace, "label_components: null labels / comp / size / workspace");
   MSAM2_REQUIRE(connectivity == 4 || connectivity == 8 || connectivity == 6 || connectivity == 18 || connectivity == 26,
                 "label_components: connectivity %d (6, 18 or 26 in 3-D; 4 or 8 slice by slice)", connectivity);
-  MSAM2_REQUIRE(cmp_sizes_ok(D, H, W), "label_components: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 1 .. %d, at most 2^31 - 2 voxels)",
-                (long long)D, CMP_MAX_D, (long long)H, (long long)W, CMP_MAX_HW);
+  LABEL_REQUIRE_SIZES("label_components", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(workspace_bytes >= msam2_label_components_workspace_bytes(D, H, W), "label_components: workspace too small (%zu of %zu bytes)",
                 workspace_bytes, msam2_label_components_workspace_bytes(D, H, W));
   MSAM2_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)comp & 3) == 0 && ((uintptr_t)size & 3) == 0,
@@ -385,23 +334,21 @@ extern "C" int msam2_label_components(const uint8_t* labels, int64_t D, int64_t 
   hipStream_t s = (hipStream_t)stream;
   const int64_t N = D * H * W;
   int* parent = (int*)workspace;
-  const dim3 grid(cmp_blocks(N)), blk(CMP_THREADS);
+  const dim3 grid(cdiv(N, CMP_THREADS * CMP_ITER)), blk(CMP_THREADS);
   hipLaunchKernelGGL(cmp_runs_kernel, grid, blk, 0, s, labels, parent, size, (int)W, N);
   hipLaunchKernelGGL(cmp_merge_kernel, grid, blk, 0, s, labels, parent, (int)H, (int)W, N, rows);
-  hipLaunchKernelGGL(cmp_flatten_kernel, dim3((unsigned)((N + CMP_THREADS * FLAT_ITER - 1) / (CMP_THREADS * FLAT_ITER))), blk, 0, s, labels, parent, comp,
-                     size, (int)W, N);
+  hipLaunchKernelGGL(cmp_flatten_kernel, dim3(cdiv(N, CMP_THREADS * FLAT_ITER)), blk, 0, s, labels, parent, comp, size, (int)W, N);
   return msam2_check_launch("label_components");
 }
 
-extern "C" size_t msam2_label_clean_workspace_bytes(int64_t n) { return n >= 1 && n <= CMP_MAX_OBJ ? sizeof(CleanTables) : 0; }
+extern "C" size_t msam2_label_clean_workspace_bytes(int64_t n) { return n >= 1 && n <= LABEL_MAX_OBJ ? sizeof(CleanTables) : 0; }
 
 extern "C" int msam2_label_clean(const uint8_t* labels, const int32_t* comp, const int32_t* size, const uint8_t* ids, int64_t n,
                                  const int32_t* min_voxels, uint32_t largest_mask, uint8_t* out, int32_t* info, void* workspace,
                                  size_t workspace_bytes, int64_t D, int64_t H, int64_t W, void* stream) {
   MSAM2_REQUIRE(labels && comp && size && ids && out && info && workspace, "label_clean: null labels / comp / size / ids / out / info / workspace");
-  MSAM2_REQUIRE(n >= 1 && n <= CMP_MAX_OBJ, "label_clean: n = %lld objects (1 .. %d per call)", (long long)n, CMP_MAX_OBJ);
-  MSAM2_REQUIRE(cmp_sizes_ok(D, H, W), "label_clean: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 1 .. %d, at most 2^31 - 2 voxels)",
-                (long long)D, CMP_MAX_D, (long long)H, (long long)W, CMP_MAX_HW);
+  LABEL_REQUIRE_OBJECTS("label_clean", n);
+  LABEL_REQUIRE_SIZES("label_clean", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(workspace_bytes >= msam2_label_clean_workspace_bytes(n), "label_clean: workspace too small (%zu of %zu bytes)", workspace_bytes,
                 msam2_label_clean_workspace_bytes(n));
   MSAM2_REQUIRE(((uintptr_t)workspace & 7) == 0, "label_clean: workspace must be 8-byte aligned");
@@ -409,23 +356,21 @@ extern "C" int msam2_label_clean(const uint8_t* labels, const int32_t* comp, con
   const int64_t N = D * H * W;
   CleanTables* t = (CleanTables*)workspace;
   hipLaunchKernelGGL(cmp_zero_kernel, dim3(1), dim3(CMP_THREADS), 0, s, (int*)workspace, (int64_t)(sizeof(CleanTables) / sizeof(int)));
-  const dim3 grid(cmp_blocks(N)), blk(CMP_THREADS);
+  const dim3 grid(cdiv(N, CMP_THREADS * CMP_ITER)), blk(CMP_THREADS);
   hipLaunchKernelGGL(clean_find_kernel, grid, blk, 0, s, labels, size, ids, (int)n, t, N);
   hipLaunchKernelGGL(clean_apply_kernel, grid, blk, 0, s, labels, comp, size, ids, (int)n, min_voxels, (unsigned)largest_mask, out, t, N);
-  hipLaunchKernelGGL(clean_info_kernel, dim3(1), dim3(CMP_MAX_OBJ), 0, s, t, (int)n, info);
+  hipLaunchKernelGGL(clean_info_kernel, dim3(1), dim3(LABEL_MAX_OBJ), 0, s, t, (int)n, info);
   return msam2_check_launch("label_clean");
 }
 
 extern "C" int msam2_label_overlap(const uint8_t* pred, const uint8_t* gt, const uint8_t* ids, int64_t D, int64_t H, int64_t W, int64_t n,
                                    int32_t* counts, void* stream) {
   MSAM2_REQUIRE(pred && gt && ids && counts, "label_overlap: null pred / gt / ids / counts");
-  MSAM2_REQUIRE(n >= 1 && n <= CMP_MAX_OBJ, "label_overlap: n = %lld objects (1 .. %d per call)", (long long)n, CMP_MAX_OBJ);
-  MSAM2_REQUIRE(cmp_sizes_ok(D, H, W), "label_overlap: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 1 .. %d, at most 2^31 - 2 voxels)",
-                (long long)D, CMP_MAX_D, (long long)H, (long long)W, CMP_MAX_HW);
+  LABEL_REQUIRE_OBJECTS("label_overlap", n);
+  LABEL_REQUIRE_SIZES("label_overlap", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   hipStream_t s = (hipStream_t)stream;
   const int64_t total = D * n * 3;
-  hipLaunchKernelGGL(cmp_zero_kernel, dim3((unsigned)min((int64_t)1024, (total + CMP_THREADS - 1) / CMP_THREADS)), dim3(CMP_THREADS), 0, s, counts,
-                     total);
-  hipLaunchKernelGGL(overlap_kernel, dim3(cmp_blocks(H * W), (unsigned)D), dim3(CMP_THREADS), 0, s, pred, gt, ids, (int)n, (int)(H * W), counts);
+  hipLaunchKernelGGL(cmp_zero_kernel, dim3(grid1d(total, 1024, CMP_THREADS)), dim3(CMP_THREADS), 0, s, counts, total);
+  hipLaunchKernelGGL(overlap_kernel, dim3(cdiv(H * W, CMP_THREADS * CMP_ITER), (unsigned)D), dim3(CMP_THREADS), 0, s, pred, gt, ids, (int)n, (int)(H * W), counts);
   return msam2_check_launch("label_overlap");
 }

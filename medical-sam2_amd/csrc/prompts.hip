@@ -27,14 +27,12 @@
 namespace {
 
 constexpr int STAT_THREADS = 256;
-constexpr int STAT_MAX_OBJ = 32;
-constexpr int STAT_ROWS = 64;            // most rows of a band (LDS: STAT_MAX_OBJ x STAT_ROWS row counts)
+constexpr int STAT_ROWS = 64;            // most rows of a band (LDS: LABEL_MAX_OBJ x STAT_ROWS row counts)
 constexpr int STAT_BAND_BYTES = 16384;   // a band is the fewest whole rows that reach this, at most STAT_ROWS
-constexpr int STAT_MAX_D = 65535, STAT_MAX_HW = 8192;
 
 struct BandTables {                      // LDS of one workgroup
-  int rowcnt[STAT_MAX_OBJ * STAT_ROWS];  // [object][row of the band]
-  int c0[STAT_MAX_OBJ], c1[STAT_MAX_OBJ], r0[STAT_MAX_OBJ], r1[STAT_MAX_OBJ], cnt[STAT_MAX_OBJ];
+  int rowcnt[LABEL_MAX_OBJ * STAT_ROWS]; // [object][row of the band]
+  int c0[LABEL_MAX_OBJ], c1[LABEL_MAX_OBJ], r0[LABEL_MAX_OBJ], r1[LABEL_MAX_OBJ], cnt[LABEL_MAX_OBJ];
   signed char lut[256];                  // label value -> object index, -1 = ignored
 };
 
@@ -70,14 +68,14 @@ __global__ __launch_bounds__(STAT_THREADS) void label_stats_kernel(const uint8_t
   __shared__ BandTables t;
   const int tid = threadIdx.x, lane = tid & 63, d = blockIdx.y;
   const int y0 = blockIdx.x * band_rows, nrows = min(band_rows, H - y0);
-  for (int i = tid; i < STAT_MAX_OBJ * STAT_ROWS; i += STAT_THREADS) t.rowcnt[i] = 0;
-  if (tid < STAT_MAX_OBJ) {
+  for (int i = tid; i < LABEL_MAX_OBJ * STAT_ROWS; i += STAT_THREADS) t.rowcnt[i] = 0;
+  if (tid < LABEL_MAX_OBJ) {
     t.c0[tid] = t.r0[tid] = INT_MAX;
     t.c1[tid] = t.r1[tid] = -1;
     t.cnt[tid] = 0;
   }
-  t.lut[tid] = -1;                                          // STAT_THREADS == 256
-  __syncthreads();
+  t.lut[tid] = -1;                                          // STAT_THREADS == 256.  (ids_to_object_table spelled out: with the call
+  __syncthreads();                                          //  this kernel's listing comes out three lines shorter)
   if (tid < n) t.lut[ids[tid]] = (signed char)tid;
   __syncthreads();
 
@@ -107,9 +105,7 @@ __global__ __launch_bounds__(STAT_THREADS) void label_stats_kernel(const uint8_t
     const unsigned long long heads = __ballot(lane == 0 || key < 0 || key != prev);
     if (plain) {
       if ((heads >> lane) & 1) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int m = rest ? __ffsll((long long)rest) : 64 - lane;
-        add_run(t, t.lut[first], row, col, m << 4);
+        add_run(t, t.lut[first], row, col, run_length(heads, lane) << 4);
       }
     } else if (live) {
       const unsigned long long lo = v.x | ((unsigned long long)v.y << 32), hi = v.z | ((unsigned long long)v.w << 32);
@@ -156,8 +152,8 @@ __device__ __forceinline__ int block_scan(int v, int* wsum, int* total) {
   }
   if (lane == 63) wsum[wave] = s;
   __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
+  int before = 0, all = 0;                                  // (spelled out here and in label_pick_kernel's column scan: with one shared
+#pragma unroll                                              //  function for both, label_pick_kernel's listing comes out three lines shorter)
   for (int w = 0; w < 4; ++w) {
     const int x = wsum[w];
     before += w < wave ? x : 0;
@@ -216,14 +212,14 @@ __global__ __launch_bounds__(STAT_THREADS) void label_pick_kernel(const uint8_t*
         const unsigned long long m = __ballot(hit);
         if (lane == 0) wsum[wave] = __popcll(m);
         __syncthreads();
-        int before = 0, all = 0;
+        int before = 0, all = 0;                            // (block_scan's four-wave sums: see there)
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
           const int s = wsum[w];
           before += w < wave ? s : 0;
           all += s;
         }
-        const int rank = seen + before + __popcll(m & ((1ull << lane) - 1ull));
+        const int rank = seen + before + lanes_below(m, lane);
         if (hit && rank == kr) {
           res[0] = x;
           res[1] = row;
@@ -241,24 +237,19 @@ __global__ __launch_bounds__(STAT_THREADS) void label_pick_kernel(const uint8_t*
   }
 }
 
-bool sizes_ok(int64_t D, int64_t H, int64_t W) {
-  return D >= 1 && D <= STAT_MAX_D && H >= 1 && H <= STAT_MAX_HW && W >= 1 && W <= STAT_MAX_HW;
-}
-
 }  // namespace
 
 extern "C" int msam2_label_stats(const uint8_t* labels, const uint8_t* ids, int64_t D, int64_t H, int64_t W, int64_t n, int* stats, int* rows,
                                  void* stream) {
   MSAM2_REQUIRE(labels && ids && stats && rows, "label_stats: null labels / ids / stats / rows");
-  MSAM2_REQUIRE(n >= 1 && n <= STAT_MAX_OBJ, "label_stats: n = %lld objects (1 .. %d per call)", (long long)n, STAT_MAX_OBJ);
-  MSAM2_REQUIRE(sizes_ok(D, H, W), "label_stats: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 1 .. %d)", (long long)D, STAT_MAX_D,
-                (long long)H, (long long)W, STAT_MAX_HW);
+  LABEL_REQUIRE_OBJECTS("label_stats", n);
+  LABEL_REQUIRE_SIZES("label_stats", D, H, W, 1, LABEL_NO_VOXEL_CAP, "");
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(stats, 0xff, (size_t)(D * n * 5) * sizeof(int), s) != hipSuccess) return msam2_check_launch("label_stats (memset)");
-  int64_t band = (STAT_BAND_BYTES + W - 1) / W;
+  int64_t band = cdiv(STAT_BAND_BYTES, W);
   band = band < STAT_ROWS ? band : STAT_ROWS;
   band = band < H ? band : H;
-  hipLaunchKernelGGL(label_stats_kernel, dim3((unsigned)((H + band - 1) / band), (unsigned)D), dim3(STAT_THREADS), 0, s, labels, ids, (int)n,
+  hipLaunchKernelGGL(label_stats_kernel, dim3(cdiv(H, band), (unsigned)D), dim3(STAT_THREADS), 0, s, labels, ids, (int)n,
                      (int)H, (int)W, (int)band, stats, rows);
   return msam2_check_launch("label_stats");
 }
@@ -268,9 +259,8 @@ extern "C" int msam2_label_pick(const uint8_t* labels, const uint8_t* ids, const
                                 int64_t D, int64_t H, int64_t W, int64_t n, int* xy, void* stream) {
   MSAM2_REQUIRE(labels && ids && stats && rows && xy, "label_pick: null labels / ids / stats / rows / xy");
   MSAM2_REQUIRE((k != nullptr) != (u != nullptr), "label_pick: exactly one of k (indices) and u (uniform words) is needed");
-  MSAM2_REQUIRE(n >= 1 && n <= STAT_MAX_OBJ, "label_pick: n = %lld objects (1 .. %d per call)", (long long)n, STAT_MAX_OBJ);
-  MSAM2_REQUIRE(sizes_ok(D, H, W), "label_pick: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 1 .. %d)", (long long)D, STAT_MAX_D,
-                (long long)H, (long long)W, STAT_MAX_HW);
+  LABEL_REQUIRE_OBJECTS("label_pick", n);
+  LABEL_REQUIRE_SIZES("label_pick", D, H, W, 1, LABEL_NO_VOXEL_CAP, "");
   hipLaunchKernelGGL(label_pick_kernel, dim3((unsigned)n, (unsigned)D), dim3(STAT_THREADS), 0, (hipStream_t)stream, labels, ids, stats, rows, k,
                      reinterpret_cast<const unsigned*>(u), (int)H, (int)W, (int)n, xy);
   return msam2_check_launch("label_pick");

@@ -25,9 +25,6 @@
 namespace {
 
 constexpr int SRF_THREADS = 256;
-constexpr int SRF_MAX_OBJ = 32;
-constexpr int SRF_MAX_D = 65535, SRF_MAX_HW = 8192;
-constexpr int64_t SRF_MAX_VOXELS = (1ll << 31) - 2;
 constexpr int SRF_NONE = 0xFFFF;                            // no feature in this row of the box (a real distance is <= 8191)
 enum { SRF_SURFACE = 0, SRF_OUTSIDE = 1 };
 
@@ -41,7 +38,7 @@ struct SrfOrgan {
 };
 struct SrfJobs {                                            // a kernel argument: 2 KiB
   int n, D, H, W;
-  SrfOrgan o[SRF_MAX_OBJ];
+  SrfOrgan o[LABEL_MAX_OBJ];
 };
 
 __host__ __device__ __forceinline__ long long srf_round8(long long b) { return (b + 7) & ~7ll; }
@@ -241,7 +238,7 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
     const bool query = (mine >> it) & 1u;
     const unsigned long long qm = __ballot(query);
     if (query) {
-      const int64_t slot = at + (int)__popcll(qm & ((1ull << lane) - 1ull));
+      const int64_t slot = at + lanes_below(qm, lane);
       if (slot < o.cap[dir]) {                              // past the capacity: counted, not stored
         const SrfVoxel v(first + it * SRF_THREADS + threadIdx.x, o);
         out[o.seg[dir] + slot] = srf_scan_z(t, o, v.zb, v.yb, v.xb, sz2);
@@ -251,27 +248,31 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
   }
 }
 
-bool srf_sizes_ok(int64_t D, int64_t H, int64_t W) {
-  return D >= 1 && D <= SRF_MAX_D && H >= 2 && H <= SRF_MAX_HW && W >= 2 && W <= SRF_MAX_HW && D * H * W <= SRF_MAX_VOXELS;
-}
-bool srf_box_ok(const int32_t* box, int64_t D, int64_t H, int64_t W) {   // (z0, z1, y0, y1, x0, x1), inclusive
+// A box is six host integers (z0, z1, y0, y1, x0, x1), inclusive.  Is it upright and inside a D x H x W volume?
+bool srf_box_ok(const int32_t* box, int64_t D, int64_t H, int64_t W) {
   return box[0] >= 0 && box[0] <= box[1] && box[1] < D && box[2] >= 0 && box[2] <= box[3] && box[3] < H && box[4] >= 0 && box[4] <= box[5] &&
          box[5] < W;
 }
+// its sizes (of a box that srf_box_ok accepted)
+struct SrfExtent {
+  int bd, bh, bw;
+  int64_t rows() const { return (int64_t)bd * bh; }
+};
+SrfExtent srf_extent(const int32_t* box) { return {box[1] - box[0] + 1, box[3] - box[2] + 1, box[5] - box[4] + 1}; }
 // A spacing is usable iff its square is a normal float64 and 2^36 times it is finite: the largest squared index difference is below 2^33, so
 // no product or sum overflows (inf * 0 would be NaN at a feature voxel) and no square flushes to 0 or loses bits as a subnormal.  False for NaN.
 constexpr double SRF_MIN_SPACING2 = 2.2250738585072014e-308, SRF_MAX_SPACING2 = 1.7976931348623157e308 / 68719476736.0;
 bool srf_spacing_ok(double s) { return s > 0.0 && s * s >= SRF_MIN_SPACING2 && s * s <= SRF_MAX_SPACING2; }
 // The row pass runs one wave per row of the box in one launch: 64 threads per row must stay below 2^32 in all (2^25 rows: half of that).
 constexpr int64_t SRF_MAX_ROWS = 1ll << 25;
-bool srf_rows_ok(const int32_t* box) { return (int64_t)(box[1] - box[0] + 1) * (box[3] - box[2] + 1) <= SRF_MAX_ROWS; }
+bool srf_rows_ok(const int32_t* box) { return srf_extent(box).rows() <= SRF_MAX_ROWS; }
 
 void srf_set_box(SrfOrgan& o, const int32_t* box) {
+  const SrfExtent e = srf_extent(box);
   o.z0 = box[0], o.y0 = box[2], o.x0 = box[4];
-  o.bd = box[1] - box[0] + 1, o.bh = box[3] - box[2] + 1, o.bw = box[5] - box[4] + 1;
+  o.bd = e.bd, o.bh = e.bh, o.bw = e.bw;
 }
 int64_t srf_vox(const SrfOrgan& o) { return (int64_t)o.bd * o.bh * o.bw; }
-unsigned srf_blocks(int64_t n, int64_t per) { return (unsigned)((n + per - 1) / per); }
 
 // the three passes up to t, for jobs.n organs and `dirs` directions
 void srf_launch_fields(const uint8_t* a, const uint8_t* b, int mode, const SrfJobs& jobs, int dirs, char* ws, double sy, double sx, int* counts,
@@ -284,23 +285,21 @@ void srf_launch_fields(const uint8_t* a, const uint8_t* b, int mode, const SrfJo
   }
   const unsigned gy = dirs == 2 ? 2 * jobs.n : 1;           // dense: organ 0, direction 0
   hipLaunchKernelGGL(srf_zero_kernel, dim3(1, gy), dim3(SRF_THREADS), 0, s, jobs, ws, counts);
-  hipLaunchKernelGGL(srf_row_kernel, dim3(srf_blocks(rows, SRF_THREADS / 64), gy), dim3(SRF_THREADS), 0, s, a, b, mode, jobs, ws);
-  hipLaunchKernelGGL(srf_col_kernel, dim3(srf_blocks(vox, SRF_THREADS), gy), dim3(SRF_THREADS), 0, s, jobs, ws, sx * sx, sy * sy);
+  hipLaunchKernelGGL(srf_row_kernel, dim3(cdiv(rows, SRF_THREADS / 64), gy), dim3(SRF_THREADS), 0, s, a, b, mode, jobs, ws);
+  hipLaunchKernelGGL(srf_col_kernel, dim3(cdiv(vox, SRF_THREADS), gy), dim3(SRF_THREADS), 0, s, jobs, ws, sx * sx, sy * sy);
 }
 
 }  // namespace
 
 extern "C" size_t msam2_label_edt_workspace_bytes(int64_t bd, int64_t bh, int64_t bw) {
-  if (!(bd >= 1 && bd <= SRF_MAX_D && bh >= 1 && bh <= SRF_MAX_HW && bw >= 1 && bw <= SRF_MAX_HW && bd * bh * bw <= SRF_MAX_VOXELS && bd * bh <= SRF_MAX_ROWS))
-    return 0;
+  if (!label_sizes_ok(bd, bh, bw, 1, LABEL_MAX_VOXELS) || bd * bh > SRF_MAX_ROWS) return 0;   // a box may be one row or column thin
   return (size_t)srf_dir_bytes(bd, bd * bh * bw);
 }
 
 extern "C" int msam2_label_edt(const uint8_t* labels, int64_t D, int64_t H, int64_t W, int value, int features, const int32_t* box, double sz,
                                double sy, double sx, double* d2, void* workspace, size_t workspace_bytes, void* stream) {
   MSAM2_REQUIRE(labels && d2 && workspace, "label_edt: null labels / d2 / workspace");
-  MSAM2_REQUIRE(srf_sizes_ok(D, H, W), "label_edt: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 2 .. %d, at most 2^31 - 2 voxels)", (long long)D,
-                SRF_MAX_D, (long long)H, (long long)W, SRF_MAX_HW);
+  LABEL_REQUIRE_SIZES("label_edt", D, H, W, 2, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(value >= 0 && value <= 255, "label_edt: value %d (0 .. 255)", value);
   MSAM2_REQUIRE(features == SRF_SURFACE || features == SRF_OUTSIDE, "label_edt: features %d (0: the surface of value, 1: the voxels != value)",
                 features);
@@ -310,8 +309,7 @@ extern "C" int msam2_label_edt(const uint8_t* labels, int64_t D, int64_t H, int6
   if (!box) box = whole;                                    // host integers (z0, z1, y0, y1, x0, x1), inclusive
   MSAM2_REQUIRE(srf_box_ok(box, D, H, W), "label_edt: box (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", box[0],
                 box[1], box[2], box[3], box[4], box[5], (long long)D, (long long)H, (long long)W);
-  MSAM2_REQUIRE(srf_rows_ok(box), "label_edt: the box has more than 2^25 rows (slices x rows: %lld)",
-                (long long)(box[1] - box[0] + 1) * (box[3] - box[2] + 1));
+  MSAM2_REQUIRE(srf_rows_ok(box), "label_edt: the box has more than 2^25 rows (slices x rows: %lld)", (long long)srf_extent(box).rows());
   SrfJobs jobs = {};
   jobs.n = 1, jobs.D = (int)D, jobs.H = (int)H, jobs.W = (int)W;
   srf_set_box(jobs.o[0], box);
@@ -321,19 +319,20 @@ extern "C" int msam2_label_edt(const uint8_t* labels, int64_t D, int64_t H, int6
   MSAM2_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)d2 & 7) == 0, "label_edt: d2 / workspace must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   srf_launch_fields(labels, labels, features, jobs, 1, (char*)workspace, sy, sx, nullptr, s);
-  hipLaunchKernelGGL(srf_z_dense_kernel, dim3(srf_blocks(srf_vox(jobs.o[0]), SRF_THREADS)), dim3(SRF_THREADS), 0, s, jobs, (char*)workspace, sz * sz,
+  hipLaunchKernelGGL(srf_z_dense_kernel, dim3(cdiv(srf_vox(jobs.o[0]), SRF_THREADS)), dim3(SRF_THREADS), 0, s, jobs, (char*)workspace, sz * sz,
                      d2);
   return msam2_check_launch("label_edt");
 }
 
 // boxes: HOST int32 [n, 6]
 extern "C" size_t msam2_label_surface_distances_workspace_bytes(const int32_t* boxes, int64_t n) {
-  if (!boxes || n < 1 || n > SRF_MAX_OBJ) return 0;
+  if (!boxes || n < 1 || n > LABEL_MAX_OBJ) return 0;
   size_t total = 0;
   for (int64_t j = 0; j < n; ++j) {
     const int32_t* bx = boxes + 6 * j;
-    if (!srf_box_ok(bx, SRF_MAX_D, SRF_MAX_HW, SRF_MAX_HW)) return 0;
-    const size_t one = msam2_label_edt_workspace_bytes(bx[1] - bx[0] + 1, bx[3] - bx[2] + 1, bx[5] - bx[4] + 1);
+    if (!srf_box_ok(bx, LABEL_MAX_SLICES, LABEL_MAX_SIDE, LABEL_MAX_SIDE)) return 0;
+    const SrfExtent e = srf_extent(bx);
+    const size_t one = msam2_label_edt_workspace_bytes(e.bd, e.bh, e.bw);
     if (!one) return 0;
     total += 2 * one;
   }
@@ -346,10 +345,8 @@ extern "C" int msam2_label_surface_distances(const uint8_t* pred, const uint8_t*
                                              size_t workspace_bytes, void* stream) {
   MSAM2_REQUIRE(pred && gt && ids && boxes && seg_offsets && capacity && dist && counts && workspace,
                 "label_surface_distances: null pred / gt / ids / boxes / seg_offsets / capacity / dist / counts / workspace");
-  MSAM2_REQUIRE(n >= 1 && n <= SRF_MAX_OBJ, "label_surface_distances: n = %lld objects (1 .. %d per call)", (long long)n, SRF_MAX_OBJ);
-  MSAM2_REQUIRE(srf_sizes_ok(D, H, W),
-                "label_surface_distances: bad sizes (D %lld of 1 .. %d, H x W %lldx%lld of 2 .. %d, at most 2^31 - 2 voxels)", (long long)D,
-                SRF_MAX_D, (long long)H, (long long)W, SRF_MAX_HW);
+  LABEL_REQUIRE_OBJECTS("label_surface_distances", n);
+  LABEL_REQUIRE_SIZES("label_surface_distances", D, H, W, 2, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(srf_spacing_ok(sz) && srf_spacing_ok(sy) && srf_spacing_ok(sx),
                 "label_surface_distances: spacing (%g, %g, %g): every value must be positive with a square in 2.3e-308 .. 2.6e297", sz, sy, sx);
   MSAM2_REQUIRE(dist_len >= 0, "label_surface_distances: dist_len %lld", (long long)dist_len);
@@ -362,7 +359,7 @@ extern "C" int msam2_label_surface_distances(const uint8_t* pred, const uint8_t*
                   "label_surface_distances: box %d (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", j, bx[0], bx[1],
                   bx[2], bx[3], bx[4], bx[5], (long long)D, (long long)H, (long long)W);
     MSAM2_REQUIRE(srf_rows_ok(bx), "label_surface_distances: box %d has more than 2^25 rows (slices x rows: %lld)", j,
-                  (long long)(bx[1] - bx[0] + 1) * (bx[3] - bx[2] + 1));
+                  (long long)srf_extent(bx).rows());
     SrfOrgan& o = jobs.o[j];
     srf_set_box(o, bx);
     o.value = ids[j];                                       // ids: HOST bytes, like the boxes
@@ -384,7 +381,7 @@ extern "C" int msam2_label_surface_distances(const uint8_t* pred, const uint8_t*
   int64_t vox = 1;
   for (int j = 0; j < jobs.n; ++j)
     if (srf_vox(jobs.o[j]) > vox) vox = srf_vox(jobs.o[j]);
-  hipLaunchKernelGGL(srf_z_query_kernel, dim3(srf_blocks(vox, SRF_Z_ITER * SRF_THREADS), 2 * (unsigned)n), dim3(SRF_THREADS), 0, s, pred, gt, jobs,
+  hipLaunchKernelGGL(srf_z_query_kernel, dim3(cdiv(vox, SRF_Z_ITER * SRF_THREADS), 2 * (unsigned)n), dim3(SRF_THREADS), 0, s, pred, gt, jobs,
                      (char*)workspace, sz * sz, dist, counts);
   return msam2_check_launch("label_surface_distances");
 }

@@ -66,7 +66,7 @@ __device__ __forceinline__ float resize_value(const float* __restrict__ p, const
 }
 
 constexpr int LBL_THREADS = 256, LBL_ITER = 4;          // voxel groups per thread: a workgroup owns 1024 groups of VPT voxels of one slice
-constexpr int LBL_MAX_OBJ = 32, LBL_MAX_THR = 8;
+constexpr int LBL_MAX_THR = 8;
 
 // Counts of one object over the VPT voxels of each lane of this wave, added to the workgroup's LDS counters c[k * kstride + (0, 1, 2)] =
 // (|P & G|, |P|, |G|) of threshold k.  P = in && v > th[k]; the ballots are wave-uniform, so are the branches around the LDS atomics.
@@ -90,11 +90,7 @@ __device__ __forceinline__ void tally_object(int* c, int kstride, const float (&
       cp += __popcll(mp);
       ci += __popcll(mp & mg[e]);
     }
-    if (lane0) {
-      if (ci) atomicAdd(c + k * kstride + 0, ci);
-      if (cp) atomicAdd(c + k * kstride + 1, cp);
-      if (cg) atomicAdd(c + k * kstride + 2, cg);
-    }
+    if (lane0) LABEL_OVERLAP_ADD(c + k * kstride, ci, cp, cg);
   }
 }
 
@@ -115,7 +111,7 @@ __global__ __launch_bounds__(LBL_THREADS) void label_slices_kernel(const float* 
   const int Wg = W / VPT, groups = H * Wg;                  // H * W < 2^31 (host)
   const int64_t slice = (int64_t)t * H * W;
   const bool lane0 = (threadIdx.x & 63) == 0;
-  __shared__ int cnt[COUNT ? LBL_MAX_THR * LBL_MAX_OBJ * 3 : 1];
+  __shared__ int cnt[COUNT ? LBL_MAX_THR * LABEL_MAX_OBJ * 3 : 1];
   float th[LBL_MAX_THR];
   if (COUNT) {
 #pragma unroll
@@ -210,7 +206,7 @@ void launch_label_slices(hipStream_t s, const float* logits, const uint8_t* ids,
                          int64_t W, float label_thr, const float* thr, int64_t K, const uint8_t* gt, int exclusive, uint8_t* labels,
                          int* counts) {
   const int64_t groups = H * (W / VPT), per = (int64_t)LBL_THREADS * LBL_ITER;
-  hipLaunchKernelGGL((label_slices_kernel<VPT, COUNT>), dim3((unsigned)((groups + per - 1) / per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits,
+  hipLaunchKernelGGL((label_slices_kernel<VPT, COUNT>), dim3(cdiv(groups, per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits,
                      ids, (int)n, (int)lh, (int)lw, (int)H, (int)W, label_thr, thr, (int)K, gt, exclusive, labels, counts, (int)T);
 }
 
@@ -220,9 +216,9 @@ extern "C" int msam2_label_slices(const float* logits, const uint8_t* ids, int64
                                   float label_thr, const float* thresholds, int64_t K, const uint8_t* gt, int exclusive, uint8_t* labels,
                                   int* counts, void* stream) {
   MSAM2_REQUIRE(logits && ids, "label_slices: null logits / ids");
-  MSAM2_REQUIRE(n >= 1 && n <= LBL_MAX_OBJ, "label_slices: n = %lld objects (1 .. %d per call)", (long long)n, LBL_MAX_OBJ);
+  LABEL_REQUIRE_OBJECTS("label_slices", n);
   MSAM2_REQUIRE(K >= 0 && K <= LBL_MAX_THR, "label_slices: K = %lld thresholds (at most %d per call)", (long long)K, LBL_MAX_THR);
-  MSAM2_REQUIRE(T >= 1 && T <= 65535 && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
+  MSAM2_REQUIRE(T >= 1 && T <= LABEL_MAX_SLICES && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
                 "label_slices: bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)T, (long long)lh, (long long)lw, (long long)H,
                 (long long)W);
   MSAM2_REQUIRE(labels || counts, "label_slices: neither labels nor counts requested");

@@ -38,7 +38,6 @@ constexpr int PREP_TW = 64, PREP_TH = 32;        // output tile of the fused for
 constexpr int PREP_LDS_BUDGET = 64 * 1024;       // no opt-in attribute needed; two workgroups per CU at the limit, ~8 KiB at 512 -> 1024
 constexpr int PREP_LUT_BYTES = 3 * 256 * 4;
 constexpr int PREP_BITS = 22;                    // Pillow's PRECISION_BITS = 32 - 8 - 2
-constexpr int PREP_MAX_SIDE = 8192, PREP_MAX_T = 65535;
 enum { SRC_U8 = 0, SRC_I16 = 1, SRC_F32 = 2 };
 
 }  // namespace
@@ -292,7 +291,7 @@ FusedShape fused_shape(int64_t H0, int64_t W0, int64_t S) {
 }
 
 bool prep_sizes_ok(int64_t T, int64_t H0, int64_t W0, int64_t S) {
-  return T >= 1 && T <= PREP_MAX_T && H0 >= 1 && H0 <= PREP_MAX_SIDE && W0 >= 1 && W0 <= PREP_MAX_SIDE && S >= 1 && S <= PREP_MAX_SIDE;
+  return label_sizes_ok(T, H0, W0, 1, LABEL_NO_VOXEL_CAP) && S >= 1 && S <= LABEL_MAX_SIDE;   // the source stack, and the output side
 }
 
 // MSAM2_VOLUME_PREP_FUSED, read per call: 0 = the two-launch form, 1 = the fused form (an error where it does not fit), unset = by size
@@ -373,7 +372,7 @@ extern "C" int msam2_volume_prep(const void* src, int src_type, int64_t T, int64
   MSAM2_REQUIRE(src_type == SRC_U8 || src_type == SRC_I16 || src_type == SRC_F32, "volume_prep: src_type %d (0 uint8, 1 int16, 2 float32)", src_type);
   MSAM2_REQUIRE(Cin == 1 || Cin == 3, "volume_prep: Cin = %lld (1 or 3)", (long long)Cin);
   MSAM2_REQUIRE(prep_sizes_ok(T, H0, W0, S), "volume_prep: bad sizes (T %lld of 1 .. %d, H0 x W0 %lldx%lld and S %lld of 1 .. %d)", (long long)T,
-                PREP_MAX_T, (long long)H0, (long long)W0, (long long)S, PREP_MAX_SIDE);
+                LABEL_MAX_SLICES, (long long)H0, (long long)W0, (long long)S, LABEL_MAX_SIDE);
   MSAM2_REQUIRE(src_type == SRC_U8 || windows, "volume_prep: int16 / float32 sources need windows (HOST pointer to three (lo, hi) pairs)");
   MSAM2_REQUIRE(ksize_x == prep_ksize(W0, S) && ksize_y == prep_ksize(H0, S),
                 "volume_prep: table sizes ksize_x %lld, ksize_y %lld; %lld -> %lld needs %d and %lld -> %lld needs %d (0: pass skipped)", (long long)ksize_x,
@@ -431,7 +430,7 @@ extern "C" int msam2_label_resize(const void* src, int src_type, int64_t T, int6
   MSAM2_REQUIRE(src && ymap && xmap && out, "label_resize: null src / ymap / xmap / out");
   MSAM2_REQUIRE(src_type >= LAB_U8 && src_type <= LAB_I64, "label_resize: src_type %d (0 uint8, 1 int16, 2 int32, 3 int64)", src_type);
   MSAM2_REQUIRE(prep_sizes_ok(T, H0, W0, S), "label_resize: bad sizes (T %lld of 1 .. %d, H0 x W0 %lldx%lld and S %lld of 1 .. %d)", (long long)T,
-                PREP_MAX_T, (long long)H0, (long long)W0, (long long)S, PREP_MAX_SIDE);
+                LABEL_MAX_SLICES, (long long)H0, (long long)W0, (long long)S, LABEL_MAX_SIDE);
   LabelResizeParams P = {};
   P.src = src, P.T = (int)T, P.H0 = (int)H0, P.W0 = (int)W0, P.S = (int)S, P.ymap = ymap, P.xmap = xmap, P.out = out;
   for (int i = 0; i < 8; ++i) P.keep[i] = keep8 ? keep8[i] : 0xffffffffu;

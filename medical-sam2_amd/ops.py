@@ -815,15 +815,40 @@ def box_nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float) -> 
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The label-volume entries (csrc/volume_labels.hip, prompts.hip, volume_prep.hip, components.hip, surface.hip).  Their limits, checked here
+# so that the message names the caller's tensor; each mirrors a constant of the library, which checks again:
+LABEL_MAX_OBJECTS = 32            # csrc/common.h LABEL_MAX_OBJ: objects (ids) per call
+LABEL_MAX_SLICES = 65535          # csrc/common.h LABEL_MAX_SLICES: D of a volume, T of a stack
+LABEL_MAX_SIDE = 8192             # csrc/common.h LABEL_MAX_SIDE: rows and columns
+LABEL_MAX_VOXELS = 2 ** 31 - 2    # csrc/common.h LABEL_MAX_VOXELS: D * H * W of the entries that index voxels with an int32
+LABEL_MAX_THRESHOLDS = 8          # csrc/volume_labels.hip LBL_MAX_THR: thresholds per label_slices call
+
+
+def _label_values(what: str, ids, at_least: int):
+    """host integers or a tensor -> a list of label values, each 1 .. 255"""
+    vals = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+    _req(len(vals) >= at_least and all(1 <= v <= 255 for v in vals), f"{what} must be integers in 1 .. 255 (0 is the background)")
+    return vals
+
+
+def _device_table(what: str, t, dtype, shape, dev, whose: str, dtype_text: Optional[str] = None) -> None:
+    """t must be a contiguous tensor of `dtype` (one, or a tuple of accepted ones: the first is named) and `shape` on `dev`, the device of
+    the tensor `whose` names ("labels'", "source's")"""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    _req(isinstance(t, torch.Tensor) and t.dtype in dtypes and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev,
+         f"{what} must be {dtype_text or str(dtypes[0]).split('.')[-1]} contiguous {list(shape)} on the {whose} device")
+
+
+def _workspace8(nbytes: int, dev) -> torch.Tensor:
+    """at least nbytes bytes, 8-byte aligned"""
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # end of the 3-D path: label volumes and per-organ counts from low-res logits (csrc/volume_labels.hip)
-LABEL_MAX_OBJECTS = 32
-LABEL_MAX_THRESHOLDS = 8
-
-
 def label_ids(ids, device) -> torch.Tensor:
     """Label values of the objects as the uint8 [n] device tensor label_slices takes: checked on the host (integers 1 .. 255, distinct)."""
-    vals = [int(v) for v in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
-    _req(len(vals) >= 1 and all(1 <= v <= 255 for v in vals), "label_slices: ids must be integers in 1 .. 255 (0 is the background)")
+    vals = _label_values("label_slices: ids", ids, 1)
     _req(len(set(vals)) == len(vals), "label_slices: ids must be distinct")
     return torch.tensor(vals, dtype=torch.uint8).to(device)
 
@@ -852,11 +877,9 @@ def label_slices(logits: torch.Tensor, ids, H: int, W: int, label_thr: float = 0
         K = thr_d.numel()
         counts = torch.empty(K, T, n, 3, dtype=torch.int32, device=dev)
     if gt is not None:
-        _req(gt.dtype == torch.uint8 and gt.is_contiguous() and tuple(gt.shape) == (T, H, W) and gt.device == dev,
-             f"label_slices: gt must be uint8 contiguous [{T}, {H}, {W}] on the logits' device")
+        _device_table("label_slices: gt", gt, torch.uint8, (T, H, W), dev, "logits'")
     if isinstance(labels, torch.Tensor):
-        _req(labels.dtype == torch.uint8 and labels.is_contiguous() and tuple(labels.shape) == (T, H, W) and labels.device == dev,
-             f"label_slices: labels must be uint8 contiguous [{T}, {H}, {W}] on the logits' device")
+        _device_table("label_slices: labels", labels, torch.uint8, (T, H, W), dev, "logits'")
         out = labels
     elif labels:
         out = torch.empty(T, H, W, dtype=torch.uint8, device=dev)
@@ -867,12 +890,10 @@ def label_slices(logits: torch.Tensor, ids, H: int, W: int, label_thr: float = 0
 
 # ---------------------------------------------------------------------------------------------------------------------
 # start of the 3-D path: box and click prompts from a label volume (csrc/prompts.hip)
-LABEL_MAX_SLICES = 65535
-LABEL_MAX_SIDE = 8192
-
-
-def _label_volume_args(what: str, labels: torch.Tensor, ids):
-    """the checks the entries on label volumes share -> (ids on the device, D, H, W, n)"""
+def _label_volume_args(what: str, labels: torch.Tensor, ids, min_side: int = 1, max_voxels: bool = False):
+    """the checks the entries on label volumes share -> (ids on the device, D, H, W, n).  Every entry states its own contract: min_side = 2
+    where a voxel needs an in-plane neighbour (csrc/surface.hip), max_voxels where the library indexes voxels with an int32 (components.hip,
+    surface.hip; label_stats and label_pick use 64-bit offsets and have no cap)"""
     _req(isinstance(labels, torch.Tensor) and labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous(),
          f"{what}: labels must be a uint8 contiguous [D, H, W] label volume")
     D, H, W = labels.shape
@@ -887,6 +908,8 @@ def _label_volume_args(what: str, labels: torch.Tensor, ids):
         _req(ids_d.dtype == torch.uint8 and ids_d.dim() == 1 and 1 <= n <= LABEL_MAX_OBJECTS,
              f"{what}: ids must be 1 .. {LABEL_MAX_OBJECTS} uint8 label values, got {n}")
     _req(labels.is_cuda, f"{what}: the label volume must be on the GPU")
+    _req(H >= min_side and W >= min_side, f"{what}: H x W = {H} x {W} (at least {min_side} rows and columns)")
+    _req(not max_voxels or D * H * W <= LABEL_MAX_VOXELS, f"{what}: {D * H * W} voxels (at most 2^31 - 2)")
     return ids_d, D, H, W, n
 
 
@@ -899,8 +922,7 @@ def label_stats(labels: torch.Tensor, ids, rows: Optional[torch.Tensor] = None):
     dev = labels.device
     if rows is None:
         rows = torch.empty(D, n, H, dtype=torch.int32, device=dev)
-    _req(rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (D, n, H) and rows.device == dev,
-         f"label_stats: rows must be int32 contiguous [{D}, {n}, {H}] on the labels' device")
+    _device_table("label_stats: rows", rows, torch.int32, (D, n, H), dev, "labels'")
     stats = torch.empty(D, n, 5, dtype=torch.int32, device=dev)
     check(lib().msam2_label_stats(_p(labels), _p(ids_d), D, H, W, n, _p(stats), _p(rows), _stream()))
     return stats, rows
@@ -914,13 +936,12 @@ def label_pick(labels: torch.Tensor, ids, stats: torch.Tensor, rows: torch.Tenso
     ids_d, D, H, W, n = _label_volume_args("label_pick", labels, ids)
     dev = labels.device
     _req((k is None) != (u is None), "label_pick: exactly one of k and u")
-    _req(stats.dtype == torch.int32 and stats.is_contiguous() and tuple(stats.shape) == (D, n, 5) and stats.device == dev,
-         f"label_pick: stats must be int32 contiguous [{D}, {n}, 5] on the labels' device")
-    _req(rows.dtype == torch.int32 and rows.is_contiguous() and tuple(rows.shape) == (D, n, H) and rows.device == dev,
-         f"label_pick: rows must be int32 contiguous [{D}, {n}, {H}] on the labels' device")
-    t = k if u is None else u
-    _req(t.dtype in ((torch.int32,) if u is None else (torch.uint32, torch.int32)) and t.is_contiguous() and tuple(t.shape) == (D, n)
-         and t.device == dev, f"label_pick: {'k must be int32' if u is None else 'u must be uint32'} contiguous [{D}, {n}] on the labels' device")
+    _device_table("label_pick: stats", stats, torch.int32, (D, n, 5), dev, "labels'")
+    _device_table("label_pick: rows", rows, torch.int32, (D, n, H), dev, "labels'")
+    if u is None:
+        _device_table("label_pick: k", k, torch.int32, (D, n), dev, "labels'")
+    else:
+        _device_table("label_pick: u", u, (torch.uint32, torch.int32), (D, n), dev, "labels'")
     xy = torch.empty(D, n, 2, dtype=torch.int32, device=dev)
     check(lib().msam2_label_pick(_p(labels), _p(ids_d), _p(stats), _p(rows), _p(k), _p(u), D, H, W, n, _p(xy), _stream()))
     return xy
@@ -932,9 +953,9 @@ PREP_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.float32: 2}
 LABEL_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}
 
 
-def _int32_table(what: str, t: Optional[torch.Tensor], shape, dev) -> None:
-    _req(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == dev,
-         f"{what} must be int32 contiguous {list(shape)} on the source's device")
+def _prep_sizes(what: str, T: int, H0: int, W0: int, S: int) -> None:
+    _req(1 <= T <= LABEL_MAX_SLICES and 1 <= H0 <= LABEL_MAX_SIDE and 1 <= W0 <= LABEL_MAX_SIDE and 1 <= S <= LABEL_MAX_SIDE,
+         f"{what}: sizes {T} x {H0} x {W0} -> {S} (1 .. {LABEL_MAX_SLICES} slices, sides 1 .. {LABEL_MAX_SIDE})")
 
 
 def volume_prep_workspace_bytes(T: int, H0: int, W0: int, size: int) -> int:
@@ -955,8 +976,7 @@ def volume_prep(src: torch.Tensor, size: int, tables_x, tables_y, windows=None, 
     T, Cin, H0, W0 = src.shape
     S, dev = int(size), src.device
     _req(Cin in (1, 3), f"volume_prep: Cin = {Cin} (1 or 3)")
-    _req(1 <= T <= LABEL_MAX_SLICES and 1 <= H0 <= LABEL_MAX_SIDE and 1 <= W0 <= LABEL_MAX_SIDE and 1 <= S <= LABEL_MAX_SIDE,
-         f"volume_prep: sizes {T} x {H0} x {W0} -> {S} (1 .. {LABEL_MAX_SLICES} slices, sides 1 .. {LABEL_MAX_SIDE})")
+    _prep_sizes("volume_prep", T, H0, W0, S)
     tabs = []
     for what, n, tab in (("tables_x", W0, tables_x), ("tables_y", H0, tables_y)):
         if n == S:
@@ -965,8 +985,8 @@ def volume_prep(src: torch.Tensor, size: int, tables_x, tables_y, windows=None, 
             continue
         _req(tab is not None and len(tab) == 2 and isinstance(tab[0], torch.Tensor) and tab[0].dim() == 2, f"volume_prep: {what} = (coefficients, bounds)")
         ks = tab[0].shape[1]
-        _int32_table(f"volume_prep: {what}[0]", tab[0], (S, ks), dev)
-        _int32_table(f"volume_prep: {what}[1]", tab[1], (S, 2), dev)
+        _device_table(f"volume_prep: {what}[0]", tab[0], torch.int32, (S, ks), dev, "source's")
+        _device_table(f"volume_prep: {what}[1]", tab[1], torch.int32, (S, 2), dev, "source's")
         tabs += [tab[0], tab[1], ks]
     win = None
     if src.dtype != torch.uint8:
@@ -975,8 +995,7 @@ def volume_prep(src: torch.Tensor, size: int, tables_x, tables_y, windows=None, 
     res = []
     for what, t, dt in (("out", out, F32), ("grey", grey, torch.uint8)):
         if isinstance(t, torch.Tensor):
-            _req(t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (T, 3, S, S) and t.device == dev,
-                 f"volume_prep: {what} must be {dt} contiguous [{T}, 3, {S}, {S}] on the source's device")
+            _device_table(f"volume_prep: {what}", t, dt, (T, 3, S, S), dev, "source's", str(dt))
             res.append(t)
         else:
             res.append(torch.empty(T, 3, S, S, dtype=dt, device=dev) if t else None)
@@ -1001,21 +1020,17 @@ def label_resize(src: torch.Tensor, size: int, ymap: torch.Tensor, xmap: torch.T
          "label_resize: src must be a uint8 / int16 / int32 / int64 contiguous [T, H0, W0] tensor on the GPU")
     T, H0, W0 = src.shape
     S, dev = int(size), src.device
-    _req(1 <= T <= LABEL_MAX_SLICES and 1 <= H0 <= LABEL_MAX_SIDE and 1 <= W0 <= LABEL_MAX_SIDE and 1 <= S <= LABEL_MAX_SIDE,
-         f"label_resize: sizes {T} x {H0} x {W0} -> {S} (1 .. {LABEL_MAX_SLICES} slices, sides 1 .. {LABEL_MAX_SIDE})")
-    _int32_table("label_resize: ymap", ymap, (S,), dev)
-    _int32_table("label_resize: xmap", xmap, (S,), dev)
+    _prep_sizes("label_resize", T, H0, W0, S)
+    _device_table("label_resize: ymap", ymap, torch.int32, (S,), dev, "source's")
+    _device_table("label_resize: xmap", xmap, torch.int32, (S,), dev, "source's")
     keep = None
     if obj_ids is not None:
-        vals = [int(v) for v in (obj_ids.tolist() if isinstance(obj_ids, torch.Tensor) else obj_ids)]
-        _req(all(1 <= v <= 255 for v in vals), "label_resize: obj_ids must be integers in 1 .. 255 (0 is the background)")
         keep = (ctypes.c_uint32 * 8)()
-        for v in vals:
+        for v in _label_values("label_resize: obj_ids", obj_ids, 0):      # (may repeat, may be empty: nothing is kept)
             keep[v >> 5] |= 1 << (v & 31)
     if out is None:
         out = torch.empty(T, S, S, dtype=torch.uint8, device=dev)
-    _req(out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (T, S, S) and out.device == dev,
-         f"label_resize: out must be uint8 contiguous [{T}, {S}, {S}] on the source's device")
+    _device_table("label_resize: out", out, torch.uint8, (T, S, S), dev, "source's")
     check(lib().msam2_label_resize(_p(src), LABEL_SOURCE_TYPES[src.dtype], T, H0, W0, S, _p(ymap), _p(xmap), keep, _p(out), _stream()))
     return out
 
@@ -1023,12 +1038,6 @@ def label_resize(src: torch.Tensor, size: int, ymap: torch.Tensor, xmap: torch.T
 # ---------------------------------------------------------------------------------------------------------------------
 # between the two: connected components, island removal and overlap counts of label volumes (csrc/components.hip)
 LABEL_CONNECTIVITIES = (4, 8, 6, 18, 26)
-LABEL_MAX_VOXELS = 2 ** 31 - 2
-
-
-def _label_table(what: str, name: str, t: torch.Tensor, like: torch.Tensor, dtype=torch.int32):
-    _req(isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and t.shape == like.shape and t.device == like.device,
-         f"{what}: {name} must be {str(dtype).split('.')[-1]} contiguous {list(like.shape)} on the labels' device")
 
 
 def label_components(labels: torch.Tensor, connectivity: int = 26):
@@ -1037,8 +1046,7 @@ def label_components(labels: torch.Tensor, connectivity: int = 26):
     the background, else 1 + the smallest linear index of the voxel's component; size = the component's voxel count at that smallest voxel,
     0 elsewhere.  All 255 values are handled at once.  Nothing is copied to the host."""
     _req(int(connectivity) in LABEL_CONNECTIVITIES, f"label_components: connectivity {connectivity} (one of {LABEL_CONNECTIVITIES})")
-    _, D, H, W, _ = _label_volume_args("label_components", labels, None)
-    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_components: {D * H * W} voxels (at most 2^31 - 2)")
+    _, D, H, W, _ = _label_volume_args("label_components", labels, None, max_voxels=True)
     dev = labels.device
     comp = torch.empty(D, H, W, dtype=torch.int32, device=dev)
     size = torch.empty_like(comp)
@@ -1065,11 +1073,10 @@ def label_clean(labels: torch.Tensor, comp: torch.Tensor, size: torch.Tensor, id
     or an int32 device tensor [n]; keep_largest: one bool or one per object; out: None (a new volume), or a uint8 volume to fill -- labels
     itself for in place.  info = (components found, voxels found, largest size, its canonical name or 0, components kept, voxels kept).
     Nothing is copied to the host."""
-    ids_d, D, H, W, n = _label_volume_args("label_clean", labels, ids)
-    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_clean: {D * H * W} voxels (at most 2^31 - 2)")
+    ids_d, D, H, W, n = _label_volume_args("label_clean", labels, ids, max_voxels=True)
     dev = labels.device
-    _label_table("label_clean", "comp", comp, labels)
-    _label_table("label_clean", "size", size, labels)
+    _device_table("label_clean: comp", comp, torch.int32, labels.shape, labels.device, "labels'")
+    _device_table("label_clean: size", size, torch.int32, labels.shape, labels.device, "labels'")
     mask = label_largest_mask(keep_largest, n)
     mv = None
     if isinstance(min_voxels, torch.Tensor):
@@ -1081,10 +1088,10 @@ def label_clean(labels: torch.Tensor, comp: torch.Tensor, size: torch.Tensor, id
         mv = torch.tensor(vals, dtype=torch.int32).to(dev) if any(vals) else None
     if out is None:
         out = torch.empty_like(labels)
-    _label_table("label_clean", "out", out, labels, torch.uint8)
+    _device_table("label_clean: out", out, torch.uint8, labels.shape, labels.device, "labels'")
     info = torch.empty(n, 6, dtype=torch.int32, device=dev)
     nb = lib().msam2_label_clean_workspace_bytes(n)
-    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    ws = _workspace8(nb, dev)
     check(lib().msam2_label_clean(_p(labels), _p(comp), _p(size), _p(ids_d), n, _p(mv), mask, _p(out), _p(info), _p(ws), nb, D, H, W, _stream()))
     return out, info
 
@@ -1092,9 +1099,8 @@ def label_clean(labels: torch.Tensor, comp: torch.Tensor, size: torch.Tensor, id
 def label_overlap(pred: torch.Tensor, gt: torch.Tensor, ids) -> torch.Tensor:
     """counts int32 [D, n, 3] = (|P & G|, |P|, |G|) per slice and object, P = pred == ids[j], G = gt == ids[j], of two uint8 [D, H, W] label
     volumes: the triple label_slices gives with exclusive=True at one threshold.  Nothing is copied to the host."""
-    ids_d, D, H, W, n = _label_volume_args("label_overlap", pred, ids)
-    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_overlap: {D * H * W} voxels (at most 2^31 - 2)")
-    _label_table("label_overlap", "gt", gt, pred, torch.uint8)
+    ids_d, D, H, W, n = _label_volume_args("label_overlap", pred, ids, max_voxels=True)
+    _device_table("label_overlap: gt", gt, torch.uint8, pred.shape, pred.device, "labels'")
     counts = torch.empty(D, n, 3, dtype=torch.int32, device=pred.device)
     check(lib().msam2_label_overlap(_p(pred), _p(gt), _p(ids_d), D, H, W, n, _p(counts), _stream()))
     return counts
@@ -1123,9 +1129,7 @@ def label_edt(labels: torch.Tensor, value: int, spacing=(1.0, 1.0, 1.0), feature
     plane when D == 1); "outside": the voxels != value (the classic in-mask distance; beyond the volume there are no features).
     box: host integers (z0, z1, y0, y1, x0, x1), inclusive, default the whole volume; features are taken from the box only.
     Nothing is copied to the host."""
-    _, D, H, W, _ = _label_volume_args("label_edt", labels, None)
-    _req(H >= 2 and W >= 2, f"label_edt: H x W = {H} x {W} (at least 2 rows and columns)")
-    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_edt: {D * H * W} voxels (at most 2^31 - 2)")
+    _, D, H, W, _ = _label_volume_args("label_edt", labels, None, min_side=2, max_voxels=True)
     _req(features in EDT_FEATURES, f"label_edt: features {features!r} (one of {tuple(EDT_FEATURES)})")
     _req(0 <= int(value) <= 255, f"label_edt: value {value} (0 .. 255)")
     sz, sy, sx = _spacing("label_edt", spacing)
@@ -1136,7 +1140,7 @@ def label_edt(labels: torch.Tensor, value: int, spacing=(1.0, 1.0, 1.0), feature
     dev = labels.device
     d2 = torch.empty(bd, bh, bw, dtype=torch.float64, device=dev)
     nb = lib().msam2_label_edt_workspace_bytes(bd, bh, bw)
-    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    ws = _workspace8(nb, dev)
     check(lib().msam2_label_edt(_p(labels), D, H, W, int(value), EDT_FEATURES[features], (ctypes.c_int32 * 6)(*bx), sz, sy, sx, _p(d2), _p(ws), nb,
                                 _stream()))
     return d2
@@ -1179,10 +1183,8 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
     only synchronisation on the way in; nothing else is copied to the host.
     Organs are processed in groups whose workspace (20 bytes per box voxel) stays below `workspace_bytes`; an organ whose box alone needs more
     raises with the needed size in the message."""
-    ids_d, D, H, W, n = _label_volume_args("label_surface_distances", pred, ids)
-    _req(H >= 2 and W >= 2, f"label_surface_distances: H x W = {H} x {W} (at least 2 rows and columns)")
-    _req(D * H * W <= LABEL_MAX_VOXELS, f"label_surface_distances: {D * H * W} voxels (at most 2^31 - 2)")
-    _label_table("label_surface_distances", "gt", gt, pred, torch.uint8)
+    ids_d, D, H, W, n = _label_volume_args("label_surface_distances", pred, ids, min_side=2, max_voxels=True)
+    _device_table("label_surface_distances: gt", gt, torch.uint8, pred.shape, pred.device, "labels'")
     sz, sy, sx = _spacing("label_surface_distances", spacing)
     dev = pred.device
     sp, _ = label_stats(pred, ids_d)
@@ -1216,7 +1218,7 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
         cur.append(j)
         used += nb
     groups.append(cur)
-    ws = torch.empty((max(sum(need[j] for j in g) for g in groups) + 7) // 8, dtype=torch.int64, device=dev)
+    ws = _workspace8(max(sum(need[j] for j in g) for g in groups), dev)
     for g in groups:
         k = len(g)
         flat = lambda rows: [v for j in g for v in rows[j]]                                                 # noqa: E731

@@ -108,6 +108,21 @@ def test_argument_errors_cross_the_abi_as_codes():
         assert msg.startswith(what.split(":")[0] + ":"), (what, msg)
 
 
+def test_workspace_sizes_are_zero_exactly_beyond_the_limits():
+    """msam2_label_components_workspace_bytes returns 0 for the sizes the entry refuses and only for them: every dimension at its limit and
+    one beyond, and the voxel cap (2^31 - 2 = 49981 x 2387 x 18; 2^31 - 1 is prime, so the next volume that exists is 2^31)"""
+    from medical_sam2_amd import _lib
+    L = _lib.lib()
+    ws = L.msam2_label_components_workspace_bytes
+    assert ws(1, 1, 1) == 4 and ws(0, 1, 1) == 0 and ws(1, 0, 1) == 0 and ws(1, 1, 0) == 0
+    assert ws(65535, 1, 1) == 65535 * 4 and ws(65536, 1, 1) == 0
+    assert ws(1, 8192, 1) == 8192 * 4 and ws(1, 8193, 1) == 0
+    assert ws(1, 1, 8192) == 8192 * 4 and ws(1, 1, 8193) == 0
+    assert ws(49981, 2387, 18) == (2 ** 31 - 2) * 4 and ws(32768, 8192, 8) == 0
+    clean = L.msam2_label_clean_workspace_bytes
+    assert clean(1) == clean(32) > 0 and clean(0) == 0 and clean(33) == 0
+
+
 def test_wrappers_check_their_arguments_without_a_device():
     import medical_sam2_amd.ops as ops
     from medical_sam2_amd.volume_labels import clean_labels, label_scores

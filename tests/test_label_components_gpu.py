@@ -297,8 +297,10 @@ def test_clean_equals_the_restatement_through_the_abi(name):
 
 def test_overlap_equals_the_restatement_and_label_slices():
     import medical_sam2_amd.ops as ops
-    for name in ("blobs13_4x256x256", "blobs32_9x33x100", "noise4_9x33x100"):
-        vol, ids = CLEAN_CASES[name]
+    # D * n * 3 counters are zeroed 256 per workgroup: 156 and 864 (a remainder), 54, and 64 x 4 x 3 = 768 (three whole workgroups)
+    cases = dict(CLEAN_CASES, noise4_64x2x3=(R.noise((64, 2, 3), 4, 30), [1, 2, 3, 4]))
+    for name in ("blobs13_4x256x256", "blobs32_9x33x100", "noise4_9x33x100", "noise4_64x2x3"):
+        vol, ids = cases[name]
         gt = np.ascontiguousarray(np.roll(vol, (1, 3, -5), axis=(0, 1, 2)))
         gt[gt == ids[0]] = ids[-1]
         for shift in (0, 1):

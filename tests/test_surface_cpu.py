@@ -209,6 +209,27 @@ def test_argument_errors_of_the_surface_entries_are_codes_with_messages():
     assert L.msam2_label_surface_distances_workspace_bytes(i32(0, 3, 7, 0, 0, 15), 1) == 0
 
 
+def test_workspace_sizes_are_zero_exactly_beyond_the_limits():
+    """the two workspace-size entries return 0 for the boxes their entries refuse and only for them: every dimension at its limit and one
+    beyond (a box may be one row or column thin), 2^25 and 2^25 + 1 = 8283 x 4051 rows, 2^31 - 2 = 77 x 4681 x 5958 and 2^31 voxels, 32 and
+    33 boxes"""
+    from medical_sam2_amd import _lib
+    L = _lib.lib()
+    i32 = lambda *v: (ctypes.c_int32 * len(v))(*v)                                                         # noqa: E731
+    one, many = L.msam2_label_edt_workspace_bytes, L.msam2_label_surface_distances_workspace_bytes
+    assert one(1, 1, 1) == 8 + 8 + 8 and one(0, 1, 1) == 0 and one(1, 0, 1) == 0 and one(1, 1, 0) == 0
+    assert one(65535, 1, 1) > 0 and one(65536, 1, 1) == 0
+    assert one(1, 8192, 1) > 0 and one(1, 8193, 1) == 0
+    assert one(1, 1, 8192) > 0 and one(1, 1, 8193) == 0
+    assert one(4096, 8192, 1) > 0 and one(8283, 4051, 1) == 0
+    assert one(77, 4681, 5958) == (2 ** 31 - 2) * 10 + 4 + 312 and one(128, 4096, 4096) == 0
+    assert many(i32(0, 65534, 0, 0, 0, 0), 1) == 2 * one(65535, 1, 1) and many(i32(0, 65535, 0, 0, 0, 0), 1) == 0
+    assert many(i32(0, 0, 0, 8191, 0, 0), 1) == 2 * one(1, 8192, 1) and many(i32(0, 0, 0, 8192, 0, 0), 1) == 0
+    assert many(i32(0, 0, 0, 0, 0, 8191), 1) == 2 * one(1, 1, 8192) and many(i32(0, 0, 0, 0, 0, 8192), 1) == 0
+    assert many(i32(*([0, 3, 0, 7, 0, 15] * 32)), 32) == 64 * one(4, 8, 16) and many(i32(*([0, 3, 0, 7, 0, 15] * 33)), 33) == 0
+    assert many(i32(0, 3, 0, 7, 0, 15), 0) == 0 and many(None, 1) == 0
+
+
 def test_wrapper_argument_checks_need_no_device():
     import torch
     import medical_sam2_amd.ops as ops

@@ -178,6 +178,7 @@ def _dense_cases():
     yield "wide_box_5_70_outside", (wide, 1, 77, "outside", (3, 5, 10, 22, 5, 70))
     yield "wide_box_63_64", (wide, 0, 77, "surface", (0, 8, 0, 32, 63, 64))
     yield "wide_box_64_99_outside", (wide, 0, 77, "outside", (2, 4, 12, 18, 64, 99))
+    yield "wide_box_256_voxels", (wide, 1, 77, "surface", (0, 7, 0, 7, 0, 3))          # 64 rows, 256 voxels: whole workgroups in every launch
     yield "wide_one_row", (wide, 1, 77, "surface", (4, 4, 16, 16, 3, 99))
     yield "wide_one_row_outside", (wide, 1, 77, "outside", (4, 4, 13, 13, 3, 99))
     yield "wide_one_column_of_slices", (wide, 1, 77, "outside", (0, 8, 16, 16, 50, 50))
@@ -280,7 +281,8 @@ def test_boxes_cut_queries_and_features():
     pred, gt, ids = fixture(name)
     whole = tuple(R.whole(pred.shape) for _ in ids)
     cut = ((1, 4, 3, 18, 2, 9), (0, 8, 9, 9, 0, 99), (5, 7, 20, 32, 25, 30))
-    for boxes in (whole, cut):
+    full = ((0, 7, 8, 23, 10, 25), (0, 7, 0, 7, 0, 3), (0, 7, 8, 23, 10, 25))          # the largest: 2048 voxels, one whole workgroup of the z pass
+    for boxes in (whole, cut, full):
         run = Batch(pred, gt, ids, boxes, shift=1)
         for spacing in R.SPACINGS[:2]:
             check_batch(run.run(spacing), batch_reference(name, spacing, boxes), (boxes, spacing))
