@@ -45,6 +45,8 @@ SIGNATURES = {
     "msam2_attention_merge": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_z, c_p]),
     "msam2_window_attention_fwd": (c_i, [c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_p, c_p, c_l, c_l,
                                          c_l, c_l, c_l, c_f, c_p]),
+    "msam2_window_qkv_attention_supported": (c_i, [c_l, c_l, c_l, c_l, c_i, c_l, c_l]),
+    "msam2_window_qkv_attention_fwd": (c_i, [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_f, c_p]),
     "msam2_attention_small_fwd": (c_i, [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_f,
                                         c_p]),
     "msam2_add_cast": (c_i, [c_p, c_i, c_l, c_l, c_p, c_i, c_l, c_l, c_f, c_p, c_i, c_l, c_l, c_l, c_p]),

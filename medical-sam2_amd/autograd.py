@@ -337,7 +337,8 @@ def forward_image(model, imgs: torch.Tensor) -> dict:
         dec = model.sam_mask_decoder
         params += [dec.conv_s0.weight, dec.conv_s0.bias, dec.conv_s1.weight, dec.conv_s1.bias]
     if not any(p.requires_grad for p in params):
-        with torch.no_grad():                          # a frozen encoder (train_3d.py:34-37 leaves it out of both optimisers): plain forward
+        from .modeling.encoder import two_launch_qkv_attention
+        with torch.no_grad(), two_launch_qkv_attention():   # a frozen encoder (train_3d.py:34-37 leaves it out of both optimisers): plain forward
             return model.forward_image(imgs)
     feats = ImageEncoderFn.apply(model, imgs, *params)
     with torch.no_grad():                              # sine position maps: input-independent constants (image_encoder.py:101-133)

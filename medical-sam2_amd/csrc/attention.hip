@@ -87,10 +87,6 @@ __device__ __forceinline__ WgCoords xcd_wg_coords() {
   return {lid % gx, (lid / gx) % gy, lid / (gx * gy)};
 }
 
-// The 32x32 MFMA accumulator of lane (r = lane & 31, h = lane >> 5) holds column r, and in register e row (e & 3) + 8 * (e >> 2) + 4 * h.
-// For S^T = K Q^T that row is the key of score register e (the column is the lane's query); for O^T it is the channel within a 32-block.
-__device__ __forceinline__ constexpr int s_frag_key(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-
 // Lazy move of a row's running softmax reference (MSAM2_RESCALE_SLACK above): only when some lane of the wave sees the tile maximum mx
 // exceed m_run by more than the slack are the running sum and the O accumulators rescaled to the new reference.
 template <int DBLK>
@@ -106,21 +102,6 @@ __device__ __forceinline__ void softmax_move_reference(float mx, float& m_run, f
     m_run = m_new;
   }
 }
-
-// Normalise-and-store of this lane's O^T column (one query row of DBLK * 32 channels) at dst: register 4 g + e of block d is channel
-// 32 d + 8 g + 4 h + e (s_frag_key), so every group g is one 8-byte store.  A macro because a function changes the listing of EVERY kernel
-// that calls it (after inlining the stores' address arithmetic loses its inbounds / no-wrap marks and the epilogue is scheduled
-// differently); tools/isa_diff.py holds this text to the code the kernels had with the loop written out.
-#define ATTN_STORE_O_ROWS(DBLK, dst, o, inv, h)                                           \
-  do {                                                                                \
-    op16* const dst_ = (dst);                                                         \
-    _Pragma("unroll") for (int d_ = 0; d_ < DBLK; ++d_)                               \
-      _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) {                              \
-        op16x4 w_;                                                                    \
-        _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) w_[e_] = f2op((o)[d_][4 * g_ + e_] * (inv)); \
-        *reinterpret_cast<op16x4*>(dst_ + d_ * 32 + 8 * g_ + 4 * (h)) = w_;           \
-      }                                                                               \
-  } while (0)
 
 __device__ __forceinline__ int64_t win_token_offset(int t, int ws, int wy, int wx, int himg, int wimg, bool& valid) {
   const int ty = t / ws, tx = t - ty * ws;

@@ -221,6 +221,33 @@ struct DmaImage {
 typedef DmaImage<128> Img128;
 typedef DmaImage<64> Img64;
 
+// Slot of 16-byte chunk c of row r in the LDS images with 192- / 384-byte rows (mlp_fused.hip's weight chunks, attention.hip's
+// attn_winproj_kernel): conflict free for the 32-row ds_read_b128 fragment reads; applied where the image is filled and on the reads.
+template <int RB>
+__device__ __forceinline__ int mlp_swz(int c, int r) {
+  if constexpr (RB == 192) return (c & ~3) | ((c & 3) ^ ((r >> 2) & 3));
+  else return (c & ~7) | ((c & 7) ^ ((r >> 1) & 7));
+}
+
+// The 32x32 MFMA accumulator of lane (r = lane & 31, h = lane >> 5) holds column r, and in register e row (e & 3) + 8 * (e >> 2) + 4 * h.
+// For S^T = K Q^T that row is the key of score register e (the column is the lane's query); for O^T it is the channel within a 32-block.
+__device__ __forceinline__ constexpr int s_frag_key(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// Normalise-and-store of this lane's O^T column (one query row of DBLK * 32 channels) at dst: register 4 g + e of block d is channel
+// 32 d + 8 g + 4 h + e (s_frag_key), so every group g is one 8-byte store.  A macro because a function changes the listing of EVERY kernel
+// that calls it (after inlining the stores' address arithmetic loses its inbounds / no-wrap marks and the epilogue is scheduled
+// differently); tools/isa_diff.py holds this text to the code the kernels had with the loop written out.
+#define ATTN_STORE_O_ROWS(DBLK, dst, o, inv, h)                                           \
+  do {                                                                                \
+    op16* const dst_ = (dst);                                                         \
+    _Pragma("unroll") for (int d_ = 0; d_ < DBLK; ++d_)                               \
+      _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) {                              \
+        op16x4 w_;                                                                    \
+        _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_) w_[e_] = f2op((o)[d_][4 * g_ + e_] * (inv)); \
+        *reinterpret_cast<op16x4*>(dst_ + d_ * 32 + 8 * g_ + 4 * (h)) = w_;           \
+      }                                                                               \
+  } while (0)
+
 // host: raise kernel K's dynamic-LDS limit once per process (per kernel instance); the return code is ignored
 template <auto K>
 static inline void ensure_dyn_lds(int bytes) {

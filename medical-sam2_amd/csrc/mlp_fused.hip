@@ -33,12 +33,6 @@ struct MlpFusedParams {
   op16* out16;           // optional second output: the same rows in the 16-bit operand type (a stage's last block: the FPN's lateral GEMM operand)
 };
 
-template <int RB>
-__device__ __forceinline__ int mlp_swz(int c, int r) {
-  if constexpr (RB == 192) return (c & ~3) | ((c & 3) ^ ((r >> 2) & 3));
-  else return (c & ~7) | ((c & 7) ^ ((r >> 1) & 7));
-}
-
 // NWV waves per workgroup (4 or 8).  With 8 (round 4) the workgroup still owns ONE weight ring in LDS, a wave carries TB = half as many
 // token blocks, and every SIMD holds two waves: one wave's GELU / LayerNorm vector work and LDS reads run under the other's MFMAs, and a
 // wave's registers (<= 256) no longer spill (the 4-wave form at dim 192 spilled 21-35 registers of a 512-register budget).

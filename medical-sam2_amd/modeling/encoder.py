@@ -21,7 +21,24 @@ import os as _os
 _POOL_GEMM = _os.environ.get("MSAM2_NO_POOL_GEMM") is None   # experiment switches
 _QPOOL_GEMM = _os.environ.get("MSAM2_NO_QPOOL_GEMM") is None
 _FUSED_MLP = _os.environ.get("MSAM2_NO_FUSED_MLP") is None
+_FUSED_QKV_ATTN = _os.environ.get("MSAM2_NO_FUSED_QKV_ATTN") is None   # A/B switch: qkv GEMM + window attention as two launches
 _FUSED_PATCH = _os.environ.get("MSAM2_NO_FUSED_PATCH") is None
+_TWO_LAUNCH = 0   # depth of two_launch_qkv_attention()
+
+
+class two_launch_qkv_attention:
+    """Context of the TRAINING forwards (training.py, training_3d.py): inside it the trunk's forward keeps the qkv GEMM and the window
+    attention as two launches, the q | k | v bits every backward of this package was validated against (the BPTT chain's gradients are
+    ill-conditioned in the encoder's features: DESIGN.md 8, item 00-ii)."""
+
+    def __enter__(self):
+        global _TWO_LAUNCH
+        _TWO_LAUNCH += 1
+
+    def __exit__(self, *exc):
+        global _TWO_LAUNCH
+        _TWO_LAUNCH -= 1
+        return False
 
 
 class PatchEmbed(nn.Module):
@@ -185,9 +202,11 @@ class MultiScaleBlock(nn.Module):
         return (D, Dp, wc.get("qkvw_p", [a.qkv.weight], qkv_w), wc.get("qkvb_p", [a.qkv.bias], qkv_b),
                 wc.get("ow_p", [a.proj.weight], proj_w))
 
-    def run(self, t: torch.Tensor, B: int, H: int, W: int, emit16: bool = False) -> Tuple[torch.Tensor, int, int]:
+    def run(self, t: torch.Tensor, B: int, H: int, W: int, emit16: bool = False, fused_qkv_attn: bool = False) -> Tuple[torch.Tensor, int, int]:
         """fp32 tokens [B*H*W, dim] -> (fp32 tokens [B*H'*W', dim_out], H', W').  emit16 (a stage's last block): `self.out16` also holds the
-        result in the 16-bit operand type when the block's last kernel could write it in the same store (else None)."""
+        result in the 16-bit operand type when the block's last kernel could write it in the same store (else None).  fused_qkv_attn (the
+        inference trunk asks for it; the training forward does not, its backward recomputes the block from the q | k | v map of the GEMM
+        path and must see the same bits): where the kernel is built, the qkv projection runs inside the window-attention kernel."""
         self.out16 = None
         wc, a = self._wc, self.attn
         heads, dim_out = a.num_heads, self.dim_out
@@ -205,19 +224,24 @@ class MultiScaleBlock(nn.Module):
                     shortcut = ops.maxpool2x2(shortcut, B, H, W)
         else:
             shortcut = t
-        if _POOL_GEMM and _QPOOL_GEMM and pool and B * H * W >= 256 and H % 2 == 0 and W % 2 == 0 and width % 32 == 0:
-            qkv, qp = ops.gemm_qkv_pool2x2(xn, qkv_w, qkv_b, B, H, W, width)   # k | v in image order + pooled q, one GEMM
-        else:
-            qkv = ops.gemm(xn, qkv_w, qkv_b)  # 16-bit [T, 3*width]
-            qp = ops.maxpool2x2(qkv[:, :width], B, H, W) if pool else None
         Hq, Wq = (H // 2, W // 2) if pool else (H, W)
-        if self.window_size > 0:
-            o = ops.window_attention(qkv, B, H, W, heads, self.window_size, qkv_b, q_pooled=qp, scale=scale)
+        # (the gate looks at per-slice quantities only, never at B: a slice's features must not depend on its batch mates)
+        if (fused_qkv_attn and _FUSED_QKV_ATTN and self.window_size > 0 and Dp == D
+                and ops.window_qkv_attention_supported(self.dim, dim_out, heads, self.window_size, pool, H, W)):
+            o = ops.window_qkv_attention(xn, qkv_w, qkv_b, B, H, W, heads, self.window_size, pool, scale)   # q | k | v stay in registers
         else:
-            v5 = qkv.view(B, H * W, 3, heads, Dp)
-            q = (qp.view(B, Hq * Wq, heads, Dp) if pool else v5[:, :, 0]).permute(0, 2, 1, 3)
-            o = ops.attention(q, v5[:, :, 1].permute(0, 2, 1, 3), v5[:, :, 2].permute(0, 2, 1, 3), scale=scale)
-            o = o.permute(0, 2, 1, 3).reshape(B * Hq * Wq, width)
+            if _POOL_GEMM and _QPOOL_GEMM and pool and B * H * W >= 256 and H % 2 == 0 and W % 2 == 0 and width % 32 == 0:
+                qkv, qp = ops.gemm_qkv_pool2x2(xn, qkv_w, qkv_b, B, H, W, width)   # k | v in image order + pooled q, one GEMM
+            else:
+                qkv = ops.gemm(xn, qkv_w, qkv_b)  # 16-bit [T, 3*width]
+                qp = ops.maxpool2x2(qkv[:, :width], B, H, W) if pool else None
+            if self.window_size > 0:
+                o = ops.window_attention(qkv, B, H, W, heads, self.window_size, qkv_b, q_pooled=qp, scale=scale)
+            else:
+                v5 = qkv.view(B, H * W, 3, heads, Dp)
+                q = (qp.view(B, Hq * Wq, heads, Dp) if pool else v5[:, :, 0]).permute(0, 2, 1, 3)
+                o = ops.attention(q, v5[:, :, 1].permute(0, 2, 1, 3), v5[:, :, 2].permute(0, 2, 1, 3), scale=scale)
+                o = o.permute(0, 2, 1, 3).reshape(B * Hq * Wq, width)
         t = ops.gemm(o, proj_w, v_f32(wc, "ob", a.proj.bias), residual=shortcut, out_dtype=F32)
         mlp = self.mlp
         if (_FUSED_MLP and ops.ln_mlp_residual_supported(dim_out) and mlp.num_layers == 2 and mlp._act_code == ops.ACT_GELU
@@ -296,7 +320,7 @@ class Hiera(nn.Module):
         outputs = []
         for i, blk in enumerate(self.blocks):
             is_out = i == self.stage_ends[-1] or (i in self.stage_ends and self.return_interm_layers)
-            t, h, w = blk.run(t, B, h, w, emit16=is_out)
+            t, h, w = blk.run(t, B, h, w, emit16=is_out, fused_qkv_attn=_TWO_LAUNCH == 0)
             if is_out:
                 v = nchw_view(t, B, h, w)
                 # the 16-bit token-major copy the block's last kernel wrote beside the fp32 rows (stages 1 / 2): FpnNeck takes it as its lateral

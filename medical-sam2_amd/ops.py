@@ -321,6 +321,27 @@ def window_attention(qkv: torch.Tensor, B: int, H: int, W: int, heads: int, ws: 
     return o
 
 
+def window_qkv_attention_supported(dim: int, dim_out: int, heads: int, ws: int, pool: bool, H: int, W: int) -> bool:
+    """True when `window_qkv_attention` is built for a block of this form (per-slice quantities only, never the batch)."""
+    return bool(lib().msam2_window_qkv_attention_supported(dim, dim_out, heads, ws, int(bool(pool)), H, W))
+
+
+def window_qkv_attention(xn: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, B: int, H: int, W: int, heads: int, ws: int,
+                         pool: bool = False, scale: Optional[float] = None) -> torch.Tensor:
+    """`window_attention(gemm(xn, w, bias), ...)` (with 2x2 max-pooled queries when `pool`) as one kernel: the q | k | v map is never
+    written.  xn 16-bit [B*H*W, dim], w 16-bit [3*heads*96, dim], bias fp32 -> o 16-bit [B*Hq*Wq, heads*96].  A form that is not built
+    (`window_qkv_attention_supported`) is an error."""
+    _req(xn.dim() == 2 and w.dim() == 2 and xn.shape[0] == B * H * W and xn.shape[1] == w.shape[1] and w.shape[0] == 3 * heads * 96,
+         "window_qkv_attention shapes")
+    _req(xn.dtype == OP16 and w.dtype == OP16 and xn.is_contiguous() and w.is_contiguous(), "window_qkv_attention operands: 16-bit, contiguous")
+    _req(bias.dtype == F32 and bias.is_contiguous() and bias.numel() == w.shape[0], "window_qkv_attention: bias is fp32 [3*heads*96]")
+    hq, wq = (H // 2, W // 2) if pool else (H, W)
+    o = torch.empty(B * hq * wq, heads * 96, dtype=OP16, device=xn.device)
+    check(lib().msam2_window_qkv_attention_fwd(_p(xn), _p(w), _p(bias), _p(o), B, H, W, xn.shape[1], heads, ws, int(bool(pool)),
+                                               scale if scale is not None else 1.0 / math.sqrt(96), _stream()))
+    return o
+
+
 def attention_small(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decoder attention with head dim 16/32: q [B,Lq,C], k/v [B,Lk,C] bf16 (C = heads*D contiguous) -> [B,Lq,C] bf16."""
     B, Lq, C = q.shape

@@ -372,7 +372,9 @@ def train_step_2d(model, opt_mem: DecoderAdam, opt_dec: DecoderAdam, imgs, pts, 
     if opt_enc is not None:
         backbone_out, enc_state = be.image_encoder_forward_saved(model, imgs)
     else:
-        backbone_out = model.forward_image(imgs)
+        from .modeling.encoder import two_launch_qkv_attention
+        with two_launch_qkv_attention():
+            backbone_out = model.forward_image(imgs)
     _, vision_feats, vision_pos_embeds, feat_sizes = model._prepare_backbone_features(backbone_out)
     h, w = feat_sizes[-1]
     se, _ = model.sam_prompt_encoder(points=(pts, labels), boxes=None, masks=None, batch_size=B)

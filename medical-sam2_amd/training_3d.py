@@ -28,6 +28,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import backward as bwd
+from .modeling.encoder import two_launch_qkv_attention
 from . import ops
 from ._lib import check, lib
 from .ops import F32, OP16, _p, _stream
@@ -84,7 +85,8 @@ def volume_forward_saved(model, volume: torch.Tensor, prompts: Dict[int, dict], 
     order = cond_ids + [t for t in range(T) if t not in prompts]
     for t in order:
         is_cond = t in prompts
-        bo = model.forward_image(volume[t][None])
+        with two_launch_qkv_attention():
+            bo = model.forward_image(volume[t][None])
         bo = {"backbone_fpn": [f.expand(n, -1, -1, -1) for f in bo["backbone_fpn"]],
               "vision_pos_enc": [q.expand(n, -1, -1, -1) for q in bo["vision_pos_enc"]]}
         _, feats, pos, sizes = model._prepare_backbone_features(bo)
