@@ -22,7 +22,6 @@ logits: a gradient arriving there RAISES -- `_RaiseOnGrad` -- instead of being d
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional
 
 import torch
@@ -30,6 +29,7 @@ import torch.nn.functional as F
 
 from . import backward as bwd
 from . import ops
+from .links import decoder_link, pow2_scale_of
 from .ops import F32, OP16
 
 NO_OBJ_SCORE = -1024.0
@@ -38,12 +38,6 @@ NO_OBJ_SCORE = -1024.0
 def active(model) -> bool:
     """the autograd bridge applies: grad mode on and the module in train() mode (module docstring)"""
     return torch.is_grad_enabled() and model.training
-
-
-def _pow2(t: torch.Tensor) -> float:
-    """power of two that brings max|t| to [2^-4, 2^-3] (one host read)"""
-    a = float(t.detach().abs().max().item())
-    return 2.0 ** (-3 - math.ceil(math.log2(a))) if a > 0 and math.isfinite(a) else 1.0
 
 
 def _named(module) -> List[str]:
@@ -109,7 +103,7 @@ class MemoryAttentionFn(torch.autograd.Function):
             return (None,) * (6 + len(ctx.params))
         _check(ctx, ctx.params, "MemoryAttention")
         with torch.no_grad():
-            s = _pow2(dy)
+            s = pow2_scale_of(dy)
             st = dict(ctx.state)
             st["ctxs"] = list(st["ctxs"])               # the explicit backward releases its state as it goes: keep ours for retain_graph=True
             dcurr, dmem, dmem_pos, grads = bwd.memory_attention_backward_saved(ctx.module, st, dy.to(F32) * s)
@@ -149,34 +143,11 @@ class MaskDecoderFn(torch.autograd.Function):
         if d_masks is None and d_tokens is None:
             return (None,) * n_in
         _check(ctx, ctx.params, "MaskDecoder")
-        dec = ctx.args[0]
         with torch.no_grad():
-            dev = ctx.args[1].device
-            B, h, w = ctx.args[6:9]
-            nm, C = dec.num_mask_tokens, dec.transformer_dim
-            # One scale for both upstream gradients, chosen from the MASK gradient (it enters as a 16-bit GEMM operand right away); the token
-            # gradient is added in fp32 before anything is rounded and only has to stay inside the 16-bit range -- if it would not, the two
-            # are back-propagated separately (the decoder backward is linear).  Same rule as training_3d.volume_backward.
-            a_m = float(d_masks.abs().max().item()) if d_masks is not None else 0.0
-            a_t = float(d_tokens.abs().max().item()) if d_tokens is not None else 0.0
-            if a_m == 0.0 and a_t == 0.0:
+            link = decoder_link(ctx.args, d_masks, d_tokens)
+            if link is None:
                 return (None,) * n_in
-            dm = d_masks.to(F32).contiguous() if a_m > 0 else torch.zeros(B, nm, 4 * h, 4 * w, dtype=F32, device=dev)
-            dt = d_tokens.to(F32).contiguous() if a_t > 0 else None
-            s_d = _pow2(dm) if a_m > 0 else _pow2(dt)
-            aux: dict = {}
-            if a_m > 0 and a_t * s_d > 1024.0:
-                d_src, d_sp, g = bwd.mask_decoder_backward(*ctx.args, dm * s_d, aux=aux)
-                s_t = _pow2(dt)
-                aux2: dict = {}
-                d_src2, d_sp2, g2 = bwd.mask_decoder_backward(*ctx.args, torch.zeros_like(dm), aux=aux2, d_mask_tokens=dt * s_t)
-                r = s_d / s_t
-                d_src, d_sp = d_src + d_src2 * r, d_sp + d_sp2 * r
-                g = {k: v + g2[k] * r for k, v in g.items()}
-                for k in ("d_feat_s0", "d_feat_s1"):
-                    aux[k] = aux[k].to(F32) + aux2[k].to(F32) * r
-            else:
-                d_src, d_sp, g = bwd.mask_decoder_backward(*ctx.args, dm * s_d, aux=aux, d_mask_tokens=None if dt is None else dt * s_d)
+            d_src, d_sp, g, aux, s_d = link
             inv = 1.0 / s_d
             d_f0 = aux["d_feat_s0"].to(F32) * inv if ctx.need_hr else None
             d_f1 = aux["d_feat_s1"].to(F32) * inv if ctx.need_hr else None
@@ -216,7 +187,7 @@ class MemoryEncoderFn(torch.autograd.Function):
         enc, pix, m, mode, sc, bi, B, H, W = ctx.args
         with torch.no_grad():
             d = tokens_of(dy.to(F32))
-            s = _pow2(d)
+            s = pow2_scale_of(d)
             d_pix, g, d_mask = bwd.memory_encoder_backward(enc, pix, m, mode, sc, bi, B, H, W, (d * s).contiguous(), need_dmask=True)
             inv = 1.0 / s
             d_top = (d_pix.to(F32) * inv).view(B, H * W, -1).transpose(0, 1)
@@ -243,7 +214,7 @@ class TokenMLPFn(torch.autograd.Function):
             return (None,) * (2 + len(ctx.params))
         _check(ctx, ctx.params, "obj_ptr_proj")
         with torch.no_grad():
-            s = _pow2(dy)
+            s = pow2_scale_of(dy)
             g: dict = {}
             d_tok = bwd.mlp_layers_backward(ctx.mlp, ctx.tok16, (dy.to(F32) * s).contiguous(), "p", g)
             inv = 1.0 / s
@@ -337,9 +308,9 @@ def forward_image(model, imgs: torch.Tensor) -> dict:
         dec = model.sam_mask_decoder
         params += [dec.conv_s0.weight, dec.conv_s0.bias, dec.conv_s1.weight, dec.conv_s1.bias]
     if not any(p.requires_grad for p in params):
-        from .modeling.encoder import two_launch_qkv_attention
-        with torch.no_grad(), two_launch_qkv_attention():   # a frozen encoder (train_3d.py:34-37 leaves it out of both optimisers): plain forward
-            return model.forward_image(imgs)
+        from .modeling.encoder import frozen_forward_image
+        with torch.no_grad():                              # a frozen encoder (train_3d.py:34-37 leaves it out of both optimisers): plain forward
+            return frozen_forward_image(model, imgs)
     feats = ImageEncoderFn.apply(model, imgs, *params)
     with torch.no_grad():                              # sine position maps: input-independent constants (image_encoder.py:101-133)
         pos = [model.image_encoder.neck.position_encoding(f).to(f.dtype) for f in feats]

@@ -23,6 +23,7 @@ import torch
 from . import backward as bwd
 from . import ops
 from ._lib import check, lib
+from .links import amax_of, pow2_scale
 from .modeling.common import OP16, F32, nchw_view, to_bf16, tokens_of, v_f32, w_bf16
 from .ops import _is_bf16, _p, _stream
 
@@ -279,11 +280,6 @@ def _lateral_backward(x_tok: torch.Tensor, conv, d_out: torch.Tensor, post=None,
     return dx, g_lat, g_post
 
 
-def _pow2_scale(amax: float) -> float:
-    import math
-    return 2.0 ** (-3 - math.ceil(math.log2(amax))) if amax > 0 and math.isfinite(amax) else 1.0
-
-
 def record_scaled_amax(scales: dict, key: str, scaled: torch.Tensor, calibrating: bool) -> None:
     """Running max|scaled gradient| of one link, kept ON THE DEVICE next to its cached scale (scales["_amax"][key], a 1-element tensor
     created while calibrating and updated in place afterwards, so the update is part of a captured graph).  The scales are calibrated
@@ -356,8 +352,7 @@ def image_encoder_backward(model, state: dict, d_fpn: List[Optional[torch.Tensor
     def rescaled(key: str, parts):
         """sum of (tensor, scale) pairs brought to the cached / calibrated power-of-two scale of `key`; returns (tensor, scale)"""
         if calibrate:
-            amax = max(float(t.abs().max().item()) / s for t, s in parts)
-            scales[key] = _pow2_scale(amax)
+            scales[key] = pow2_scale(max(amax_of(t) / s for t, s in parts))
         s_new = scales[key]
         acc = None
         for t, s in parts:

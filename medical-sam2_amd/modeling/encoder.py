@@ -27,7 +27,7 @@ _TWO_LAUNCH = 0   # depth of two_launch_qkv_attention()
 
 
 class two_launch_qkv_attention:
-    """Context of the TRAINING forwards (training.py, training_3d.py): inside it the trunk's forward keeps the qkv GEMM and the window
+    """Context of the TRAINING forwards (entered by `frozen_forward_image` below): inside it the trunk's forward keeps the qkv GEMM and the window
     attention as two launches, the q | k | v bits every backward of this package was validated against (the BPTT chain's gradients are
     ill-conditioned in the encoder's features: DESIGN.md 8, item 00-ii)."""
 
@@ -39,6 +39,13 @@ class two_launch_qkv_attention:
         global _TWO_LAUNCH
         _TWO_LAUNCH -= 1
         return False
+
+
+def frozen_forward_image(model, imgs: torch.Tensor) -> dict:
+    """`model.forward_image` of a frozen encoder as every training driver runs it -- the one place in the package that enters
+    `two_launch_qkv_attention` for a training forward: a caller that runs the plain forward instead moves 16-bit outputs by an ulp."""
+    with two_launch_qkv_attention():
+        return model.forward_image(imgs)
 
 
 class PatchEmbed(nn.Module):

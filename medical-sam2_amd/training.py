@@ -20,12 +20,12 @@ Pinned by tests/test_backward_gpu.py (oracle + autograd + torch.optim) and tests
 """
 from __future__ import annotations
 
-import math
 from typing import Dict
 
 import torch
 
 from . import backward as bwd
+from . import links
 from . import ops
 from . import parallel
 from ._lib import check, lib
@@ -67,8 +67,16 @@ class DecoderAdam:
         """weight_decay = 0: torch.optim.Adam as train_3d.py:50-54 builds it; > 0: torch.optim.AdamW's decoupled decay (train_2d.py:43-47)."""
         self.decoder, self.lr, self.betas, self.eps, self.weight_decay = decoder, lr, betas, eps, weight_decay
         self.state: Dict[str, tuple] = {}
+        self.reset_calibration()
         self._t_dev = None          # int32 [2] on the parameters' device: [step count t (advanced by a kernel inside every step), number of
                                     # non-finite gradient elements skipped so far]
+
+    def reset_calibration(self):
+        """Drop what the first eager step calibrated and every captured replay reuses (`GraphedStep.recalibrate` does).
+        calibrated_loss_scales {mask_index | ("bank", mask_index): memory loss scale / decoder loss scale};
+        calibrated_block_scales {mask_index: the per-link scales of `backward_encoder.image_encoder_backward`} (on the encoder's optimiser);
+        scale_monitor: the device-side running maxima of `backward_encoder.record_scaled_amax`."""
+        self.calibrated_loss_scales, self.calibrated_block_scales, self.scale_monitor = {}, {}, {}
 
     @property
     def t(self) -> int:
@@ -176,10 +184,9 @@ class GraphedStep:
 
     def _scale_dicts(self):
         for o in self.optimizers:
-            if getattr(o, "scale_monitor", None):
+            if o.scale_monitor:
                 yield o.scale_monitor
-            for d in (getattr(o, "calibrated_block_scales", None) or {}).values():
-                yield d
+            yield from o.calibrated_block_scales.values()
 
     def drift(self) -> dict:
         """{link: scaled max|gradient| outside the safe band since the last call} plus {"skipped_elements": n} when Adam skipped non-finite
@@ -203,12 +210,7 @@ class GraphedStep:
     def recalibrate(self):
         """drop every cached scale, run the step eagerly once (it calibrates afresh, with host reads) and capture it again"""
         for o in self.optimizers:
-            if hasattr(o, "calibrated_loss_scales"):
-                o.calibrated_loss_scales = {}
-            if hasattr(o, "calibrated_block_scales"):
-                o.calibrated_block_scales = None
-            if hasattr(o, "scale_monitor"):
-                o.scale_monitor = {}
+            o.reset_calibration()
         self.eager_fn()
         self._capture()
         self.recalibrations += 1
@@ -221,8 +223,7 @@ def _shared_pow2_scale(amax: torch.Tensor, data_parallel: bool, group=None) -> f
     if data_parallel and parallel._is_dist(group):
         import torch.distributed as dist
         dist.all_reduce(amax, op=dist.ReduceOp.MAX, group=group)
-    a = float(amax.item())
-    return 2.0 ** (-3 - math.ceil(math.log2(a))) if a > 0 and math.isfinite(a) else 1.0
+    return links.pow2_scale(float(amax.item()))
 
 
 def _assert_same_on_all_ranks(value: float, what: str, group=None):
@@ -231,6 +232,18 @@ def _assert_same_on_all_ranks(value: float, what: str, group=None):
         vals = [None] * dist.get_world_size(group)
         dist.all_gather_object(vals, float(value), group=group)
         assert all(v == vals[0] for v in vals), f"{what} differs across the data-parallel ranks: {vals}"
+
+
+def _scaled_mask_loss(masks: torch.Tensor, target_masks: torch.Tensor, pos_weight: float, mask_index: int = None):
+    """(loss, d loss / d masks multiplied by scale, scale, number of elements under the mean) for both loss forms: all mask tokens
+    against target_masks [B, nm, 4h, 4w], or -- mask_index, the reference's loss -- that one mask up-sampled to target_masks [B, 1, S, S].
+    The scale is `links.bce_loss_scale`: fixed, so the step stays capturable."""
+    if mask_index is None:
+        (loss, d_masks), n_loss = bce_with_logits(masks, target_masks, pos_weight), masks.numel()
+    else:
+        (loss, d_masks), n_loss = upsampled_mask_loss(masks, target_masks, mask_index, pos_weight), target_masks.numel()
+    scale = links.bce_loss_scale(n_loss, pos_weight, mask_index is not None)
+    return loss, d_masks.mul_(scale), scale, n_loss
 
 
 @torch.no_grad()
@@ -243,18 +256,7 @@ def decoder_finetune_step(decoder, optimizer: DecoderAdam, src_tokens, pe_tokens
     step -- ~3000 small launches -- can be captured in a hipGraph and replayed without host work).  data_parallel: one process per GPU,
     each on its own slices; the gradients are averaged with `parallel.allreduce_gradients` (one bucketed RCCL all-reduce) before Adam."""
     masks, _, _, _ = decoder.predict_masks_tokens(src_tokens, pe_tokens, sparse, feat_s0, feat_s1, B, h, w)
-    if mask_index is None:
-        loss, d_masks = bce_with_logits(masks, target_masks, pos_weight)
-        n_loss = masks.numel()
-    else:   # the reference's loss: one mask, up-sampled to the target's (video) resolution -- target_masks [B, 1, S, S]
-        loss, d_masks = upsampled_mask_loss(masks, target_masks, mask_index, pos_weight)
-        n_loss = target_masks.numel()
-    # Loss scale: |dloss/dlogit| <= max(pos_weight, 1) / n is ~1e-6 at 1024^2 -- below the 16-bit operand's normal range (fp16: 6e-5).
-    # A fixed power of two (data independent, so the step stays capturable) brings the largest entry to 2^-4; the backward is linear
-    # in d_masks, the update kernel multiplies the gradients by the inverse.
-    # (n_loss elements share the mean; the up-sampling adjoint sums ~16 of them per low-res pixel: still <= 2^0)
-    scale = 2.0 ** (math.floor(math.log2(n_loss / max(float(pos_weight), 1.0))) - 4 - (0 if mask_index is None else 4))
-    d_masks.mul_(scale)
+    loss, d_masks, scale, _ = _scaled_mask_loss(masks, target_masks, pos_weight, mask_index)
     _, _, grads = bwd.mask_decoder_backward(decoder, src_tokens, pe_tokens, sparse, feat_s0, feat_s1, B, h, w, d_masks)
     inv_world = 1.0
     if data_parallel:                                   # each rank on its own slices: mean of the per-rank gradients over RCCL
@@ -293,14 +295,7 @@ def memory_decoder_loss_grads(memory_attention, decoder, curr, curr_pos, memory,
     masks, _, _, _ = decoder.predict_masks_tokens(src, pe_tokens, sparse, feat_s0, feat_s1, B, h, w)
     if aux is not None:
         aux["masks"] = masks                                                     # [B, num_mask_tokens, 4h, 4w] logits of this forward
-    if mask_index is None:
-        loss, d_masks = bce_with_logits(masks, target_masks, pos_weight)
-        n_loss, extra = masks.numel(), 0
-    else:                                                                        # the reference's loss form (see upsampled_mask_loss)
-        loss, d_masks = upsampled_mask_loss(masks, target_masks, mask_index, pos_weight)
-        n_loss, extra = target_masks.numel(), 4
-    scale = 2.0 ** (math.floor(math.log2(n_loss / max(float(pos_weight), 1.0))) - 4 - extra)
-    d_masks.mul_(scale)
+    loss, d_masks, scale, _ = _scaled_mask_loss(masks, target_masks, pos_weight, mask_index)
     d_src, _, g_dec = bwd.mask_decoder_backward(decoder, src, pe_tokens, sparse, feat_s0, feat_s1, B, h, w, d_masks, aux=aux)
     if on_decoder_grads is not None:
         on_decoder_grads(g_dec)                                                  # e.g. start their all-reduce under the memory attention's backward
@@ -325,7 +320,7 @@ def memory_decoder_finetune_step(memory_attention, decoder, opt_mem: DecoderAdam
     """One optimisation step of both parameter groups train_3d.py:34-54 builds around the frozen image encoder -- the mask decoder
     (`sam_layers`) and the memory attention (the bulk of `mem_layers`) -- on the loss of `memory_decoder_loss_grads` (same arguments).  The first call calibrates the memory group's loss scale (one host
     synchronisation) and stores it on `opt_mem`; later calls -- and a hipGraph captured after it -- reuse it."""
-    cal = getattr(opt_mem, "calibrated_loss_scales", {})                         # one calibration per loss form, made on its first (eager) step
+    cal = opt_mem.calibrated_loss_scales                                         # one calibration per loss form, made on its first (eager) step
     if kwargs.get("mem_scale") is None:
         kwargs["mem_scale"] = cal.get(kwargs.get("mask_index"))
     calibrating = kwargs.get("mem_scale") is None
@@ -334,7 +329,6 @@ def memory_decoder_finetune_step(memory_attention, decoder, opt_mem: DecoderAdam
     loss, scale, scale_mem, g_dec, g_mem, _ = memory_decoder_loss_grads(memory_attention, decoder, *args, data_parallel=data_parallel,
                                                                        on_decoder_grads=hook, **kwargs)
     cal[kwargs.get("mask_index")] = scale_mem / scale
-    opt_mem.calibrated_loss_scales = cal
     inv_world = 1.0
     if data_parallel:
         if calibrating:                                 # the calibration was collective (MAX over ranks): every rank must hold the same scale
@@ -364,17 +358,15 @@ def train_step_2d(model, opt_mem: DecoderAdam, opt_dec: DecoderAdam, imgs, pts, 
     by `parallel.allreduce_gradients_async`, started as soon as the group's backward is done so that the transfer runs under the next
     group's backward (decoder under memory attention, memory attention under image encoder), and averaged inside Adam (grad_scale).
     Returns (loss, maskmem_features [B,64,S/16,S/16])."""
-    from . import backward as bwd_mod
     from . import backward_encoder as be
     from .modeling.common import refresh_casts, to_bf16, tokens_of
+    from .modeling.encoder import frozen_forward_image
     B = imgs.shape[0]
     refresh_casts(model)                               # the previous step's Adam left every 16-bit weight copy stale: one multi-tensor copy
     if opt_enc is not None:
         backbone_out, enc_state = be.image_encoder_forward_saved(model, imgs)
     else:
-        from .modeling.encoder import two_launch_qkv_attention
-        with two_launch_qkv_attention():
-            backbone_out = model.forward_image(imgs)
+        backbone_out = frozen_forward_image(model, imgs)
     _, vision_feats, vision_pos_embeds, feat_sizes = model._prepare_backbone_features(backbone_out)
     h, w = feat_sizes[-1]
     se, _ = model.sam_prompt_encoder(points=(pts, labels), boxes=None, masks=None, batch_size=B)
@@ -383,20 +375,17 @@ def train_step_2d(model, opt_mem: DecoderAdam, opt_dec: DecoderAdam, imgs, pts, 
     f0, f1 = to_bf16(tokens_of(hr[0])), to_bf16(tokens_of(hr[1]))
     dense = model.sam_prompt_encoder.no_mask_embed.weight.detach().reshape(1, -1)
     aux: dict = {}
-    cal = getattr(opt_mem, "calibrated_loss_scales", {})                         # one calibration per loss form
+    cal = opt_mem.calibrated_loss_scales                                         # one calibration per loss form
     pend: dict = {}
-    mon = getattr(opt_mem, "scale_monitor", None)
-    if mon is None:
-        mon = opt_mem.scale_monitor = {}
-    kwargs = dict(dense_tokens=dense, aux=aux, mem_scale=cal.get(mask_index), mask_index=mask_index, data_parallel=data_parallel, monitor=mon,
+    kwargs = dict(dense_tokens=dense, aux=aux, mem_scale=cal.get(mask_index), mask_index=mask_index, data_parallel=data_parallel,
+                  monitor=opt_mem.scale_monitor,
                   on_decoder_grads=(lambda g: pend.__setitem__("dec", parallel.allreduce_gradients_async(g))) if data_parallel else None)
     # weight-gradient outputs of this backward pass come from buffers zeroed once (backward.ZeroArena): no zeroing launch per GEMM
-    with bwd_mod.zero_arena():
+    with bwd.zero_arena():
         loss, scale, scale_mem, g_dec, g_mem, dcurr = memory_decoder_loss_grads(
             model.memory_attention, model.sam_mask_decoder, vision_feats[-1], vision_pos_embeds[-1], memory, memory_pos, 0, pe, se.to(torch.float32),
             f0, f1, B, h, w, target_masks, **kwargs)
         cal[mask_index] = scale_mem / scale
-        opt_mem.calibrated_loss_scales = cal
         inv_world = 1.0
         if data_parallel:
             pend["mem"] = parallel.allreduce_gradients_async(g_mem)
@@ -405,11 +394,8 @@ def train_step_2d(model, opt_mem: DecoderAdam, opt_dec: DecoderAdam, imgs, pts, 
             # the memory attention's query stream (`scale_mem`); the encoder backward runs every block under its own cached scale
             C = dcurr.shape[-1]
             d_top = dcurr.transpose(0, 1).reshape(B * h * w, C).contiguous()
-            enc_scales = getattr(opt_enc, "calibrated_block_scales", None)
-            if enc_scales is None:
-                enc_scales = opt_enc.calibrated_block_scales = {}
             g_all = be.image_encoder_backward(model, enc_state, [aux["d_feat_s0"], aux["d_feat_s1"], d_top], [scale, scale, scale_mem],
-                                              enc_scales.setdefault(mask_index, {}))
+                                              opt_enc.calibrated_block_scales.setdefault(mask_index, {}))
             if data_parallel:
                 g_all, inv_world = parallel.allreduce_gradients(g_all)
             g_enc = {k[len("image_encoder."):]: v for k, v in g_all.items() if k.startswith("image_encoder.")}
@@ -489,13 +475,11 @@ def memory_bank_finetune_step(model, optimizers: Dict[str, DecoderAdam], *args, 
     "memory_encoder" to a DecoderAdam over `model.sam_mask_decoder` / `model.memory_attention` / `model.memory_encoder` (train_3d.py:50-54
     runs the first at lr 1e-4 and the memory groups at 1e-8); groups without an optimiser are left alone."""
     holder = optimizers.get("memory_attention")
-    cal = getattr(holder, "calibrated_loss_scales", {}) if holder is not None else {}
+    cal = holder.calibrated_loss_scales if holder is not None else {}
     if kwargs.get("mem_scale") is None:
         kwargs["mem_scale"] = cal.get(("bank", kwargs.get("mask_index")))
     loss, scales, grads = memory_bank_loss_grads(model, *args, **kwargs)
-    if holder is not None:
-        cal[("bank", kwargs.get("mask_index"))] = scales["memory_attention"] / scales["decoder"]
-        holder.calibrated_loss_scales = cal
+    cal[("bank", kwargs.get("mask_index"))] = scales["memory_attention"] / scales["decoder"]
     for grp, opt in optimizers.items():
         opt.step(grads[grp], grad_scale=1.0 / scales[grp])
     return float(loss.item()) if sync else loss

@@ -22,15 +22,15 @@ What is not differentiated, as in the reference's optimisers: image encoder, pro
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional
 
 import torch
 
 from . import backward as bwd
-from .modeling.encoder import two_launch_qkv_attention
 from . import ops
 from ._lib import check, lib
+from .links import accumulate, decoder_link, pow2_scale_of
+from .modeling.encoder import frozen_forward_image
 from .ops import F32, OP16, _p, _stream
 from .training import DecoderAdam, upsampled_mask_loss
 
@@ -38,19 +38,6 @@ GROUPS = ("decoder", "memory_attention", "memory_encoder", "obj_ptr_proj")
 # train_step_3d(bounded_tape=None): volumes longer than this many slices train on the bounded tape (the memory attention of a propagated
 # slice is run a second time in the backward: +1 forward of 4 layers per slice against O(slices x keys) of saved projections)
 BOUNDED_TAPE_FROM = 16
-
-
-def _pow2(t: torch.Tensor) -> float:
-    """power of two that brings max|t| to [2^-4, 2^-3] (one host read)"""
-    a = float(t.abs().max().item())
-    return 2.0 ** (-3 - math.ceil(math.log2(a))) if a > 0 and math.isfinite(a) else 1.0
-
-
-def _acc(dst: Dict[str, torch.Tensor], src: Dict[str, torch.Tensor], inv_scale: float, prefix: str = ""):
-    for k, v in src.items():
-        k = prefix + k
-        g = v.to(F32) * inv_scale
-        dst[k] = g if k not in dst else dst[k] + g
 
 
 def _prompt_points(pr: dict):
@@ -85,8 +72,7 @@ def volume_forward_saved(model, volume: torch.Tensor, prompts: Dict[int, dict], 
     order = cond_ids + [t for t in range(T) if t not in prompts]
     for t in order:
         is_cond = t in prompts
-        with two_launch_qkv_attention():
-            bo = model.forward_image(volume[t][None])
+        bo = frozen_forward_image(model, volume[t][None])
         bo = {"backbone_fpn": [f.expand(n, -1, -1, -1) for f in bo["backbone_fpn"]],
               "vision_pos_enc": [q.expand(n, -1, -1, -1) for q in bo["vision_pos_enc"]]}
         _, feats, pos, sizes = model._prepare_backbone_features(bo)
@@ -170,11 +156,11 @@ def volume_backward(model, tape: dict, d_low: Dict[int, torch.Tensor]) -> Dict[s
         dl = None if dl is None else dl.to(F32).clone()
         # 1. memory of this slice was attended to later: memory encoder backward, continue into the mask
         if t in d_mem:
-            s_e = _pow2(d_mem[t])
+            s_e = pow2_scale_of(d_mem[t])
             pix = ops.add_cast(fr["top"].transpose(0, 1), None, 1.0, OP16).view(n * L, C)
             _, g_enc, dmask = bwd.memory_encoder_backward(enc, pix, fr["high"], fr["mode"], sc, bi, n, h, w, (d_mem[t] * s_e).contiguous(),
                                                           need_dmask=True)
-            _acc(grads["memory_encoder"], g_enc, 1.0 / s_e)
+            accumulate(grads["memory_encoder"], g_enc, 1.0 / s_e)
             h4, w4 = fr["out"]["pred_masks"].shape[-2:]
             dlow_e = torch.empty(n, h4, w4, dtype=F32, device=dev)
             check(lib().msam2_bilinear_upsample_bwd(_p(dmask.contiguous()), _p(dlow_e), n, h4, w4, S, S, _stream()))
@@ -184,10 +170,10 @@ def volume_backward(model, tape: dict, d_low: Dict[int, torch.Tensor]) -> Dict[s
         d_tok = None
         if t in d_ptr:
             dp = d_ptr[t] * alive.view(n, 1)
-            s_p = _pow2(dp)
+            s_p = pow2_scale_of(dp)
             g_ptr: dict = {}
             d_token = bwd.mlp_layers_backward(model.obj_ptr_proj, fr["tok16"], (dp * s_p).contiguous(), "p", g_ptr)
-            _acc(grads["obj_ptr_proj"], {k[2:]: v for k, v in g_ptr.items()}, 1.0 / s_p)
+            accumulate(grads["obj_ptr_proj"], {k[2:]: v for k, v in g_ptr.items()}, 1.0 / s_p)
             d_tok = d_token.to(F32) / s_p                                                # [n, C]
         if dl is None and d_tok is None:
             continue
@@ -195,36 +181,22 @@ def volume_backward(model, tape: dict, d_low: Dict[int, torch.Tensor]) -> Dict[s
         nm = dec.num_mask_tokens
         h4, w4 = fr["out"]["pred_masks"].shape[-2:]
         ar = torch.arange(n, device=dev)
-        d_masks = torch.zeros(n, nm, h4, w4, dtype=F32, device=dev)
+        d_masks = d_mtok = None
         if dl is not None:
+            d_masks = torch.zeros(n, nm, h4, w4, dtype=F32, device=dev)
             d_masks[ar, fr["mask_sel"]] = (dl * alive.view(n, 1, 1, 1))[:, 0]
-        d_mtok = None
         if d_tok is not None:
             d_mtok = torch.zeros(n, nm, C, dtype=F32, device=dev)
             d_mtok[ar, fr["tok_sel"] if fr["tok_sel"] is not None else torch.zeros(n, dtype=torch.long, device=dev)] = d_tok
-        # One scale for both upstream gradients, chosen from the MASK gradient: it is the one that enters as a 16-bit GEMM operand right
-        # away (d_masks against the up-scaled features), and a mean-reduced BCE gradient scaled by anything much larger's maximum would
-        # land in fp16's subnormals.  The token gradient is added in fp32 to the
-        # hyper-network path's result before anything is rounded, so it only has to stay inside the 16-bit RANGE: if it would not
-        # (ratio beyond 2^13), the two upstream gradients are back-propagated separately -- the decoder backward is linear.
-        a_m = float(d_masks.abs().max().item()) if dl is not None else 0.0
-        a_t = float(d_mtok.abs().max().item()) if d_mtok is not None else 0.0
-        s_d = _pow2(d_masks) if a_m > 0 else _pow2(d_mtok)
-        args = (dec, fr["src"], fr["pe"], fr["sparse"], fr["f0"], fr["f1"], n, h, w)
-        if a_m > 0 and a_t * s_d > 1024.0:
-            d_src, _, g_dec = bwd.mask_decoder_backward(*args, d_masks * s_d)
-            s_t = _pow2(d_mtok)
-            d_src2, _, g_dec2 = bwd.mask_decoder_backward(*args, torch.zeros_like(d_masks), d_mask_tokens=d_mtok * s_t)
-            r = s_d / s_t
-            d_src = d_src + d_src2 * r
-            g_dec = {k: v + g_dec2[k] * r for k, v in g_dec.items()}
-        else:
-            d_src, _, g_dec = bwd.mask_decoder_backward(*args, d_masks * s_d, d_mask_tokens=None if d_mtok is None else d_mtok * s_d)
-        _acc(grads["decoder"], g_dec, 1.0 / s_d)
+        link = decoder_link((dec, fr["src"], fr["pe"], fr["sparse"], fr["f0"], fr["f1"], n, h, w), d_masks, d_mtok)
+        if link is None:
+            continue                                     # every object of the slice absent: both gradients are zero
+        d_src, _, g_dec, _, s_d = link
+        accumulate(grads["decoder"], g_dec, 1.0 / s_d)
         if fr["cond"]:
             continue                                     # src = features + no_mem_embed: nothing trained upstream
         # 4. memory attention; its d memory goes back to the slices the bank was assembled from
-        s_m = _pow2(d_src)
+        s_m = pow2_scale_of(d_src)
         state = fr.get("state")
         if state is None:                                # bounded tape: this slice's memory attention forward again (see volume_forward_saved)
             spatial, ptrs = fr["mem_sel"]
@@ -233,7 +205,7 @@ def volume_backward(model, tape: dict, d_low: Dict[int, torch.Tensor]) -> Dict[s
             del memory, memory_pos
         _, dmemory, _, g_mem = bwd.memory_attention_backward_saved(ma, state, (d_src * s_m).view(n, L, C).transpose(0, 1))
         del state
-        _acc(grads["memory_attention"], g_mem, 1.0 / (s_d * s_m))
+        accumulate(grads["memory_attention"], g_mem, 1.0 / (s_d * s_m))
         dmemory = dmemory.to(F32) / (s_d * s_m)                                          # [Nk, n, 64]
         for i, u in enumerate(fr["spatial"]):
             g = dmemory[i * L:(i + 1) * L].transpose(0, 1).reshape(n * L, md)
@@ -282,8 +254,7 @@ def train_step_3d(model, optimizers: Dict[str, DecoderAdam], volume: torch.Tenso
     if grads_out is not None:
         grads_out["non_prompt"], grads_out["prompt"] = g_np, g_p
     g_dec = dict(g_p["decoder"])
-    for k, v in g_np["decoder"].items():
-        g_dec[k] = g_dec[k] + v if k in g_dec else v
+    accumulate(g_dec, g_np["decoder"])
     step_grads = {"decoder": g_dec, "memory_attention": g_np["memory_attention"], "memory_encoder": g_np["memory_encoder"],
                   "obj_ptr_proj": g_np["obj_ptr_proj"]}
     inv_world = 1.0
