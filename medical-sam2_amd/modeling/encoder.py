@@ -23,6 +23,10 @@ _QPOOL_GEMM = _os.environ.get("MSAM2_NO_QPOOL_GEMM") is None
 _FUSED_MLP = _os.environ.get("MSAM2_NO_FUSED_MLP") is None
 _FUSED_QKV_ATTN = _os.environ.get("MSAM2_NO_FUSED_QKV_ATTN") is None   # A/B switch: qkv GEMM + window attention as two launches
 _FUSED_PATCH = _os.environ.get("MSAM2_NO_FUSED_PATCH") is None
+_FUSED_GEMM_LN = _os.environ.get("MSAM2_NO_FUSED_GEMM_LN") is None   # A/B switch: a residual GEMM and the LayerNorm behind it as two launches
+# per-shape switch of that fusion: the reduction lengths that are dispatched (384: the proj GEMM of a stage-3 block, 1536: its fc2).  A shape
+# that does not beat its two launches inside the step is taken off this list and stays in the library
+_FUSED_GEMM_LN_K = frozenset(int(k) for k in _os.environ.get("MSAM2_FUSED_GEMM_LN_K", "384,1536").split(",") if k.strip())
 _TWO_LAUNCH = 0   # depth of two_launch_qkv_attention()
 
 
@@ -39,6 +43,11 @@ class two_launch_qkv_attention:
         global _TWO_LAUNCH
         _TWO_LAUNCH -= 1
         return False
+
+
+def _gemm_ln_dispatched(N: int, K: int) -> bool:
+    """Does a residual GEMM [*, K] -> [*, N] that was handed a LayerNorm run both as one kernel?  (per-slice quantities only, never B)"""
+    return _FUSED_GEMM_LN and K in _FUSED_GEMM_LN_K and ops.gemm_residual_layernorm_supported(N, K)
 
 
 def frozen_forward_image(model, imgs: torch.Tensor) -> dict:
@@ -106,16 +115,21 @@ class MLP(nn.Module):
         self._act_code = ops.ACT_GELU if isinstance(self.act, nn.GELU) else ops.ACT_RELU
         self._wc = WeightCache()
 
-    def run(self, x_bf16: torch.Tensor, residual: Optional[torch.Tensor] = None, out_dtype=F32) -> torch.Tensor:
-        """x [rows, in] bf16 -> [rows, out]; hidden activations bf16, last layer (+ residual) in out_dtype."""
+    def run(self, x_bf16: torch.Tensor, residual: Optional[torch.Tensor] = None, out_dtype=F32, ln=None):
+        """x [rows, in] bf16 -> [rows, out]; hidden activations bf16, last layer (+ residual) in out_dtype.
+        ln = (weight, bias, eps) of the LayerNorm that follows (only the inference trunk passes one): the result is then the pair
+        (rows, LayerNorm(rows) in the 16-bit operand type, or None where the last GEMM could not produce it in the same kernel)."""
         h = x_bf16
         for i, layer in enumerate(self.layers):
             last = i == self.num_layers - 1
             last_act = ops.ACT_SIGMOID if self.sigmoid_output else ops.ACT_NONE
+            if (last and ln is not None and residual is not None and out_dtype == F32 and last_act == ops.ACT_NONE
+                    and _gemm_ln_dispatched(layer.out_features, layer.in_features)):
+                return ops.gemm_residual_layernorm(h, w_bf16(self._wc, f"w{i}", layer.weight), v_f32(self._wc, f"b{i}", layer.bias), residual, *ln)
             h = ops.gemm(h, w_bf16(self._wc, f"w{i}", layer.weight), v_f32(self._wc, f"b{i}", layer.bias),
                          act=last_act if last else self._act_code, residual=residual if last else None,
                          out_dtype=out_dtype if last else OP16)
-        return h
+        return h if ln is None else (h, None)
 
     def run_tokens(self, x: torch.Tensor) -> torch.Tensor:
         """fp32 [rows, in] (a few rows: decoder tokens) -> fp32 [rows, out].  A 3-layer ReLU MLP of width 256 runs as ONE launch
@@ -209,18 +223,23 @@ class MultiScaleBlock(nn.Module):
         return (D, Dp, wc.get("qkvw_p", [a.qkv.weight], qkv_w), wc.get("qkvb_p", [a.qkv.bias], qkv_b),
                 wc.get("ow_p", [a.proj.weight], proj_w))
 
-    def run(self, t: torch.Tensor, B: int, H: int, W: int, emit16: bool = False, fused_qkv_attn: bool = False) -> Tuple[torch.Tensor, int, int]:
+    def run(self, t: torch.Tensor, B: int, H: int, W: int, emit16: bool = False, fused_qkv_attn: bool = False, fused_gemm_ln: bool = False,
+            xn: Optional[torch.Tensor] = None, next_norm=None) -> Tuple[torch.Tensor, int, int]:
         """fp32 tokens [B*H*W, dim] -> (fp32 tokens [B*H'*W', dim_out], H', W').  emit16 (a stage's last block): `self.out16` also holds the
         result in the 16-bit operand type when the block's last kernel could write it in the same store (else None).  fused_qkv_attn (the
         inference trunk asks for it; the training forward does not, its backward recomputes the block from the q | k | v map of the GEMM
-        path and must see the same bits): where the kernel is built, the qkv projection runs inside the window-attention kernel."""
-        self.out16 = None
+        path and must see the same bits): where the kernel is built, the qkv projection runs inside the window-attention kernel.
+        fused_gemm_ln (the inference trunk only, as fused_qkv_attn): the proj GEMM also writes norm2's rows, and fc2 the rows of next_norm =
+        (weight, bias, eps), the next block's norm1 -- left in `self.next_xn` (None where fc2 could not) for the caller to hand to that block
+        as `xn`, the rows this block's own norm1 would compute from t."""
+        self.out16 = self.next_xn = None
         wc, a = self._wc, self.attn
         heads, dim_out = a.num_heads, self.dim_out
         D, Dp, qkv_w, qkv_b, proj_w = self._packed_attn_weights()
         width = heads * Dp                      # per-token width of each of q, k, v in the (possibly padded) layout
         scale = 1.0 / (D ** 0.5)
-        xn = ops.layernorm(t, v_f32(wc, "n1w", self.norm1.weight), v_f32(wc, "n1b", self.norm1.bias), 1e-6)
+        if xn is None:
+            xn = ops.layernorm(t, v_f32(wc, "n1w", self.norm1.weight), v_f32(wc, "n1b", self.norm1.bias), 1e-6)
         pool = self.q_stride is not None
         if self.dim != dim_out:
             if _POOL_GEMM and pool and B * H * W >= 256 and H % 2 == 0 and W % 2 == 0:   # projection + 2x2 max-pool in one GEMM
@@ -249,10 +268,16 @@ class MultiScaleBlock(nn.Module):
                 q = (qp.view(B, Hq * Wq, heads, Dp) if pool else v5[:, :, 0]).permute(0, 2, 1, 3)
                 o = ops.attention(q, v5[:, :, 1].permute(0, 2, 1, 3), v5[:, :, 2].permute(0, 2, 1, 3), scale=scale)
                 o = o.permute(0, 2, 1, 3).reshape(B * Hq * Wq, width)
-        t = ops.gemm(o, proj_w, v_f32(wc, "ob", a.proj.bias), residual=shortcut, out_dtype=F32)
         mlp = self.mlp
-        if (_FUSED_MLP and ops.ln_mlp_residual_supported(dim_out) and mlp.num_layers == 2 and mlp._act_code == ops.ACT_GELU
-                and mlp.layers[0].out_features == 4 * dim_out and Hq * Wq >= 1024):
+        one_kernel_mlp = (_FUSED_MLP and ops.ln_mlp_residual_supported(dim_out) and mlp.num_layers == 2 and mlp._act_code == ops.ACT_GELU
+                          and mlp.layers[0].out_features == 4 * dim_out and Hq * Wq >= 1024)
+        xn2 = None
+        if fused_gemm_ln and not one_kernel_mlp and _gemm_ln_dispatched(dim_out, width):   # the proj GEMM writes norm2's rows as well
+            t, xn2 = ops.gemm_residual_layernorm(o, proj_w, v_f32(wc, "ob", a.proj.bias), shortcut,
+                                                 v_f32(wc, "n2w", self.norm2.weight), v_f32(wc, "n2b", self.norm2.bias), 1e-6)
+        else:
+            t = ops.gemm(o, proj_w, v_f32(wc, "ob", a.proj.bias), residual=shortcut, out_dtype=F32)
+        if one_kernel_mlp:
             # the two high-resolution stages: LayerNorm + fc1 + GELU + fc2 + residual as one kernel, the hidden map stays in registers
             # (the gate looks at the tokens PER SLICE, never at the batch: a slice's features must not depend on its batch mates)
             w2p = mlp._wc.get("w1p", [mlp.layers[1].weight], lambda: ops.mlp_fused_permute_w2(mlp.layers[1].weight.detach().to(OP16).contiguous()))
@@ -262,8 +287,12 @@ class MultiScaleBlock(nn.Module):
             if emit16:
                 t, self.out16 = t
             return t, Hq, Wq
-        xn2 = ops.layernorm(t, v_f32(wc, "n2w", self.norm2.weight), v_f32(wc, "n2b", self.norm2.bias), 1e-6)
-        t = self.mlp.run(xn2, residual=t, out_dtype=F32)
+        if xn2 is None:
+            xn2 = ops.layernorm(t, v_f32(wc, "n2w", self.norm2.weight), v_f32(wc, "n2b", self.norm2.bias), 1e-6)
+        if fused_gemm_ln and next_norm is not None:   # fc2 writes the next block's norm1 rows as well, where that form is dispatched
+            t, self.next_xn = mlp.run(xn2, residual=t, out_dtype=F32, ln=next_norm)
+        else:
+            t = mlp.run(xn2, residual=t, out_dtype=F32)
         return t, Hq, Wq
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -325,9 +354,14 @@ class Hiera(nn.Module):
         h = w = S // 4
         t = self.patch_embed.tokens(x, self._pos_tokens(h, w))
         outputs = []
+        fused = _TWO_LAUNCH == 0       # the inference trunk; the training forwards keep every launch their backward was validated against
+        xn = None                      # norm1 rows of the coming block, where the previous block's fc2 wrote them
         for i, blk in enumerate(self.blocks):
             is_out = i == self.stage_ends[-1] or (i in self.stage_ends and self.return_interm_layers)
-            t, h, w = blk.run(t, B, h, w, emit16=is_out, fused_qkv_attn=_TWO_LAUNCH == 0)
+            nb = self.blocks[i + 1] if i + 1 < len(self.blocks) else None
+            next_norm = (v_f32(nb._wc, "n1w", nb.norm1.weight), v_f32(nb._wc, "n1b", nb.norm1.bias), 1e-6) if fused and nb is not None and nb.dim == blk.dim_out else None
+            t, h, w = blk.run(t, B, h, w, emit16=is_out, fused_qkv_attn=fused, fused_gemm_ln=fused, xn=xn, next_norm=next_norm)
+            xn, blk.next_xn = blk.next_xn, None
             if is_out:
                 v = nchw_view(t, B, h, w)
                 # the 16-bit token-major copy the block's last kernel wrote beside the fp32 rows (stages 1 / 2): FpnNeck takes it as its lateral

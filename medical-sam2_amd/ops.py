@@ -152,6 +152,36 @@ def layernorm_dual(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ep
     return y.reshape(x.shape), y16.reshape(x.shape)
 
 
+def gemm_residual_layernorm_supported(N: int, K: int) -> bool:
+    """True when `gemm_residual_layernorm` is built for this output width and reduction length (per-slice quantities only)."""
+    return bool(lib().msam2_gemm_residual_layernorm_supported(N, K))
+
+
+def gemm_residual_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], residual: torch.Tensor, ln_w: torch.Tensor,
+                            ln_b: torch.Tensor, eps: float, *, out: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None):
+    """(c32, y16) = (a @ w^T + bias + residual in fp32, LayerNorm(c32 rows) in the 16-bit operand type) from one kernel: the bits of
+    `gemm(a, w, bias, residual=residual, out_dtype=F32)` and of `layernorm(c32, ln_w, ln_b, eps)`.  a [M, K], w [N, K] 16-bit, residual fp32
+    [M, N].  A form that is not built (`gemm_residual_layernorm_supported`) is an error."""
+    _req(a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1], f"gemm_residual_layernorm shapes {tuple(a.shape)} x {tuple(w.shape)}")
+    _req(a.dtype == OP16 and w.dtype == OP16 and a.stride(1) == 1 and w.stride(1) == 1, "gemm_residual_layernorm operands: 16-bit, K-contiguous")
+    M, K = a.shape
+    N = w.shape[0]
+    _req(gemm_residual_layernorm_supported(N, K), f"gemm_residual_layernorm: N = {N}, K = {K} is not built (N = 384, K % 64 == 0)")
+    _req(residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1, "gemm_residual_layernorm: residual must be fp32 [M, N]")
+    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
+         and (bias is None or (bias.dtype == F32 and bias.numel() == N and bias.is_contiguous())),
+         "gemm_residual_layernorm: bias, ln_w, ln_b are fp32 [N]")
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=a.device)
+    if out16 is None:
+        out16 = torch.empty(M, N, dtype=OP16, device=a.device)
+    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
+         "gemm_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    check(lib().msam2_gemm_residual_layernorm(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(residual), residual.stride(0), _p(out),
+                                              out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16), out16.stride(0), M, N, K, _stream()))
+    return out, out16
+
+
 def ln_mlp_residual_supported(dim: int) -> bool:
     return bool(lib().msam2_ln_mlp_residual_supported(dim))
 
