@@ -22,6 +22,23 @@
 // common.h's DmaImage: a row is 12 / 24 chunks long and the swizzle permutes inside groups of 4 / 8 of them.
 #include "common.h"
 
+// Lanes l and l + 32 trade one op16x4 each: given a (the lower half keeps it) and b (the upper half keeps it), lanes 0-31 return
+// (own a, partner's a), lanes 32-63 (partner's b, own b).  v_permlane32_swap exchanges the first operand's upper-half lanes with the
+// second's lower-half lanes.
+__device__ __forceinline__ op16x8 half_trade(op16x4 a, op16x4 b) {
+  typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+  u32x2 ua = __builtin_bit_cast(u32x2, a), ub = __builtin_bit_cast(u32x2, b);
+  typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+  u32x4 r;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(ua[i], ub[i], false, false);
+    r[i] = sw[0];
+    r[2 + i] = sw[1];
+  }
+  return __builtin_bit_cast(op16x8, r);
+}
+
 struct MlpFusedParams {
   const float* x;        // [T, DIM] fp32 residual stream
   float* out;            // [T, DIM]
@@ -31,12 +48,29 @@ struct MlpFusedParams {
   int64_t T;
   float eps;
   op16* out16;           // optional second output: the same rows in the 16-bit operand type (a stage's last block: the FPN's lateral GEMM operand)
+  // PROJ form only (the attention's output projection in front, x = the projection's residual):
+  const op16* o;         // [T, DIM] attention output
+  const op16* wp;        // [DIM, DIM] proj weight (nn.Linear layout)
+  const float* bp;
+  const float *nln_w, *nln_b;   // optional third output: LayerNorm(out rows; nln_w, nln_b, neps) in the 16-bit operand type (the next block's norm1)
+  float neps;
+  op16* xn16;
 };
 
 // NWV waves per workgroup (4 or 8).  With 8 (round 4) the workgroup still owns ONE weight ring in LDS, a wave carries TB = half as many
 // token blocks, and every SIMD holds two waves: one wave's GELU / LayerNorm vector work and LDS reads run under the other's MFMAs, and a
 // wave's registers (<= 256) no longer spill (the 4-wave form at dim 192 spilled 21-35 registers of a 512-register budget).
-template <int DIM, int HC, int TB, int OCC = 1, int NWV = 4>
+//
+// PROJ: the block's attention output projection runs in front, x1 = res + o Wp^T + bp never exists in memory.  The fc2
+// accumulator accy is initialised with res + bp and takes Wp o^T as DB * KS1 more MFMAs (A = Wp rows, B = the token's o row, one 16-byte
+// load per k-step); LayerNorm then runs on accy, whose registers, rounded, ARE fc1's B operand -- in the accumulator's channel order, so
+// W1 comes with its input dimension permuted like W2's hidden one (msam2_mlp_fused_permute_w1).  The fc1 / GELU / fc2 loop is the same
+// and accumulates onto x1; the store adds b2 and re-reads nothing (in place is fine).  Wp: resident form (dim 96, LDS full) -- fragments
+// straight from global memory, 18 KB that stay in L1 / L2; streaming form (dim 192) -- Wp is exactly one ring slot (72 KB), one more ring
+// step at the head of every pass.  Optionally the store also writes LayerNorm(out rows) for the next block's norm1.  SIDE (PROJ only):
+// which 16-bit side outputs the store writes, bit 0 out16, bit 1 xn16 -- compile-time, so that the store is one straight run of
+// instructions (as run-time tests every store sat in a basic block of its own).
+template <int DIM, int HC, int TB, int OCC = 1, int NWV = 4, bool PROJ = false, int SIDE = 0>
 __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int HID = 4 * DIM, NCH = HID / HC, KS1 = DIM / 16, DB = DIM / 32, HB = HC / 32;
@@ -45,9 +79,10 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
   constexpr int W1B = HC * RB1, W2B = DIM * RB2, BUF = W1B + W2B;
   constexpr int PIECES1 = W1B / 1024, PIECES2 = W2B / 1024, PW1 = (PIECES1 + NWV - 1) / NWV, PW2 = (PIECES2 + NWV - 1) / NWV;
   static_assert((RB1 == 192 || RB1 == 384) && (RB2 == 192 || RB2 == 384), "row swizzles are built for 192 / 384-byte rows");
-  static_assert(2 * BUF + (3 * DIM + HID) * 4 <= 160 * 1024, "LDS budget");   // (pieces are dealt j * NWV + wave: a last, partial round is guarded)
+  static_assert(2 * BUF + (3 * DIM + HID + (PROJ ? 3 * DIM : 0)) * 4 <= 160 * 1024, "LDS budget");   // (pieces are dealt j * NWV + wave: a last, partial round is guarded)
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-  float* prm = reinterpret_cast<float*>(smem + 2 * BUF);     // [gamma DIM | beta DIM | b2 DIM | b1 HID]
+  float* prm = reinterpret_cast<float*>(smem + 2 * BUF);     // [gamma DIM | beta DIM | b2 DIM | b1 HID], PROJ: [| bp DIM | next gamma DIM | next beta DIM]
+  constexpr int PRM_BP = 3 * DIM + HID, PRM_NG = PRM_BP + DIM, PRM_NB = PRM_NG + DIM;
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -58,6 +93,14 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
     prm[2 * DIM + i] = p.b2[i];
   }
   for (int i = tid; i < HID; i += NWV * 64) prm[3 * DIM + i] = p.b1[i];
+  if constexpr (PROJ)
+    for (int i = tid; i < DIM; i += NWV * 64) {
+      prm[PRM_BP + i] = p.bp[i];
+      if constexpr (SIDE & 2) {
+        prm[PRM_NG + i] = p.nln_w[i];
+        prm[PRM_NB + i] = p.nln_b[i];
+      }
+    }
 
   // ---- weight stream: per-lane source offsets of this wave's DMA pieces (chunk-independent part), scalar chunk offset added per issue
   const auto w1_rsrc = raw_rsrc(p.w1, HID * DIM * 2);
@@ -90,21 +133,134 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
   const int64_t pass_tokens = NWV * 32 * TB;
   const int64_t n_pass = (p.T + pass_tokens - 1) / pass_tokens;
   int64_t g_chunk = 0;                                       // running chunk count of this workgroup (buffer = parity)
+  constexpr bool RING_WP = PROJ && !((NCH == 2) && NWV == 8);   // streaming PROJ form: Wp is a ring step of its own in front of chunk 0
+  // Wp [DIM][DIM] as a ring step: rows of RB1 bytes like a W1 chunk's, two W1-chunk-shaped halves of HC rows with the same lane offsets
+  // (HC rows further down the row swizzle repeats), filling the slot exactly
+  auto issue_wp = [&](int buf) {
+    if constexpr (RING_WP) {
+      static_assert(2 * HC == DIM && W1B == W2B && RB1 == 384 && (HC / 2) % 8 == 0, "Wp = one ring slot, swizzle period divides HC");
+      const auto wp_rsrc = raw_rsrc(p.wp, DIM * DIM * 2);
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int j = 0; j < PW1; ++j)
+          if (j * NWV + wave < PIECES1)
+            glds16(wp_rsrc, smem + buf * BUF + half * W1B + (j * NWV + wave) * 1024, off1[j], (unsigned)(half * W1B));
+    }
+  };
   // RESIDENT (two chunks = the whole of W1 and W2 fit the two ring buffers: dim 96): both chunks are loaded ONCE and stay; the pass loop
   // then has no DMA, no wait and no barrier, so the 8 waves drift apart and one wave's LayerNorm prologue / store epilogue runs under the
   // others' MFMAs (round 4).  Otherwise the ring streams chunk c + 1 under chunk c, one barrier per chunk.
   constexpr bool RESIDENT = (NCH == 2) && NWV == 8;
   if ((int64_t)blockIdx.x < n_pass) {
-    issue(0, 0);
+    if constexpr (RING_WP) issue_wp(0);
+    else issue(0, 0);
     if constexpr (RESIDENT) issue(1, 1);
   }
   if constexpr (RESIDENT) wait_vmcnt<0>();
   __syncthreads();                                           // parameters visible (streaming form: the DMA is waited for inside the loop)
 
   for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-    // ---- this wave's TB token blocks: LayerNorm -> 16-bit B fragments
     op16x8 xf[TB][KS1];
     int64_t tok[TB];
+    f32x16 accy[TB][DB];
+    if constexpr (PROJ) {
+      // ---- x1 = res + bp + Wp o^T in accy: row loads first (res in the accumulator's channel order, o in the operand's)
+      op16x8 of[TB][KS1];
+#pragma unroll
+      for (int tb = 0; tb < TB; ++tb) {
+        const int64_t t = pass * pass_tokens + (int64_t)(wave * TB + tb) * 32 + r;
+        tok[tb] = t;
+        const int64_t tc = t < p.T ? t : p.T - 1;
+        const float* xr = p.x + tc * DIM;
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xr + d * 32 + 8 * g + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) accy[tb][d][4 * g + e] = v[e];
+          }
+#pragma unroll
+        for (int k = 0; k < KS1; ++k) of[tb][k] = *reinterpret_cast<const op16x8*>(p.o + tc * DIM + 16 * k + 8 * h);
+      }
+      const unsigned char* wps = smem;
+      if constexpr (RING_WP) {
+        const int buf = (int)(g_chunk & 1);
+        wait_vmcnt<0>();     // this wave's pieces of Wp (and its rows) have landed
+        __builtin_amdgcn_s_barrier();                        // ... every wave's; the other buffer is no longer read
+        issue(0, buf ^ 1);
+        wps = smem + buf * BUF;
+        ++g_chunk;
+      }
+      // Wp fragments of d-block d + 1 are requested before the MFMAs of d-block d and no further ahead (all DB * KS1 at once, as the
+      // compiler would have them, is 72 registers beside accy's 96 and o's 48)
+      auto load_ap = [&](op16x8 (&ap)[KS1], int d) {
+        const int rowp = d * 32 + r;
+#pragma unroll
+        for (int k = 0; k < KS1; ++k) {
+          if constexpr (RING_WP) ap[k] = *reinterpret_cast<const op16x8*>(wps + rowp * RB1 + (mlp_swz<RB1>(2 * k + h, rowp) << 4));
+          else ap[k] = *reinterpret_cast<const op16x8*>(p.wp + rowp * DIM + 16 * k + 8 * h);
+        }
+      };
+      op16x8 ap[2][KS1];
+      load_ap(ap[0], 0);
+#pragma unroll
+      for (int d = 0; d < DB; ++d) {
+        if (d + 1 < DB) load_ap(ap[(d + 1) & 1], d + 1);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 bv = *reinterpret_cast<const f32x4*>(prm + PRM_BP + d * 32 + 8 * g + 4 * h);
+#pragma unroll
+          for (int tb = 0; tb < TB; ++tb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) accy[tb][d][4 * g + e] += bv[e];
+        }
+#pragma unroll
+        for (int tb = 0; tb < TB; ++tb)
+#pragma unroll
+          for (int k = 0; k < KS1; ++k) accy[tb][d] = MSAM2_MFMA_32x32x16(ap[d & 1][k], of[tb][k], accy[tb][d], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // ---- LayerNorm on accy (the lane's half row + one cross-half add, two passes); registers 0-7 / 8-15 of d-block d, rounded, are
+      // k-steps 2d / 2d + 1 of fc1's B operand (W1's input index is permuted to this order)
+#pragma unroll
+      for (int tb = 0; tb < TB; ++tb) {
+        // two independent chains (registers 0-7 / 8-15: the even / odd k-steps the rows become), then one add.  (The order is not free
+        // to change: tests/test_amg_gpu.py has two cases that sit ON a discrete decision -- a prompt set with stability 3137 / 3201 =
+        // 0.98001 against the threshold 0.98, and an NMS that keeps 3 of ~210 masks against a bar of 3 -- and one chain moves the first,
+        // four chains the second)
+        float s2[2] = {0.f, 0.f}, q2h[2] = {0.f, 0.f};
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) s2[e >> 3] += accy[tb][d][e];
+        float s = s2[0] + s2[1];
+        s += __shfl_xor(s, 32, 64);
+        const float mean = s * (1.f / DIM);
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const float dlt = accy[tb][d][e] - mean;
+            q2h[e >> 3] += dlt * dlt;
+          }
+        float q2 = q2h[0] + q2h[1];
+        q2 += __shfl_xor(q2, 32, 64);
+        const float rstd = 1.0f / sqrtf(q2 * (1.f / DIM) + p.eps);
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const f32x4 gm = *reinterpret_cast<const f32x4*>(prm + d * 32 + 8 * g + 4 * h);
+            const f32x4 bt = *reinterpret_cast<const f32x4*>(prm + DIM + d * 32 + 8 * g + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              xf[tb][2 * d + (g >> 1)][4 * (g & 1) + e] = f2op((accy[tb][d][4 * g + e] - mean) * rstd * gm[e] + bt[e]);
+          }
+      }
+    } else {
+    // ---- this wave's TB token blocks: LayerNorm -> 16-bit B fragments
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb) {
       const int64_t t = pass * pass_tokens + (int64_t)(wave * TB + tb) * 32 + r;
@@ -146,13 +302,14 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
         xf[tb][k] = f;
       }
     }
-    f32x16 accy[TB][DB];
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb)
 #pragma unroll
       for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int e = 0; e < 16; ++e) accy[tb][d][e] = 0.f;
+
+    }
 
     for (int chunk = 0; chunk < NCH; ++chunk, ++g_chunk) {
       const int buf = RESIDENT ? chunk : (int)(g_chunk & 1);
@@ -161,7 +318,10 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
         __builtin_amdgcn_s_barrier();                        // ... every wave's; the other buffer is no longer read
         const bool more_here = chunk + 1 < NCH;
         const bool more = more_here || (pass + gridDim.x < n_pass);
-        if (more) issue(more_here ? chunk + 1 : 0, buf ^ 1);
+        if (more) {
+          if (RING_WP && !more_here) issue_wp(buf ^ 1);
+          else issue(more_here ? chunk + 1 : 0, buf ^ 1);
+        }
       }
       const unsigned char* w1s = smem + buf * BUF;
       const unsigned char* w2s = w1s + W1B;
@@ -207,6 +367,84 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
         }
       }
     }
+    if constexpr (PROJ) {
+      // ---- epilogue: + b2, fp32 store of the lane's half row from accy (x1 is in it: nothing is re-read); optionally the rows' 16-bit
+      // rounding and their LayerNorm with the next block's norm1 parameters (statistics as above, every lane takes part in the adds)
+#pragma unroll
+      for (int tb = 0; tb < TB; ++tb) {
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(prm + 2 * DIM + d * 32 + 8 * g + 4 * h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              accy[tb][d][4 * g + e] += bv[e];
+              s += accy[tb][d][4 * g + e];
+            }
+          }
+        float mean = 0.f, rstd = 0.f;
+        if constexpr (SIDE & 2) {
+          s += __shfl_xor(s, 32, 64);
+          mean = s * (1.f / DIM);
+          float q2 = 0.f;
+#pragma unroll
+          for (int d = 0; d < DB; ++d)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+              const float dlt = accy[tb][d][e] - mean;
+              q2 += dlt * dlt;
+            }
+          q2 += __shfl_xor(q2, 32, 64);
+          rstd = 1.0f / sqrtf(q2 * (1.f / DIM) + p.neps);
+        }
+        if (tok[tb] < p.T) {
+          float* yr = p.out + tok[tb] * DIM;
+#pragma unroll
+          for (int d = 0; d < DB; ++d) {
+            if constexpr (SIDE & 2) __builtin_amdgcn_sched_barrier(0);   // one d-block's LayerNorm parameters at a time (all DB at once spill)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const int ch = d * 32 + 8 * g + 4 * h;
+              f32x4 o;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) o[e] = accy[tb][d][4 * g + e];
+              *reinterpret_cast<f32x4*>(yr + ch) = o;
+            }
+            // 16-bit side outputs: a lane's 4 channels of register group g and the other half's 4 are adjacent in the row, so the halves
+            // trade (the lower keeps even g, the upper odd g) and every lane stores 8 channels = 16 bytes: half as many scattered stores
+            if constexpr (SIDE != 0) {
+#pragma unroll
+              for (int m = 0; m < 2; ++m) {
+                op16x4 lo[2], hi[2];                            // [output: 0 out16, 1 xn16], register groups 2m and 2m + 1
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                  const int g = 2 * m + q, ch = d * 32 + 8 * g + 4 * h;
+                  f32x4 gm = {0.f, 0.f, 0.f, 0.f}, bt = gm;
+                  if constexpr (SIDE & 2) {
+                    gm = *reinterpret_cast<const f32x4*>(prm + PRM_NG + ch);
+                    bt = *reinterpret_cast<const f32x4*>(prm + PRM_NB + ch);
+                  }
+                  op16x4 v16, n16;
+#pragma unroll
+                  for (int e = 0; e < 4; ++e) {
+                    const float o = accy[tb][d][4 * g + e];
+                    v16[e] = f2op(o);
+                    n16[e] = f2op((o - mean) * rstd * gm[e] + bt[e]);
+                  }
+                  (q ? hi : lo)[0] = v16;
+                  (q ? hi : lo)[1] = n16;
+                }
+                const int64_t at = tok[tb] * DIM + d * 32 + 16 * m + 8 * h;
+                if constexpr (SIDE & 1) *reinterpret_cast<op16x8*>(p.out16 + at) = half_trade(lo[0], hi[0]);
+                if constexpr (SIDE & 2) *reinterpret_cast<op16x8*>(p.xn16 + at) = half_trade(lo[1], hi[1]);
+              }
+            }
+          }
+        }
+      }
+    } else {
     // ---- epilogue: + b2 + residual, fp32 store (a lane owns a token; 4 consecutive channels per register group)
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb) {
@@ -244,6 +482,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void mlp_fused_kernel(MlpFusedParams
             }
         }
       }
+    }
     }
   }
 #endif
@@ -641,4 +880,55 @@ extern "C" int msam2_ln_mlp_residual_fwd_dual(const float* x, int64_t T, int64_t
                                               void* stream) {
   MSAM2_REQUIRE(out16, "ln_mlp_residual_dual: null 16-bit output");
   return ln_mlp_residual_launch(x, T, dim, ln_w, ln_b, eps, w1, b1, w2p, b2, out, out16, stream);
+}
+
+// ---- PROJ form: the attention's output projection in front of the MLP, the next block's norm1 behind it
+// 1 when msam2_proj_ln_mlp_residual_fwd is built for this width (the proj is square: width == dim): 96 / 192.
+extern "C" int msam2_proj_ln_mlp_residual_supported(int64_t dim) { return dim == 96 || dim == 192; }
+
+// W1 [hidden, dim] with its INPUT index permuted inside every 32-block to the accumulator's register order (position 16 s + 8 h + j holds
+// channel 16 s + 8 (j >> 2) + 4 h + (j & 3)): the permutation mlp_fused_permute_kernel applies to W2's hidden index, rows and columns swapped
+extern "C" int msam2_mlp_fused_permute_w1(const void* w1, void* w1p, int64_t hidden, int64_t dim, void* stream) {
+  MSAM2_REQUIRE(w1 && w1p && hidden > 0 && dim > 0 && dim % 32 == 0, "mlp_fused_permute_w1: bad arguments");
+  hipLaunchKernelGGL(mlp_fused_permute_kernel, dim3((unsigned)min((int64_t)1024, cdiv(dim * hidden, 256))), dim3(256), 0, (hipStream_t)stream,
+                     (const op16*)w1, (op16*)w1p, (int)hidden, (int)dim);
+  return msam2_check_launch("mlp_fused_permute_w1");
+}
+
+template <int DIM, int HC, int TB, int SIDE>
+static int launch_proj_mlp_fused_side(const MlpFusedParams& p, hipStream_t s) {
+  constexpr int LDS = 2 * (2 * HC * DIM * 2) + (3 * DIM + 4 * DIM + 3 * DIM) * 4;
+  ensure_dyn_lds<mlp_fused_kernel<DIM, HC, TB, 1, 8, true, SIDE>>(LDS);
+  const int64_t n_pass = (p.T + 8 * 32 * TB - 1) / (8 * 32 * TB);
+  hipLaunchKernelGGL((mlp_fused_kernel<DIM, HC, TB, 1, 8, true, SIDE>), dim3((unsigned)min((int64_t)256, n_pass)), dim3(512), LDS, s, p);
+  return msam2_check_launch("proj_ln_mlp_residual_fwd");
+}
+
+template <int DIM, int HC, int TB>
+static int launch_proj_mlp_fused(const MlpFusedParams& p, hipStream_t s) {
+  switch ((p.out16 ? 1 : 0) | (p.xn16 ? 2 : 0)) {
+    case 0: return launch_proj_mlp_fused_side<DIM, HC, TB, 0>(p, s);
+    case 1: return launch_proj_mlp_fused_side<DIM, HC, TB, 1>(p, s);
+    case 2: return launch_proj_mlp_fused_side<DIM, HC, TB, 2>(p, s);
+    default: return launch_proj_mlp_fused_side<DIM, HC, TB, 3>(p, s);
+  }
+}
+
+// out[T, dim] (fp32) = x1 + fc2(GELU(fc1(LayerNorm(x1; ln_w, ln_b, eps)))) with x1 = res + o wp^T + bp, which is never written.  o 16-bit [T, dim],
+// wp 16-bit [dim, dim], res fp32 [T, dim] (out == res is allowed), w1p from msam2_mlp_fused_permute_w1, w2p from msam2_mlp_fused_permute_w2.
+// Optional: out16 [T, dim] = out rounded to the 16-bit operand type; xn16 [T, dim] = LayerNorm(out rows; nln_w, nln_b, neps) in that type.
+extern "C" int msam2_proj_ln_mlp_residual_fwd(const void* o, const void* wp, const float* bp, const float* res, int64_t T, int64_t dim,
+                                              const float* ln_w, const float* ln_b, float eps, const void* w1p, const float* b1, const void* w2p,
+                                              const float* b2, float* out, void* out16, const float* nln_w, const float* nln_b, float neps,
+                                              void* xn16, void* stream) {
+  MSAM2_REQUIRE(o && wp && bp && res && out && ln_w && ln_b && w1p && b1 && w2p && b2 && T > 0, "proj_ln_mlp_residual: null tensor / empty problem");
+  MSAM2_REQUIRE(msam2_proj_ln_mlp_residual_supported(dim), "proj_ln_mlp_residual: dim %lld not built (96 / 192)", (long long)dim);
+  MSAM2_REQUIRE(!xn16 || (nln_w && nln_b), "proj_ln_mlp_residual: the LayerNorm output needs its parameters");
+  MSAM2_REQUIRE((((uintptr_t)o | (uintptr_t)wp | (uintptr_t)bp | (uintptr_t)res | (uintptr_t)out | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)ln_w |
+                  (uintptr_t)ln_b | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)nln_w | (uintptr_t)nln_b) & 15) == 0 &&
+                    (((uintptr_t)out16 | (uintptr_t)xn16) & 15) == 0, "proj_ln_mlp_residual: 16-byte aligned tensors");
+  MlpFusedParams p = {res, out, ln_w, ln_b, b1, b2, (const op16*)w1p, (const op16*)w2p, T, eps, (op16*)out16,
+                      (const op16*)o, (const op16*)wp, bp, nln_w, nln_b, neps, (op16*)xn16};
+  if (dim == 96) return launch_proj_mlp_fused<96, 192, 2>(p, (hipStream_t)stream);
+  return launch_proj_mlp_fused<192, 96, 1>(p, (hipStream_t)stream);
 }

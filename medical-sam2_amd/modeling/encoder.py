@@ -27,6 +27,13 @@ _FUSED_GEMM_LN = _os.environ.get("MSAM2_NO_FUSED_GEMM_LN") is None   # A/B switc
 # per-shape switch of that fusion: the reduction lengths that are dispatched (384: the proj GEMM of a stage-3 block, 1536: its fc2).  A shape
 # that does not beat its two launches inside the step is taken off this list and stays in the library
 _FUSED_GEMM_LN_K = frozenset(int(k) for k in _os.environ.get("MSAM2_FUSED_GEMM_LN_K", "384,1536").split(",") if k.strip())
+# A/B switch: the proj GEMM, the one-kernel MLP and the next block's norm1 of a stage 1-2 block as the launches they were
+_FUSED_PROJ_MLP = _os.environ.get("MSAM2_NO_FUSED_PROJ_MLP") is None
+# per-shape switches of that fusion: the widths at which the proj GEMM is folded into the MLP kernel, and those at which that kernel also
+# writes the next block's norm1 rows.  A shape that does not beat its launches inside the step is taken off its list: the
+# norm1 rows tie with their LayerNorm launch at width 96 and lose 16 us to it at 192, so that list is empty and the form stays in the library
+_FUSED_PROJ_MLP_DIMS = frozenset(int(k) for k in _os.environ.get("MSAM2_FUSED_PROJ_MLP_DIMS", "96,192").split(",") if k.strip())
+_FUSED_PROJ_MLP_NEXT_LN_DIMS = frozenset(int(k) for k in _os.environ.get("MSAM2_FUSED_PROJ_MLP_NEXT_LN_DIMS", "").split(",") if k.strip())
 _TWO_LAUNCH = 0   # depth of two_launch_qkv_attention()
 
 
@@ -48,6 +55,11 @@ class two_launch_qkv_attention:
 def _gemm_ln_dispatched(N: int, K: int) -> bool:
     """Does a residual GEMM [*, K] -> [*, N] that was handed a LayerNorm run both as one kernel?  (per-slice quantities only, never B)"""
     return _FUSED_GEMM_LN and K in _FUSED_GEMM_LN_K and ops.gemm_residual_layernorm_supported(N, K)
+
+
+def _proj_mlp_dispatched(dim_out: int, width: int) -> bool:
+    """Does a block whose MLP runs as one kernel take its proj GEMM into that kernel?  (per-slice quantities only, never B)"""
+    return _FUSED_PROJ_MLP and width == dim_out and dim_out in _FUSED_PROJ_MLP_DIMS and ops.proj_ln_mlp_residual_supported(dim_out)
 
 
 def frozen_forward_image(model, imgs: torch.Tensor) -> dict:
@@ -231,7 +243,9 @@ class MultiScaleBlock(nn.Module):
         path and must see the same bits): where the kernel is built, the qkv projection runs inside the window-attention kernel.
         fused_gemm_ln (the inference trunk only, as fused_qkv_attn): the proj GEMM also writes norm2's rows, and fc2 the rows of next_norm =
         (weight, bias, eps), the next block's norm1 -- left in `self.next_xn` (None where fc2 could not) for the caller to hand to that block
-        as `xn`, the rows this block's own norm1 would compute from t."""
+        as `xn`, the rows this block's own norm1 would compute from t.  The same request lets a block whose MLP is one kernel (stages 1-2)
+        take the proj GEMM into it and write next_norm's rows from its store, where those forms are dispatched and the block's attention ran
+        as the one-kernel form of fused_qkv_attn."""
         self.out16 = self.next_xn = None
         wc, a = self._wc, self.attn
         heads, dim_out = a.num_heads, self.dim_out
@@ -252,8 +266,9 @@ class MultiScaleBlock(nn.Module):
             shortcut = t
         Hq, Wq = (H // 2, W // 2) if pool else (H, W)
         # (the gate looks at per-slice quantities only, never at B: a slice's features must not depend on its batch mates)
-        if (fused_qkv_attn and _FUSED_QKV_ATTN and self.window_size > 0 and Dp == D
-                and ops.window_qkv_attention_supported(self.dim, dim_out, heads, self.window_size, pool, H, W)):
+        attn_in_one_kernel = (fused_qkv_attn and _FUSED_QKV_ATTN and self.window_size > 0 and Dp == D
+                              and ops.window_qkv_attention_supported(self.dim, dim_out, heads, self.window_size, pool, H, W))
+        if attn_in_one_kernel:
             o = ops.window_qkv_attention(xn, qkv_w, qkv_b, B, H, W, heads, self.window_size, pool, scale)   # q | k | v stay in registers
         else:
             if _POOL_GEMM and _QPOOL_GEMM and pool and B * H * W >= 256 and H % 2 == 0 and W % 2 == 0 and width % 32 == 0:
@@ -271,6 +286,19 @@ class MultiScaleBlock(nn.Module):
         mlp = self.mlp
         one_kernel_mlp = (_FUSED_MLP and ops.ln_mlp_residual_supported(dim_out) and mlp.num_layers == 2 and mlp._act_code == ops.ACT_GELU
                           and mlp.layers[0].out_features == 4 * dim_out and Hq * Wq >= 1024)
+        if fused_gemm_ln and attn_in_one_kernel and one_kernel_mlp and _proj_mlp_dispatched(dim_out, width):
+            # x1 = shortcut + proj(o) stays in the MLP kernel's accumulator: no proj launch, no fp32 map written and read twice.  The proj
+            # sum is reordered, so only a block whose attention half already left the training forward's bits takes it (the stage 1-2
+            # blocks of the inference trunk): with the q | k | v fusion switched off the trunk still computes what the training forward does
+            w1p = mlp._wc.get("w0p", [mlp.layers[0].weight], lambda: ops.mlp_fused_permute_w1(mlp.layers[0].weight.detach().to(OP16).contiguous()))
+            w2p = mlp._wc.get("w1p", [mlp.layers[1].weight], lambda: ops.mlp_fused_permute_w2(mlp.layers[1].weight.detach().to(OP16).contiguous()))
+            next_ln = next_norm if next_norm is not None and dim_out in _FUSED_PROJ_MLP_NEXT_LN_DIMS else None
+            t, out16, self.next_xn = ops.proj_ln_mlp_residual(o, proj_w, v_f32(wc, "ob", a.proj.bias), shortcut, v_f32(wc, "n2w", self.norm2.weight),
+                                                              v_f32(wc, "n2b", self.norm2.bias), 1e-6, w1p, v_f32(mlp._wc, "b0", mlp.layers[0].bias),
+                                                              w2p, v_f32(mlp._wc, "b1", mlp.layers[1].bias), also16=emit16, next_ln=next_ln)
+            if emit16:
+                self.out16 = out16
+            return t, Hq, Wq
         xn2 = None
         if fused_gemm_ln and not one_kernel_mlp and _gemm_ln_dispatched(dim_out, width):   # the proj GEMM writes norm2's rows as well
             t, xn2 = ops.gemm_residual_layernorm(o, proj_w, v_f32(wc, "ob", a.proj.bias), shortcut,

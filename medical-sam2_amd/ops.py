@@ -212,6 +212,46 @@ def ln_mlp_residual(x: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps
     return out
 
 
+def proj_ln_mlp_residual_supported(dim: int) -> bool:
+    return bool(lib().msam2_proj_ln_mlp_residual_supported(dim))
+
+
+def mlp_fused_permute_w1(w1: torch.Tensor) -> torch.Tensor:
+    """kernel-ready copy of fc1's weight [hidden, dim] (16-bit) for proj_ln_mlp_residual: input index permuted per 32-block"""
+    _req(w1.dim() == 2 and w1.dtype == OP16 and w1.is_contiguous() and w1.shape[1] % 32 == 0, "mlp_fused_permute_w1: 16-bit [hidden, dim]")
+    out = torch.empty_like(w1)
+    check(lib().msam2_mlp_fused_permute_w1(_p(w1), _p(out), w1.shape[0], w1.shape[1], _stream()))
+    return out
+
+
+def mlp_fused_w1_order(dim: int) -> torch.Tensor:
+    """the permutation behind mlp_fused_permute_w1 / mlp_fused_permute_w2 (dim 96 / 192): index tensor `src` with permuted[..., i] = w[..., src[i]];
+    position 16 s + 8 h + j of every 32-block holds element 16 s + 8 (j >> 2) + 4 h + (j & 3)"""
+    i = torch.arange(dim)
+    q = i & 31
+    s, h, j = q >> 4, (q >> 3) & 1, q & 7
+    return (i & ~31) + 16 * s + 8 * (j >> 2) + 4 * h + (j & 3)
+
+
+def proj_ln_mlp_residual(o: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor, res: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float,
+                         w1p: torch.Tensor, b1: torch.Tensor, w2p: torch.Tensor, b2: torch.Tensor, also16: bool = False, next_ln=None):
+    """fp32 [T, dim] = x1 + fc2(GELU(fc1(LayerNorm(x1)))) with x1 = res + o wp^T + bp, one kernel, x1 never written (dim 96 / 192; w1p from
+    mlp_fused_permute_w1, w2p from mlp_fused_permute_w2).  Returns (out, out16 or None, xn16 or None): out16 = the rows in the 16-bit operand type
+    (also16), xn16 = LayerNorm(out rows; *next_ln) in that type (next_ln = (weight, bias, eps)) -- written by the same store."""
+    T, dim = res.shape
+    _req(res.dtype == F32 and res.is_contiguous() and o.dtype == OP16 and o.is_contiguous() and o.shape == (T, dim) and wp.dtype == OP16
+         and wp.is_contiguous() and wp.shape == (dim, dim), "proj_ln_mlp_residual: res fp32 [T, dim], o 16-bit [T, dim], wp 16-bit [dim, dim] contiguous")
+    _req(w1p.dtype == OP16 and w2p.dtype == OP16 and w1p.shape == (4 * dim, dim) and w2p.shape == (dim, 4 * dim) and w1p.is_contiguous()
+         and w2p.is_contiguous(), "proj_ln_mlp_residual: w1p [4 dim, dim], w2p [dim, 4 dim] 16-bit contiguous")
+    out = torch.empty_like(res)
+    out16 = torch.empty(res.shape, dtype=OP16, device=res.device) if also16 else None
+    xn16 = torch.empty(res.shape, dtype=OP16, device=res.device) if next_ln is not None else None
+    nw, nb, neps = next_ln if next_ln is not None else (None, None, 0.0)
+    check(lib().msam2_proj_ln_mlp_residual_fwd(_p(o), _p(wp), _p(bp), _p(res), T, dim, _p(ln_w), _p(ln_b), float(eps), _p(w1p), _p(b1), _p(w2p), _p(b2),
+                                               _p(out), _p(out16), _p(nw), _p(nb), float(neps), _p(xn16), _stream()))
+    return out, out16, xn16
+
+
 def _strides3(t: torch.Tensor) -> "ctypes.Array":
     return (ctypes.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))
 
