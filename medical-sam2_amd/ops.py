@@ -1039,6 +1039,51 @@ def label_pick(labels: torch.Tensor, ids, stats: torch.Tensor, rows: torch.Tenso
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# closing the loop: corrective clicks from the error regions of a prediction against the ground truth (csrc/clicks.hip)
+CLICK_MODES = {"center": 0, "uniform": 1}
+
+
+def label_error_clicks_workspace_bytes(D: int, H: int, W: int, n: int, mode: str = "center") -> int:
+    _req(mode in CLICK_MODES, f"label_error_clicks: mode {mode!r} (one of {tuple(CLICK_MODES)})")
+    return int(lib().msam2_label_error_clicks_workspace_bytes(D, H, W, n, CLICK_MODES[mode]))
+
+
+def label_error_clicks(pred: torch.Tensor, gt: torch.Tensor, ids, mode: str = "center", k: Optional[torch.Tensor] = None,
+                       u: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two uint8 [D, H, W] label volumes -> clicks int32 [D, n, 8] = (x, y, label, |FN|, |FP|, max d2(FN), max d2(FP), 0) per slice and object:
+    FN = {gt == ids[j] and pred != ids[j]}, FP = {pred == ids[j] and gt != ids[j]}, d2 = the squared distance to the nearest pixel outside the
+    region, the one-pixel frame around the image included.  mode="center": the voxel of largest d2 (ties to the smallest y * W + x) of the
+    region with the larger maximum, label 1 for FN (strictly larger), 0 for FP.  mode="uniform": the k-th voxel of FN | FP in raster order,
+    k int32 [D, n] or u uint32 [D, n] (int32 is taken as the same 32 bits; k = (u * count) >> 32), label 1 iff it is in FN; the d2 fields are
+    -1.  No error voxel: (-1, -1, -1, 0, 0, ...).  workspace: a contiguous 8-byte-aligned device tensor of at least
+    `label_error_clicks_workspace_bytes` bytes to reuse; out: the table to fill.  Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_error_clicks", pred, ids, max_voxels=True)
+    dev = pred.device
+    _device_table("label_error_clicks: gt", gt, torch.uint8, pred.shape, dev, "labels'")
+    _req(mode in CLICK_MODES, f"label_error_clicks: mode {mode!r} (one of {tuple(CLICK_MODES)})")
+    if mode == "center":
+        _req(k is None and u is None, "label_error_clicks: k and u belong to mode='uniform'")
+    else:
+        _req((k is None) != (u is None), "label_error_clicks: mode='uniform' needs exactly one of k and u")
+        if u is None:
+            _device_table("label_error_clicks: k", k, torch.int32, (D, n), dev, "labels'")
+        else:
+            _device_table("label_error_clicks: u", u, (torch.uint32, torch.int32), (D, n), dev, "labels'")
+    nb = lib().msam2_label_error_clicks_workspace_bytes(D, H, W, n, CLICK_MODES[mode])
+    if workspace is None:
+        workspace = _workspace8(nb, dev)
+    _req(isinstance(workspace, torch.Tensor) and workspace.is_contiguous() and workspace.device == dev
+         and workspace.numel() * workspace.element_size() >= nb and workspace.data_ptr() % 8 == 0,
+         f"label_error_clicks: workspace must be a contiguous 8-byte-aligned tensor of at least {nb} bytes on the labels' device")
+    if out is None:
+        out = torch.empty(D, n, 8, dtype=torch.int32, device=dev)
+    _device_table("label_error_clicks: out", out, torch.int32, (D, n, 8), dev, "labels'")
+    check(lib().msam2_label_error_clicks(_p(pred), _p(gt), _p(ids_d), _p(k), _p(u), D, H, W, n, CLICK_MODES[mode], _p(out), _p(workspace),
+                                         workspace.numel() * workspace.element_size(), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # in front of both: volume intake -- window, Pillow-exact resize, normalise; nearest resize of label maps (csrc/volume_prep.hip)
 PREP_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.float32: 2}
 LABEL_SOURCE_TYPES = {torch.uint8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3}

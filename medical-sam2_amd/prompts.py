@@ -11,6 +11,8 @@ caller wants host dictionaries.
 * `label_prompts`: device tensors for all slices and objects, no host sync.
 * `prompts_pack`: the dictionaries `BTCVVolumes.__getitem__` puts under "bbox", or under "pt" / "p_label".
 * `segment_prompts`: the `{slice: {...}}` prompts of `segment_volume` / `train_step_3d`; `targets_from_labels`: the latter's targets.
+* `corrective_clicks`: the next click per (slice, object) from the error regions of a prediction against the ground truth
+  (`ops.label_error_clicks`, csrc/clicks.hip); `worst_slices`: where an object's error is largest.  `interactive.refine_volume` drives them.
 
 Not reproduced: what `random_click` does with an empty mask (label 0 at a random background pixel: the dataset never calls it for an
 absent object, and `present` tells the caller), and overlapping object masks (a label volume has one value per voxel;
@@ -83,6 +85,64 @@ def label_prompts(labels: torch.Tensor, obj_ids: Sequence[int], prompt: str = "b
     present = stats[..., 0] > 0
     point_labels = torch.where(present, 1, -1).to(torch.int32).unsqueeze(-1)
     return xy.to(F32).unsqueeze(2), point_labels, present
+
+
+@torch.no_grad()
+def corrective_clicks(pred: torch.Tensor, gt: torch.Tensor, obj_ids: Sequence[int], mode: str = "center", u: Optional[torch.Tensor] = None,
+                      k: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, slices_per_call: int = 8):
+    """The next click of an interactive round, per (slice, object): pred and gt are uint8 [D, H, W] label volumes on the GPU (a prediction of
+    `volume_labels.label_volume` and the ground truth), obj_ids the label values.  Returns (points float32 [D, n, 1, 2] = (x, y),
+    point_labels int32 [D, n, 1], errors int32 [D, n, 2] = (|FN|, |FP|)) on the device (`ops.label_error_clicks`, csrc/clicks.hip).
+    mode="center": the voxel farthest from the border of the larger of the object's two error regions on that slice -- missed voxels (FN:
+    label 1) or voxels claimed wrongly (FP: label 0); SAM 2's `sample_one_point_from_error_center`.  mode="uniform": a voxel drawn uniformly
+    from FN | FP, labelled by the region it lies in (`sample_random_points_from_errors`): k int32 [D, n] selects the voxel in raster order,
+    or u uint32 [D, n] uniform words (k = (u * count) >> 32); without either the words are drawn on the device with `generator`
+    (a generator of the volumes' device, or None for the default one).
+    A pair without an error voxel gives label -1 at (-1, -1), `label_prompts`' absent convention (SAM 2 returns a negative click at (0, 0)).
+    The volume goes through `slices_per_call` slices at a time (the workspace is one chunk's; every slice is on its own, so the results do not
+    depend on the chunking); nothing is copied to the host."""
+    if mode not in ops.CLICK_MODES:
+        raise ValueError("Mode not recognized")
+    pred, gt = _volume(pred), _volume(gt)
+    assert pred.shape == gt.shape and pred.device == gt.device, "pred and gt: label volumes of one shape on one device"
+    dev = pred.device
+    ids = ops.label_ids(obj_ids, dev)
+    (D, H, W), n = pred.shape, ids.numel()
+    if mode == "uniform":
+        assert k is None or u is None, "either k or u"
+        if k is None and u is None:                          # 32 uniform bits per pair, held as int32 (the kernel reads the bits)
+            assert generator is None or generator.device.type == dev.type, f"generator on {generator.device}: the words are drawn on {dev}"
+            u = torch.randint(-2 ** 31, 2 ** 31, (D, n), dtype=torch.int64, device=dev, generator=generator).to(torch.int32)
+        k = None if k is None else k.to(device=dev, dtype=torch.int32).contiguous()
+        u = None if u is None else u.to(dev).contiguous()
+    else:
+        assert k is None and u is None, "k and u belong to mode='uniform'"
+    step = max(1, min(int(slices_per_call), D))
+    ws = ops._workspace8(ops.label_error_clicks_workspace_bytes(step, H, W, n, mode), dev)
+    table = torch.empty(D, n, 8, dtype=torch.int32, device=dev)
+    for i in range(0, D, step):
+        j = min(D, i + step)
+        ops.label_error_clicks(pred[i:j], gt[i:j], ids, mode, k=None if k is None else k[i:j], u=None if u is None else u[i:j], workspace=ws,
+                               out=table[i:j])
+    return table[..., :2].to(F32).unsqueeze(2), table[..., 2:3].contiguous(), table[..., 3:5].contiguous()
+
+
+def worst_slices(errors: torch.Tensor, per_object: int = 1) -> torch.Tensor:
+    """errors: int [D, n, 2] = (|FN|, |FP|) per slice and object (`corrective_clicks`) -> int64 [n, per_object]: per object the slices with
+    the most error voxels |FN| + |FP|, most first, ties to the lower slice; -1 where fewer than per_object slices of the object have an
+    error voxel (a slice without one is never named).  One composite integer key per (slice, object), total * D + (D - 1 - slice), ranks
+    them, so the order is defined; torch ops on errors' device only."""
+    assert errors.dim() == 3 and errors.shape[-1] == 2 and not errors.is_floating_point(), "errors: int [D, n, 2]"
+    per_object = int(per_object)
+    assert per_object >= 1, "per_object >= 1"
+    D, n, _ = errors.shape
+    total = errors.to(torch.int64).sum(-1)                                              # [D, n]
+    down = torch.arange(D - 1, -1, -1, dtype=torch.int64, device=errors.device)         # D - 1 - slice
+    key = total * D + down[:, None]
+    top = torch.topk(key, min(per_object, D), dim=0).values                            # keys are distinct per object
+    out = torch.full((per_object, n), -1, dtype=torch.int64, device=errors.device)
+    out[: top.shape[0]] = torch.where(top >= D, D - 1 - top % D, torch.full_like(top, -1))   # total >= 1 iff key >= D
+    return out.t().contiguous()
 
 
 def _jitter(r0, r1, c0, c1, variation: float, seed: Optional[int]) -> np.ndarray:
