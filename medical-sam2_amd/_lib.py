@@ -139,6 +139,8 @@ SIGNATURES = {
     "msam2_label_clean_workspace_bytes": (c_z, [c_l]),
     "msam2_label_clean": (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, ctypes.c_uint32, c_p, c_p, c_p, c_z, c_l, c_l, c_l, c_p]),
     "msam2_label_overlap": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    "msam2_label_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l, c_p, c_l, c_i, c_i, c_i]),
+    "msam2_label_fill_holes": (c_i, [c_p, c_l, c_l, c_l, c_p, c_p, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_z, c_p]),
     "msam2_label_edt_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_label_edt": (c_i, [c_p, c_l, c_l, c_l, c_i, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_z, c_p]),
     "msam2_label_surface_distances_workspace_bytes": (c_z, [c_p, c_l]),

@@ -1366,6 +1366,64 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# after island removal: the enclosed holes of every organ, 3-D or slice by slice (csrc/holes.hip)
+HOLE_CLAIMS = {"background": 0, "any": 1}
+HOLES_WORKSPACE_BYTES = 1 << 30    # an interface default, not a measured optimum
+
+
+def label_fill_holes(labels: torch.Tensor, ids, connectivity: int = 6, max_voxels=None, claim: str = "background",
+                     out: Optional[torch.Tensor] = None, workspace_bytes: int = HOLES_WORKSPACE_BYTES):
+    """scipy.ndimage.binary_fill_holes per organ of a uint8 [D, H, W] label volume on the device -> (out uint8 [D, H, W], info int32 [n, 4]).
+    A hole of v = ids[j] is a connected component of {voxels != v} under `connectivity` -- that of the BACKGROUND FLOOD, binary_fill_holes'
+    structure: 6 (scipy's default, the dual of 26-connected organs) / 18 / 26 in 3-D, 4 / 8 in plane, every slice on its own -- that holds no
+    voxel of the frame (the six faces of the volume; in plane the four edges of the slice).  Its size counts all its voxels, whatever they
+    carry; it qualifies iff max_voxels[j] == 0 or size <= max_voxels[j]; a voxel of it is eligible iff its input value is 0
+    (claim="background") or always ("any").  out = ids[j*] for the smallest j* such that the voxel is eligible in a qualifying hole of ids[j*],
+    else labels.  All holes are holes of the input: the order of ids decides only who gets a voxel that lies in the holes of several organs.
+    max_voxels: None, one int, a sequence or an int32 device tensor [n]; out: None (a new volume), or a uint8 volume to fill -- labels itself
+    for in place (a D*H*W-byte snapshot of the input then rides in the workspace).  info = (holes found, voxels in them, holes that
+    qualify, voxels of out that are ids[j] and were not in labels).
+
+    The boxes come from one `label_stats` call; one device-to-host copy of that small table (with the ids) is the only synchronisation,
+    nothing else is copied to the host.  Organs go through in groups whose workspace (9 bytes per box voxel, and the snapshot) stays below
+    `workspace_bytes`; an organ whose box alone needs more raises with the needed size in the message."""
+    ids_d, D, H, W, n = _label_volume_args("label_fill_holes", labels, ids, max_voxels=True)
+    _req(int(connectivity) in LABEL_CONNECTIVITIES, f"label_fill_holes: connectivity {connectivity} (one of {LABEL_CONNECTIVITIES})")
+    _req(claim in HOLE_CLAIMS, f"label_fill_holes: claim {claim!r} (one of {tuple(HOLE_CLAIMS)})")
+    dev = labels.device
+    mv = None
+    if isinstance(max_voxels, torch.Tensor):
+        mv = max_voxels.to(device=dev, dtype=torch.int32).contiguous()
+        _req(mv.shape == (n,), f"label_fill_holes: max_voxels must hold {n} values")
+    elif max_voxels is not None:
+        vals = [int(max_voxels)] * n if isinstance(max_voxels, int) else [int(v) for v in max_voxels]
+        _req(len(vals) == n and all(0 <= v < 2 ** 31 for v in vals), f"label_fill_holes: max_voxels must be {n} counts in 0 .. 2^31 - 1")
+        mv = torch.tensor(vals, dtype=torch.int32).to(dev) if any(vals) else None
+    if out is None:
+        out = torch.empty_like(labels)
+    _device_table("label_fill_holes: out", out, torch.uint8, labels.shape, dev, "labels'")
+    in_place = int(out.data_ptr() == labels.data_ptr())
+    st, _ = label_stats(labels, ids_d)
+    host = torch.cat([st.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")              # the one copy
+    m = D * n * 5
+    values = host[m:].tolist()
+    _req(len(set(values)) == n and all(1 <= v <= 255 for v in values), "label_fill_holes: ids must be distinct values in 1 .. 255")
+    boxes = [list(box) if box is not None else [0, 0, 0, 0, 0, 0] for _, box in _organ_extents(host[:m].reshape(D, n, 5))]
+    L = lib()
+    c, flat = int(connectivity), (ctypes.c_int32 * (6 * n))(*[v for b in boxes for v in b])
+    for j, b in enumerate(boxes):
+        nb = L.msam2_label_fill_holes_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, c, in_place, 0)
+        _req(nb <= workspace_bytes, f"label_fill_holes: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
+                                    f"workspace_bytes is {workspace_bytes}")
+    nb = min(L.msam2_label_fill_holes_workspace_bytes(D, H, W, flat, n, c, in_place, 1), int(workspace_bytes))
+    ws = torch.empty((nb + 15) // 16 * 2, dtype=torch.int64, device=dev)                                  # (the caching allocator aligns to 512 bytes)
+    info = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    check(L.msam2_label_fill_holes(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), flat, n, c, _p(mv), HOLE_CLAIMS[claim], _p(out), _p(info),
+                                   _p(ws), nb, _stream()))
+    return out, info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
 # arbitrary strides, read in place.
 BANK_MAX = 32          # physical slots the device tables are laid out for

@@ -9,7 +9,11 @@ re-evaluates the bilinear resize per voxel, `label_volume` feeds it the slices c
 Label rule (per voxel): the highest-scoring object above `label_thr` (0: the mask threshold of the video predictor), ties to the lower
 object index, 0 = background -- the per-pixel rule of the reference's non-overlapping constraint (`sam2_base.py:812-830`) applied at
 video resolution.  Counts are taken per object on its own (`exclusive=False`: what the reference's validation scores) or on the label
-volume (`exclusive=True`)."""
+volume (`exclusive=True`).
+
+Between the label volume and its scores sits the usual post-processing, on the device as well: `clean_labels` keeps the largest component of
+every organ and drops islands (csrc/components.hip), `fill_holes` fills the cavities enclosed by an organ, 3-D or slice by slice
+(csrc/holes.hip: scipy.ndimage.binary_fill_holes per organ), and `postprocess_labels` runs the two in that order."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Union
@@ -117,6 +121,18 @@ def labels_from_pack(label: Dict[int, Dict[int, torch.Tensor]], obj_list: Sequen
     return vol if device is None else vol.to(device)
 
 
+def _resolve_ids(what: str, labels: torch.Tensor, obj_ids, n):
+    """obj_ids / n as `clean_labels` documents them -> the ids on labels' device"""
+    if obj_ids is None:
+        assert n is not None and int(n) >= 1, f"{what}: without obj_ids the number of objects n is needed (the volume is not scanned)"
+        obj_ids = list(range(1, int(n) + 1))
+    dev = labels.device
+    on_dev = isinstance(obj_ids, torch.Tensor) and obj_ids.device == dev and dev.type != "cpu"
+    ids = obj_ids if on_dev else ops.label_ids(obj_ids, dev)
+    assert n is None or ids.numel() == int(n), f"{what}: {ids.numel()} ids for n = {n}"
+    return ids
+
+
 @torch.no_grad()
 def clean_labels(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, connectivity: int = 26, keep_largest=True, min_voxels=0,
                  in_place: bool = False, n: Optional[int] = None):
@@ -126,16 +142,37 @@ def clean_labels(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, 
     obj_ids: the label values (distinct, 1 .. 255; a device tensor of `ops.label_ids` is taken as is); None = 1 .. n with `n` given by the
     caller -- the volume is never scanned on the host.  Returns (cleaned uint8 [T, H, W], info int32 [n, 6]) on the device, info =
     (components found, voxels found, largest size, its canonical name or 0, components kept, voxels kept); in_place=True overwrites labels."""
-    if obj_ids is None:
-        assert n is not None and int(n) >= 1, "clean_labels: without obj_ids the number of objects n is needed (the volume is not scanned)"
-        obj_ids = list(range(1, int(n) + 1))
-    dev = labels.device
-    on_dev = isinstance(obj_ids, torch.Tensor) and obj_ids.device == dev and dev.type != "cpu"
-    ids = obj_ids if on_dev else ops.label_ids(obj_ids, dev)
-    assert n is None or ids.numel() == int(n), f"clean_labels: {ids.numel()} ids for n = {n}"
+    ids = _resolve_ids("clean_labels", labels, obj_ids, n)
     comp, size = ops.label_components(labels, connectivity)
     mv = None if isinstance(min_voxels, int) and min_voxels == 0 else min_voxels
     return ops.label_clean(labels, comp, size, ids, min_voxels=mv, keep_largest=keep_largest, out=labels if in_place else None)
+
+
+@torch.no_grad()
+def fill_holes(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, connectivity: int = 6, max_voxels=0, claim: str = "background",
+               in_place: bool = False, n: Optional[int] = None):
+    """Hole filling after `clean_labels`: scipy.ndimage.binary_fill_holes per organ of the uint8 [T, H, W] label volume on the device
+    (`ops.label_fill_holes`).  `connectivity` is that of the background flood: 6 (scipy's default) / 18 / 26 in 3-D, 4 / 8 slice by slice.
+    A hole of an organ is a component of the voxels that are not the organ's which does not reach the frame; holes of more than
+    `max_voxels` voxels stay (0: no limit; one value, or one per object); claim="background" fills only the background voxels of a hole,
+    "any" also an enclosed lesion of another label.  A voxel in the holes of several organs goes to the one first in obj_ids.
+    obj_ids / n: as `clean_labels` takes them.  Returns (filled uint8 [T, H, W], info int32 [n, 4]) on the device, info = (holes found, voxels
+    in them, holes that qualify, voxels the organ gained); in_place=True overwrites labels."""
+    ids = _resolve_ids("fill_holes", labels, obj_ids, n)
+    mv = None if isinstance(max_voxels, int) and max_voxels == 0 else max_voxels
+    return ops.label_fill_holes(labels, ids, connectivity, max_voxels=mv, claim=claim, out=labels if in_place else None)
+
+
+@torch.no_grad()
+def postprocess_labels(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, connectivity: int = 26, keep_largest=True, min_voxels=0,
+                       hole_connectivity: int = 6, max_voxels=0, claim: str = "background", in_place: bool = False, n: Optional[int] = None):
+    """The usual abdominal post-processing between `label_volume` and the scores: `clean_labels` (connectivity, keep_largest, min_voxels),
+    then `fill_holes` (hole_connectivity, max_voxels, claim) on its result.  Returns (labels, clean_info int32 [n, 6], hole_info int32 [n, 4])
+    on the device; in_place=True overwrites labels."""
+    ids = _resolve_ids("postprocess_labels", labels, obj_ids, n)
+    cleaned, clean_info = clean_labels(labels, ids, connectivity, keep_largest, min_voxels, in_place=in_place)
+    filled, hole_info = fill_holes(cleaned, ids, hole_connectivity, max_voxels, claim, in_place=True)
+    return filled, clean_info, hole_info
 
 
 @torch.no_grad()
