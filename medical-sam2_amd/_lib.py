@@ -67,6 +67,8 @@ SIGNATURES = {
     "msam2_patch_embed7x7s4": (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_p]),
     "msam2_im2col3x3s2": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p]),
     "msam2_conv3x3s2_ln_gelu": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_i, c_f, c_f, c_p]),
+    "msam2_conv3x3s2_mfma_ln_gelu_supported": (c_i, [c_l, c_l]),
+    "msam2_conv3x3s2_mfma_ln_gelu": (c_i, [c_p, c_p, c_l, c_p, c_p, c_p, c_f, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_p]),
     "msam2_dwconv7x7_ln": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_convt2x2_shuffle": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_convt2x2_shuffle_f32skip": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),

@@ -23,6 +23,23 @@ import os as _os
 _FUSED_ROPE = _os.environ.get("MSAM2_NO_FUSED_ROPE") is None   # experiment switch: rotate in a separate in-place kernel instead
 _FOLD_V = _os.environ.get("MSAM2_NO_VALUE_FOLD") is None       # experiment switch: 256-wide values through v_proj instead
 _BATCH_K_PROJ = _os.environ.get("MSAM2_BATCHED_KPROJ") is not None   # experiment switch (OFF: measured slower, see _project_all_keys)
+# A/B switch: stages 2-4 of the mask down-sampler as the three launches they were (im2col, GEMM with fp32 output, LayerNorm + GELU) instead of
+# one implicit-GEMM kernel each, and the per-stage list of that fusion: a stage that does not beat its three launches inside
+# the step is taken off the list
+_FUSED_MASK_DS = _os.environ.get("MSAM2_NO_FUSED_MASK_DS") is None
+
+
+def _stage_list(text: str) -> frozenset:
+    """'2, 4' -> {2, 4}; empty entries are skipped, so '' switches every stage off"""
+    return frozenset(int(k) for k in text.split(",") if k.strip())
+
+
+_FUSED_MASK_DS_STAGES = _stage_list(_os.environ.get("MSAM2_FUSED_MASK_DS_STAGES", "2,3,4"))
+
+
+def _mask_ds_dispatched(stage: int, cin: int, cout: int) -> bool:
+    """Does stage `stage` (2 .. 4) of the mask down-sampler, cin -> cout channels, run as one kernel?"""
+    return _FUSED_MASK_DS and stage in _FUSED_MASK_DS_STAGES and ops.conv3x3s2_mfma_ln_gelu_supported(cin, cout)
 
 
 class LayerNorm2d(nn.Module):
@@ -408,18 +425,23 @@ class MaskDownSampler(nn.Module):
         h = ops.conv3x3s2_ln_gelu(h, n, S, S, wc.get("cw0", [conv.weight], lambda: conv.weight.detach().float().contiguous()),
                                   f("cb0", conv.bias), f("lw0", ln.weight), f("lb0", ln.bias), mode, scale, bias)
         side = S // 2
-        # stages 2-4 (4->16, 16->64, 64->256): im2col + MFMA GEMM, LayerNorm2d + GELU on the fp32 result
+        # stages 2-4 (4->16, 16->64, 64->256): one implicit-GEMM kernel with bias + LayerNorm2d + GELU in its epilogue, or the three launches
+        # whose bits it reproduces: im2col + MFMA GEMM, LayerNorm2d + GELU on the fp32 result.  Both take the same packed weight
         for j in range(1, 4):
             conv, ln = enc[3 * j], enc[3 * j + 1]
-            cols = ops.im2col3x3s2(h, n, side, side)
+            cout, cin = conv.weight.shape[0], conv.weight.shape[1]
 
-            def pack(c=conv, ld=cols.shape[1]):
+            def pack(c=conv, ld=(9 * cin + 7) // 8 * 8):
                 w = c.weight.detach().permute(0, 2, 3, 1).reshape(c.weight.shape[0], -1)
                 out = torch.zeros(w.shape[0], ld, dtype=OP16, device=w.device)
                 out[:, : w.shape[1]] = w.to(OP16)
                 return out
-            g = ops.gemm(cols, wc.get(f"cw{j}", [conv.weight], pack), f(f"cb{j}", conv.bias), out_dtype=F32)
-            h = ops.layernorm(g, f(f"lw{j}", ln.weight), f(f"lb{j}", ln.bias), ln.eps, act=ops.ACT_GELU)
+            w = wc.get(f"cw{j}", [conv.weight], pack)
+            if _mask_ds_dispatched(j + 1, cin, cout):
+                h = ops.conv3x3s2_mfma_ln_gelu(h, n, side, side, w, f(f"cb{j}", conv.bias), f(f"lw{j}", ln.weight), f(f"lb{j}", ln.bias), ln.eps)
+            else:
+                g = ops.gemm(ops.im2col3x3s2(h, n, side, side), w, f(f"cb{j}", conv.bias), out_dtype=F32)
+                h = ops.layernorm(g, f(f"lw{j}", ln.weight), f(f"lb{j}", ln.bias), ln.eps, act=ops.ACT_GELU)
             side //= 2
         return ops.gemm(h, w_bf16(wc, "pw", enc[12].weight), f("pb", enc[12].bias), out_dtype=F32)
 

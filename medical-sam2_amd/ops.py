@@ -622,6 +622,32 @@ def conv3x3s2_ln_gelu(x: torch.Tensor, B: int, H: int, W: int, weight, bias, ln_
     return y
 
 
+def conv3x3s2_mfma_ln_gelu_supported(cin: int, cout: int) -> bool:
+    """True when `conv3x3s2_mfma_ln_gelu` is built for these channel counts (4 -> 16, 16 -> 64, 64 -> 256)."""
+    return bool(lib().msam2_conv3x3s2_mfma_ln_gelu_supported(cin, cout))
+
+
+def conv3x3s2_mfma_ln_gelu(x: torch.Tensor, B: int, H: int, W: int, w_packed: torch.Tensor, bias: torch.Tensor, ln_w: torch.Tensor,
+                           ln_b: torch.Tensor, eps: float, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """16-bit [B*(H/2)*(W/2), cout] = GELU(LayerNorm2d(conv3x3 s2 p1(x) + bias)) from one kernel: the bits of `im2col3x3s2` -> `gemm(out_dtype=F32)`
+    -> `layernorm(act=ACT_GELU)`.  x 16-bit contiguous NHWC [B*H*W, cin]; w_packed 16-bit [cout, ld] with columns (ky, kx, c), zero filled
+    up to ld >= ceil8(9 cin): the weight that `gemm` takes.  A form that is not built (`conv3x3s2_mfma_ln_gelu_supported`) is an error."""
+    _req(x.dtype == OP16 and x.is_contiguous() and x.numel() % (B * H * W) == 0, "conv3x3s2_mfma_ln_gelu: 16-bit contiguous NHWC")
+    cin = x.numel() // (B * H * W)
+    _req(w_packed.dim() == 2 and w_packed.dtype == OP16 and w_packed.stride(1) == 1, "conv3x3s2_mfma_ln_gelu: w_packed must be 16-bit [cout, ld]")
+    cout = w_packed.shape[0]
+    _req(conv3x3s2_mfma_ln_gelu_supported(cin, cout), f"conv3x3s2_mfma_ln_gelu: {cin} -> {cout} channels is not built (4 -> 16, 16 -> 64, 64 -> 256)")
+    _req(w_packed.shape[1] >= (9 * cin + 7) // 8 * 8, "conv3x3s2_mfma_ln_gelu: w_packed rows hold ceil8(9 cin) columns")
+    _req(all(t.dtype == F32 and t.is_contiguous() and t.numel() == cout for t in (bias, ln_w, ln_b)), "conv3x3s2_mfma_ln_gelu: bias, ln_w, ln_b are fp32 [cout]")
+    M = B * (H // 2) * (W // 2)
+    if out is None:
+        out = torch.empty(M, cout, dtype=OP16, device=x.device)
+    _req(out.dtype == OP16 and out.shape == (M, cout) and out.stride(1) == 1, "conv3x3s2_mfma_ln_gelu: out must be 16-bit [M, cout], rows contiguous")
+    check(lib().msam2_conv3x3s2_mfma_ln_gelu(_p(x), _p(w_packed), w_packed.stride(0), _p(bias), _p(ln_w), _p(ln_b), float(eps), _p(out),
+                                             out.stride(0), B, H, W, cin, cout, _stream()))
+    return out
+
+
 def dwconv7x7_ln(x: torch.Tensor, B: int, H: int, W: int, w_tap_major, bias, ln_w, ln_b) -> torch.Tensor:
     _req(x.dtype == F32 and x.is_contiguous(), "dwconv7x7_ln: fp32 contiguous NHWC")
     C = x.shape[-1]
