@@ -147,6 +147,8 @@ SIGNATURES = {
     "msam2_label_edt": (c_i, [c_p, c_l, c_l, c_l, c_i, c_i, c_p, c_d, c_d, c_d, c_p, c_p, c_z, c_p]),
     "msam2_label_surface_distances_workspace_bytes": (c_z, [c_p, c_l]),
     "msam2_label_surface_distances": (c_i, [c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_d, c_d, c_d, c_p, c_l, c_p, c_p, c_z, c_p]),
+    "msam2_label_morph_workspace_bytes": (c_z, [c_l, c_l, c_l, c_p, c_l, c_i, c_p, c_d, c_d, c_d, c_i, c_i]),
+    "msam2_label_morph": (c_i, [c_p, c_l, c_l, c_l, c_p, c_p, c_l, c_i, c_p, c_d, c_d, c_d, c_i, c_p, c_p, c_p, c_z, c_p]),
     "msam2_label_error_clicks_workspace_bytes": (c_z, [c_l, c_l, c_l, c_l, c_i]),
     "msam2_label_error_clicks": (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_z, c_p]),
     "msam2_volume_prep_workspace_bytes": (c_z, [c_l, c_l, c_l, c_l]),

@@ -5,7 +5,8 @@
 // Definitions.  A voxel is on the surface of value v iff it equals v and a face neighbour differs from v or lies outside the
 // volume (6 neighbours; D == 1: the 4 in plane).  d2(q, F) = min over f in F of ((sx2 dx^2 + sy2 dy^2) + sz2 dz^2) in float64, every product
 // and sum rounded on its own (this file is compiled with fp contraction off: no fused multiply-add), +inf for an empty F.  Float64 addition
-// and multiplication by a positive constant are monotone, so the minimum is taken axis by axis and has the bits of the brute-force minimum:
+// and multiplication by a positive constant are monotone, so the minimum is taken axis by axis and has the bits of the brute-force minimum
+// (the bodies of the row pass and of the two scans are edt_passes.h's, which morph.hip shares):
 //   * rows: one wave per row of the box, 64 columns at a time.  The features are marked on the fly from the label bytes; a ballot and one
 //     count-leading-zeros give every lane the nearest feature at or left of it, the last feature column is carried from chunk to chunk
 //     (wave-uniform); a second sweep from the right end (a feature is where the left distance is 0) takes the smaller one.  uint16 per
@@ -19,13 +20,13 @@
 // Boxes are host integers and travel to the kernels by value (SrfJobs).  Apart from the workgroup barrier around that one add no thread waits
 // for another: no spin, no grid barrier, no cooperative launch.
 #include "common.h"
+#include "edt_passes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int SRF_THREADS = 256;
-constexpr int SRF_NONE = 0xFFFF;                            // no feature in this row of the box (a real distance is <= 8191)
 enum { SRF_SURFACE = 0, SRF_OUTSIDE = 1 };
 
 struct SrfOrgan {
@@ -90,39 +91,11 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_row_kernel(const uint8_t* __r
   const SrfBufs bufs = srf_bufs(ws, o, dir);
   const int zb = (int)(row / o.bh), yb = (int)(row - (int64_t)zb * o.bh);
   const int z = o.z0 + zb, y = o.y0 + yb;
-  uint16_t* __restrict__ g = bufs.g + row * o.bw;
-  const int chunks = (o.bw + 63) >> 6;
-  int last = -1;                                            // wave-uniform: the last feature column (in the box) seen so far
-#pragma unroll 1
-  for (int c = 0; c < chunks; ++c) {
-    const int xb = c * 64 + lane;
-    const bool live = xb < o.bw;
-    bool feat = false;
-    if (live) {
-      const int x = o.x0 + xb;
-      feat = mode == SRF_SURFACE ? srf_on_surface(f, jobs.D, jobs.H, jobs.W, z, y, x, o.value)
-                                 : f[((int64_t)z * jobs.H + y) * jobs.W + x] != o.value;
-    }
-    const unsigned long long m = __ballot(feat);
-    const unsigned long long below = m & (~0ull >> (63 - lane));
-    const int dl = below ? lane - (63 - __clzll((long long)below)) : (last >= 0 ? xb - last : SRF_NONE);
-    if (live) g[xb] = (uint16_t)dl;
-    if (m) last = c * 64 + 63 - __clzll((long long)m);
-  }
-  if (last < 0) return;                                     // every element is SRF_NONE already
-  if (lane == 0) bufs.flag[zb] = 1;                         // (every row of the slice that has a feature stores the same 1)
-  int next = -1;                                            // the first feature column right of the chunk
-#pragma unroll 1
-  for (int c = chunks - 1; c >= 0; --c) {
-    const int xb = c * 64 + lane;
-    const bool live = xb < o.bw;
-    const int dl = live ? (int)g[xb] : SRF_NONE;            // this lane's own store of the first sweep
-    const unsigned long long m = __ballot(live && dl == 0);
-    const unsigned long long above = m >> lane;
-    const int dr = above ? __ffsll((long long)above) - 1 : (next >= 0 ? next - xb : SRF_NONE);
-    if (live && dr < dl) g[xb] = (uint16_t)dr;
-    if (m) next = c * 64 + __ffsll((long long)m) - 1;
-  }
+  const int64_t at = ((int64_t)z * jobs.H + y) * jobs.W + o.x0;
+  const bool any = edt_row_pass(bufs.g + row * o.bw, o.bw, lane, [&](int xb) {
+    return mode == SRF_SURFACE ? srf_on_surface(f, jobs.D, jobs.H, jobs.W, z, y, o.x0 + xb, o.value) : f[at + xb] != o.value;
+  });
+  if (any && lane == 0) bufs.flag[zb] = 1;                  // (every row of the slice that has a feature stores the same 1)
 }
 
 __global__ __launch_bounds__(SRF_THREADS) void srf_col_kernel(SrfJobs jobs, char* __restrict__ ws, double sx2, double sy2) {
@@ -136,40 +109,13 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_col_kernel(SrfJobs jobs, char
   const int xb = (int)(i - r * o.bw);
   const int zb = (int)(r / o.bh), yb = (int)(r - (int64_t)zb * o.bh);
   double best = __builtin_huge_val();
-  if (bufs.flag[zb]) {
-    const uint16_t* __restrict__ col = bufs.g + (int64_t)zb * o.bh * o.bw + xb;   // element y' of the column: col[y' * bw]
-    const int reach = max(yb, o.bh - 1 - yb);
-#pragma unroll 1
-    for (int k = 0; k <= reach; ++k) {
-      const double dy2 = sy2 * ((double)k * (double)k);
-      if (!(dy2 < best)) break;
-      if (yb - k >= 0) {
-        const int gx = col[(int64_t)(yb - k) * o.bw];
-        if (gx != SRF_NONE) best = fmin(best, sx2 * ((double)gx * (double)gx) + dy2);
-      }
-      if (k > 0 && yb + k < o.bh) {
-        const int gx = col[(int64_t)(yb + k) * o.bw];
-        if (gx != SRF_NONE) best = fmin(best, sx2 * ((double)gx * (double)gx) + dy2);
-      }
-    }
-  }
+  if (bufs.flag[zb]) best = edt_scan_y(bufs.g + (int64_t)zb * o.bh * o.bw + xb, o.bw, yb, o.bh, sx2, sy2, best);
   bufs.t[i] = best;
 }
 
 // min over z' of (t[z', y, x] + sz2 dz^2) for box voxel (zb, yb, xb)
 __device__ __forceinline__ double srf_scan_z(const double* __restrict__ t, const SrfOrgan& o, int zb, int yb, int xb, double sz2) {
-  const int64_t plane = (int64_t)o.bh * o.bw;
-  const double* __restrict__ col = t + (int64_t)yb * o.bw + xb;
-  const int reach = max(zb, o.bd - 1 - zb);
-  double best = __builtin_huge_val();
-#pragma unroll 1
-  for (int k = 0; k <= reach; ++k) {
-    const double dz2 = sz2 * ((double)k * (double)k);
-    if (!(dz2 < best)) break;
-    if (zb - k >= 0) best = fmin(best, col[(zb - k) * plane] + dz2);
-    if (k > 0 && zb + k < o.bd) best = fmin(best, col[(zb + k) * plane] + dz2);
-  }
-  return best;
+  return edt_scan_z(t + (int64_t)yb * o.bw + xb, (int64_t)o.bh * o.bw, zb, o.bd, sz2, __builtin_huge_val());
 }
 
 // box voxel i -> (zb, yb, xb)

@@ -1450,6 +1450,76 @@ def label_fill_holes(labels: torch.Tensor, ids, connectivity: int = 6, max_voxel
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# between the label volume and the scores: erosion, dilation, opening, closing by a ball of a physical radius (csrc/morph.hip)
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}
+MORPH_WORKSPACE_BYTES = 2 << 30    # an interface default, not a measured optimum
+
+
+def _radius2(what: str, radius, radius2, n: int):
+    """radius= / radius2= (one value, or one per object) -> n squared radii as floats: r2 = float(radius) * float(radius), or radius2 as is"""
+    _req((radius is None) != (radius2 is None), f"{what}: exactly one of radius and radius2")
+    given = radius if radius2 is None else radius2
+    vals = [float(v) for v in (given.tolist() if isinstance(given, torch.Tensor) else given)] if hasattr(given, "__len__") else [float(given)] * n
+    r2 = [v * v for v in vals] if radius2 is None else vals
+    _req(len(vals) == n and all(0.0 <= v < float("inf") for v in vals + r2),
+         f"{what}: radius / radius2 must be one value or {n} values, each >= 0 with a finite square")
+    return r2
+
+
+def label_morph(labels: torch.Tensor, ids, op: str, radius=None, radius2=None, spacing=(1.0, 1.0, 1.0), claim: str = "background",
+                out: Optional[torch.Tensor] = None, workspace_bytes: int = MORPH_WORKSPACE_BYTES):
+    """Erosion, dilation, opening or closing of every listed organ of a uint8 [D, H, W] label volume (H, W >= 2) by a ball of a physical
+    radius, on the device -> (out uint8 [D, H, W], info int32 [n, 4]).  d2(q, f) = ((sx^2 dx^2 + sy^2 dy^2) + sz^2 dz^2) in float64 as
+    `label_edt` computes it; the ball is d2 <= r2, with <=.  r2 reaches the library as a float64: radius= gives float(radius) * float(radius),
+    radius2= gives it directly, exactly one of the two (one value, or one per object).  (3 ** 0.5) ** 2 == 2.9999999999999996: radius=sqrt(3)
+    does NOT reach a voxel at d2 = 3, radius2=3.0 does.
+    With M = (labels == ids[j]): dilate = {q in the volume: min over f in M of d2(q, f) <= r2}; erode = {q in M: no voxel f of the volume
+    outside M has d2(q, f) <= r2} -- there are no features beyond the volume, so an organ cut by the field of view does not erode from the frame
+    (`label_edt(features="outside")`; at unit spacing scipy's binary_erosion(border_value=1)); open = dilate(erode(M)), close = erode(dilate(M)).
+    erode / open: a voxel of a listed organ that is not in its result becomes 0, everything else stays.  dilate / close: a voxel may change only
+    if it is eligible -- its input value is 0 (claim="background") or not in ids ("any": an unlisted lesion may be overwritten); a listed organ
+    never loses a voxel; an eligible voxel inside the results of several organs goes to the organ whose ORIGINAL mask is nearest (smallest d2),
+    ties to the organ earlier in ids: a margin between two neighbours is split along their mid-surface.
+    out: None (a new volume), or a uint8 volume to fill -- labels itself for in place (a D*H*W-byte snapshot of the input then rides in the
+    workspace).  info = (voxels before, voxels in the organ's own result set, voxels after, voxels taken from non-zero values); an absent organ
+    gives a row of zeros and changes nothing.
+
+    The boxes come from one `label_stats` call; one device-to-host copy of that small table (with the ids) is the only synchronisation,
+    nothing else is copied to the host.  Organs go through in groups whose workspace (19 bytes per voxel of the organ's box grown by the ball,
+    11 for erode / open; dilate / close also 8 bytes per voxel of the volume) stays below `workspace_bytes`; an organ whose box alone needs more
+    raises with the needed size in the message.  The result depends on neither the grouping nor the boxes."""
+    ids_d, D, H, W, n = _label_volume_args("label_morph", labels, ids, min_side=2, max_voxels=True)
+    _req(op in MORPH_OPS, f"label_morph: op {op!r} (one of {tuple(MORPH_OPS)})")
+    _req(claim in HOLE_CLAIMS, f"label_morph: claim {claim!r} (one of {tuple(HOLE_CLAIMS)})")
+    sz, sy, sx = _spacing("label_morph", spacing)
+    r2 = _radius2("label_morph", radius, radius2, n)
+    dev = labels.device
+    if out is None:
+        out = torch.empty_like(labels)
+    _device_table("label_morph: out", out, torch.uint8, labels.shape, dev, "labels'")
+    in_place = int(out.data_ptr() == labels.data_ptr())
+    st, _ = label_stats(labels, ids_d)
+    host = torch.cat([st.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")              # the one copy
+    m = D * n * 5
+    values = host[m:].tolist()
+    _req(len(set(values)) == n and all(1 <= v <= 255 for v in values), "label_morph: ids must be distinct values in 1 .. 255")
+    boxes = [list(box) if box is not None else [0, 0, 0, 0, 0, 0] for _, box in _organ_extents(host[:m].reshape(D, n, 5))]
+    L = lib()
+    o, flat, r2s = MORPH_OPS[op], (ctypes.c_int32 * (6 * n))(*[v for b in boxes for v in b]), (ctypes.c_double * n)(*r2)
+    for j, b in enumerate(boxes):
+        nb = L.msam2_label_morph_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, o, (ctypes.c_double * 1)(r2[j]), sz, sy, sx, in_place, 0)
+        _req(nb > 0, f"label_morph: the box of id {values[j]} grown by its ball has more than 2^25 rows (slices x rows)")
+        _req(nb <= workspace_bytes, f"label_morph: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
+                                    f"workspace_bytes is {workspace_bytes}")
+    nb = min(L.msam2_label_morph_workspace_bytes(D, H, W, flat, n, o, r2s, sz, sy, sx, in_place, 1), int(workspace_bytes))
+    ws = torch.empty((nb + 15) // 16 * 2, dtype=torch.int64, device=dev)                                  # (the caching allocator aligns to 512 bytes)
+    info = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    check(L.msam2_label_morph(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), flat, n, o, r2s, sz, sy, sx, HOLE_CLAIMS[claim], _p(out),
+                              _p(info), _p(ws), nb, _stream()))
+    return out, info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D memory bank (csrc/bank.hip); every tensor fp32.  Operands of bank_dots / bank_commit are 3-D views [rows, n_ch, n_px] with
 # arbitrary strides, read in place.
 BANK_MAX = 32          # physical slots the device tables are laid out for

@@ -13,7 +13,8 @@ volume (`exclusive=True`).
 
 Between the label volume and its scores sits the usual post-processing, on the device as well: `clean_labels` keeps the largest component of
 every organ and drops islands (csrc/components.hip), `fill_holes` fills the cavities enclosed by an organ, 3-D or slice by slice
-(csrc/holes.hip: scipy.ndimage.binary_fill_holes per organ), and `postprocess_labels` runs the two in that order."""
+(csrc/holes.hip: scipy.ndimage.binary_fill_holes per organ), and `postprocess_labels` runs the two in that order; `morph_labels` erodes,
+dilates, opens or closes every organ with a ball of a radius in millimetres (csrc/morph.hip)."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Sequence, Union
@@ -161,6 +162,24 @@ def fill_holes(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, co
     ids = _resolve_ids("fill_holes", labels, obj_ids, n)
     mv = None if isinstance(max_voxels, int) and max_voxels == 0 else max_voxels
     return ops.label_fill_holes(labels, ids, connectivity, max_voxels=mv, claim=claim, out=labels if in_place else None)
+
+
+@torch.no_grad()
+def morph_labels(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, op: str = "close", radius=1.0, spacing=(1.0, 1.0, 1.0),
+                 claim: str = "background", in_place: bool = False, n: Optional[int] = None, radius2=None):
+    """Morphology with a ball of a physical radius on the uint8 [T, H, W] label volume, per organ, on the device (`ops.label_morph`): op =
+    "erode" / "dilate" / "open" / "close", `radius` in the unit of `spacing` = (sz, sy, sx), one value or one per object.  An opening drops the
+    thin bridge that joins a leak to an organ (which `clean_labels` cannot: the bridge makes them one component); a closing fills the notches
+    and gaps open to the background that `fill_holes` leaves; a dilation is a margin that stops at the neighbours, an erosion a safe core.
+    The ball is d2 <= r2 with r2 = float(radius) * float(radius); `radius2` (then radius is ignored) gives r2 directly -- (3 ** 0.5) ** 2 ==
+    2.9999999999999996, so radius=sqrt(3) does not reach a voxel at d2 = 3 and radius2=3.0 does.  An organ cut by the field of view does not
+    erode from the frame.  dilate / close change only eligible voxels (claim="background": input value 0; "any": any value not in obj_ids), a
+    voxel several organs reach goes to the one whose original mask is nearest, ties to the one earlier in obj_ids.
+    obj_ids / n: as `clean_labels` takes them.  Returns (labels uint8 [T, H, W], info int32 [n, 4]) on the device, info = (voxels before, voxels
+    in the organ's own result set, voxels after, voxels taken from non-zero values); in_place=True overwrites labels."""
+    ids = _resolve_ids("morph_labels", labels, obj_ids, n)
+    r = dict(radius2=radius2) if radius2 is not None else dict(radius=radius)
+    return ops.label_morph(labels, ids, op, spacing=spacing, claim=claim, out=labels if in_place else None, **r)
 
 
 @torch.no_grad()
