@@ -155,6 +155,14 @@ SIGNATURES = {
     "msam2_volume_prep": (c_i, [c_p, c_i, c_l, c_l, c_l, c_l, c_l, ctypes.POINTER(c_d), c_p, c_p, c_l, c_p, c_p, c_l, ctypes.POINTER(c_f),
                                 ctypes.POINTER(c_f), c_p, c_p, c_p, c_z, c_p]),
     "msam2_label_resize": (c_i, [c_p, c_i, c_l, c_l, c_l, c_l, c_p, c_p, ctypes.POINTER(ctypes.c_uint32), c_p, c_p]),
+    "msam2_decoder_tokens_supported": (c_i, [c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_l, c_l]),
+    "msam2_decoder_tokens_self": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
+    "msam2_decoder_tokens_workspace_bytes": (c_z, [c_l, c_l]),
+    "msam2_decoder_tokens_mlp": (c_i, [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                       c_p, c_p, c_p, c_z, c_l, c_l, c_l, c_l, c_l, c_p]),
+    "msam2_decoder_tokens_tail": (c_i, [c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_l, c_l, c_l, c_l, c_p]),
+    "msam2_attention_fewq_keysplit_splits": (c_i, [c_l, c_l]),
+    "msam2_attention_fewq_keysplit": (c_i, [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p]),
     "msam2_cc_workspace_bytes": (c_z, [c_l, c_l, c_l]),
     "msam2_cc_label": (c_i, [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_z, c_p]),
     "msam2_fill_holes_workspace_bytes": (c_z, [c_l, c_l, c_l]),

@@ -2476,16 +2476,23 @@ __global__ void attn_fewkeys_kernel(const op16* q, const op16* k, const op16* v,
 // unchanged).  Every K fragment and V chunk of the wave's key range is loaded up front (8 + 8 loads per lane in flight).  The 16 waves'
 // (max, sum, O) are merged through LDS by the first 16 * Lq threads.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restrict__ q, const op16* __restrict__ k, const op16* __restrict__ v,
-                                                           op16* __restrict__ o, int64_t q_bs, int64_t q_ts, int64_t k_bs, int64_t k_ts,
-                                                           int64_t v_bs, int64_t v_ts, int64_t o_bs, int64_t o_ts, int H, int Lq, int Lk,
-                                                           float scale_log2) {
-  constexpr int D = 16, RB = 64, BK = 32, NW = 16, MAXS = 8;  // MAXS 32-key steps per wave: Lk <= 16 * 8 * 32 = 4096 (launcher)
+// KEY SPLIT (SPLITS > 1 workgroups per (batch, head), msam2_attention_fewq_keysplit): 32 workgroups leave 7 / 8 of the chip idle, so the keys of a
+// (batch, head) go to `splits` workgroups, split s taking keys [s * ceil(Lk / splits), ...); each writes the merged (max, sum, O) of its
+// 16 waves UN-normalised, fp32, to part[((b * H + head) * splits + s) * Lq + query][18] = (m, l, O[0..15]) -- an empty split reports
+// (-inf, 0, 0) -- and the token-side kernel that consumes the attention output (csrc/decoder_tokens.hip) merges the splits in split order
+// with the formula of the 16-wave merge below.  MAXS: 32-key steps per wave, ceil(keys of a split / 512) rounded up to a power of two.
+template <int MAXS, bool PARTIAL>
+__device__ __forceinline__ void attn_fewq16_body(const op16* __restrict__ q, const op16* __restrict__ k, const op16* __restrict__ v,
+                                                 op16* __restrict__ o, int64_t q_bs, int64_t q_ts, int64_t k_bs, int64_t k_ts, int64_t v_bs,
+                                                 int64_t v_ts, int64_t o_bs, int64_t o_ts, int H, int Lq, int Lk, float scale_log2,
+                                                 float* __restrict__ part_out, int splits) {
+  constexpr int D = 16, RB = 64, BK = 32, NW = 16;            // MAXS 32-key steps per wave: Lk <= 16 * 8 * 32 = 4096 at MAXS = 8 (launcher)
   __shared__ __attribute__((aligned(16))) unsigned char vt[NW][BK * RB];        // per-wave V tile
   __shared__ float part[NW][32][18];                                          // per wave and query: m, l, O[0..15]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
-  const int b = blockIdx.x / H, head = blockIdx.x - b * H;
+  const int bh = PARTIAL ? blockIdx.x / splits : blockIdx.x, split = PARTIAL ? blockIdx.x - bh * splits : 0;
+  const int b = bh / H, head = bh - b * H;
   const op16* qb = q + (int64_t)b * q_bs + head * D;
   const op16* kb = k + (int64_t)b * k_bs + head * D;
   const op16* vb = v + (int64_t)b * v_bs + head * D;
@@ -2503,8 +2510,10 @@ __global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restric
     qf = __builtin_bit_cast(op16x8, t);
   }
   // this wave's keys: steps of 32, every load issued before the first use (row indices clamped; masked below)
-  const int per = (Lk + NW - 1) / NW;                         // keys per wave
-  const int key_lo = wave * per, key_hi = min(Lk, key_lo + per);
+  const int per_split = PARTIAL ? (Lk + splits - 1) / splits : Lk;
+  const int k_lo = split * per_split, k_hi = min(Lk, k_lo + per_split);       // this workgroup's keys (empty behind the last key)
+  const int per = (max(0, k_hi - k_lo) + NW - 1) / NW;        // keys per wave
+  const int key_lo = k_lo + wave * per, key_hi = min(k_hi, key_lo + per);
   const int nsteps = max(0, (key_hi - key_lo + BK - 1) / BK);
   uint4 kfr[MAXS], vch[MAXS];
 #pragma unroll
@@ -2580,8 +2589,28 @@ __global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restric
       L += part[w][qi][1] * wgt;
       acc += part[w][qi][2 + d] * wgt;
     }
-    o[(int64_t)b * o_bs + (int64_t)qi * o_ts + head * D + d] = f2op(acc / L);
+    if constexpr (PARTIAL) {
+      float* po = part_out + ((int64_t)blockIdx.x * Lq + qi) * 18;
+      if (d == 0) { po[0] = M; po[1] = L; }
+      po[2 + d] = acc;
+    } else {
+      o[(int64_t)b * o_bs + (int64_t)qi * o_ts + head * D + d] = f2op(acc / L);
+    }
   }
+}
+
+__global__ __launch_bounds__(1024) void attn_fewq16_kernel(const op16* __restrict__ q, const op16* __restrict__ k, const op16* __restrict__ v,
+                                                           op16* __restrict__ o, int64_t q_bs, int64_t q_ts, int64_t k_bs, int64_t k_ts,
+                                                           int64_t v_bs, int64_t v_ts, int64_t o_bs, int64_t o_ts, int H, int Lq, int Lk,
+                                                           float scale_log2) {
+  attn_fewq16_body<8, false>(q, k, v, o, q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts, H, Lq, Lk, scale_log2, nullptr, 1);
+}
+
+template <int MAXS>
+__global__ __launch_bounds__(1024) void attn_fewq16_part_kernel(const op16* __restrict__ q, const op16* __restrict__ k, const op16* __restrict__ v,
+                                                                int64_t q_bs, int64_t q_ts, int64_t k_bs, int64_t k_ts, int64_t v_bs, int64_t v_ts,
+                                                                int H, int Lq, int Lk, float scale_log2, float* __restrict__ part_out, int splits) {
+  attn_fewq16_body<MAXS, true>(q, k, v, nullptr, q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, 0, 0, H, Lq, Lk, scale_log2, part_out, splits);
 }
 
 
@@ -2633,4 +2662,37 @@ extern "C" int msam2_attention_small_fwd(const void* q, int64_t q_bs, int64_t q_
     hipLaunchKernelGGL((attn_small_kernel<32>), grid, dim3(256), 0, s, (const op16*)q, (const op16*)k, (const op16*)v, (op16*)o,
                        q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, o_bs, o_ts, (int)B, (int)H, (int)Lq, (int)Lk, sl);
   return msam2_check_launch("attention_small");
+}
+
+// how many workgroups per (batch, head) msam2_attention_fewq_keysplit should get: 128 of these 1024-thread workgroups in all (one on every
+// second CU), at most 8 per (batch, head): 4 at B = 4 with 8 heads
+extern "C" int msam2_attention_fewq_keysplit_splits(int64_t B, int64_t H) {
+  if (B < 1 || H < 1) return 1;
+  return (int)max((int64_t)1, min((int64_t)8, 128 / (B * H)));
+}
+
+// The tokens -> image attention of the two-way decoder (D = 16, at most 32 queries, Lk <= 4096 image keys) with the keys of every (batch, head)
+// split over `splits` workgroups: attn_fewq16_part_kernel.  part fp32 [B * H * splits * Lq * 18]; nothing is normalised or merged.
+extern "C" int msam2_attention_fewq_keysplit(const void* q, int64_t q_bs, int64_t q_ts, const void* k, int64_t k_bs, int64_t k_ts, const void* v,
+                                             int64_t v_bs, int64_t v_ts, float* part, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t D,
+                                             int64_t splits, float scale, void* stream) {
+  MSAM2_REQUIRE(q && k && v && part, "attention_fewq_keysplit: null tensor");
+  MSAM2_REQUIRE(D == 16 && B > 0 && H > 0 && B * H <= 65535 && Lq >= 1 && Lq <= 32 && Lk >= 1 && Lk <= 4096 && splits >= 1 && splits <= 8,
+                "attention_fewq_keysplit: head dim 16, 1 .. 32 queries, 1 .. 4096 keys, 1 .. 8 splits (got D %lld, Lq %lld, Lk %lld, splits %lld)",
+                (long long)D, (long long)Lq, (long long)Lk, (long long)splits);
+  MSAM2_REQUIRE(q_ts % 8 == 0 && k_ts % 8 == 0 && v_ts % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 &&
+                    (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && ((uintptr_t)part & 3) == 0,
+                "attention_fewq_keysplit: q / k / v 16-byte aligned with strides that keep it");
+  const float sl = scale * 1.4426950408889634f;
+  const int steps = cdiv(cdiv(cdiv(Lk, splits), 16), 32);      // 32-key steps of a wave
+  const dim3 grid((unsigned)(B * H * splits));
+#define FEWQ_PART(MAXS)                                                                                                                   \
+  hipLaunchKernelGGL((attn_fewq16_part_kernel<MAXS>), grid, dim3(1024), 0, (hipStream_t)stream, (const op16*)q, (const op16*)k, (const op16*)v, \
+                     q_bs, q_ts, k_bs, k_ts, v_bs, v_ts, (int)H, (int)Lq, (int)Lk, sl, part, (int)splits)
+  if (steps <= 1) FEWQ_PART(1);
+  else if (steps <= 2) FEWQ_PART(2);
+  else if (steps <= 4) FEWQ_PART(4);
+  else FEWQ_PART(8);
+#undef FEWQ_PART
+  return msam2_check_launch("attention_fewq_keysplit");
 }

@@ -3,6 +3,7 @@ mask_decoder}.py) on the MI355X kernels.  Token-side tensors are a handful of ro
 [B*h*w, C] (fp32 residual stream + bf16 operand copies)."""
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple, Type
 
 import torch
@@ -136,6 +137,18 @@ def _image_side_projections(wc: WeightCache, key: str, keys_b: torch.Tensor, key
     return ops.gemm(keys_b, W, b, residual=R, res_mod=L)
 
 
+def _tokens_to_image_attention(attn, qp, k_img, v_img):
+    """The tokens -> image attention in front of a token-side block kernel (ops.decoder_tokens_mlp / decoder_tokens_tail): at the shapes the
+    matrix-pipe kernel serves with ONE workgroup per (image, head) -- 16-wide heads, 1024 .. 4096 image tokens -- the keys are split over enough
+    workgroups to fill the chip and the partials go to the consumer, which merges them; otherwise the attention's own launch.
+    MSAM2_NO_FEWQ_KEYSPLIT=1: never split (A/B switch)."""
+    B, Lq, C = qp.shape
+    L = k_img.shape[1]
+    if (os.environ.get("MSAM2_NO_FEWQ_KEYSPLIT") != "1" and C // attn.num_heads == 16 and Lq <= 32 and 1024 <= L <= 4096):
+        return ops.attention_fewq_keysplit(qp, k_img, v_img, attn.num_heads)
+    return attn.core(qp, k_img, v_img)
+
+
 class TwoWayAttentionBlock(nn.Module):
     """transformer.py:121-196."""
 
@@ -157,12 +170,28 @@ class TwoWayAttentionBlock(nn.Module):
         n = getattr(self, name)
         return ops.layernorm(x, v_f32(self._wc, name + "w", n.weight), v_f32(self._wc, name + "b", n.bias), n.eps, out_dtype=F32)
 
-    def run(self, queries, keys, query_pe, key_pe, B, T, L, keys_b=None):
+    def tokens_fused(self, B: int, T: int, fused_tokens: bool) -> bool:
+        """Does `run` take the token-side block kernels (ops.decoder_tokens_*)?  Only when the caller asks (the inference
+        decoder: a 16-bit value that moves by an ulp moves the training fixtures), the library is built for this block and
+        MSAM2_NO_FUSED_DEC_TOKENS=1 (A/B switch) is not set."""
+        if not fused_tokens or os.environ.get("MSAM2_NO_FUSED_DEC_TOKENS") == "1":
+            return False
+        sa, ca, ia, mlp = self.self_attn, self.cross_attn_token_to_image, self.cross_attn_image_to_token, self.mlp
+        if not (sa.num_heads == ca.num_heads == ia.num_heads and ca.internal_dim == ia.internal_dim):
+            return False
+        return ops.decoder_tokens_supported(sa.embedding_dim, sa.num_heads, sa.internal_dim, ca.internal_dim, mlp.layers[0].out_features,
+                                            mlp.num_layers, mlp._act_code, B, T)
+
+    def run(self, queries, keys, query_pe, key_pe, B, T, L, keys_b=None, fused_tokens=False, final_q=None):
         """queries/query_pe fp32 [B*T, C]; keys fp32 [B*L, C]; key_pe fp32 [L, C] (shared over the batch); keys_b: the 16-bit copy of keys when
-        the caller has it (the previous block's norm4 writes both).  Returns (queries, keys, 16-bit keys)."""
+        the caller has it (the previous block's norm4 writes both).  fused_tokens: take the token-side block kernels where they are built
+        (`tokens_fused`); final_q = (16-bit weight, fp32 bias) of the final attention's q_proj: the last block's kernel then also projects
+        queries + query_pe with it.  Returns (queries, keys, 16-bit keys, that projection or None)."""
         C = queries.shape[1]
         q3 = lambda t, n: t.view(B, n, -1)
         sa, ca, ia, wc = self.self_attn, self.cross_attn_token_to_image, self.cross_attn_image_to_token, self._wc
+        if self.tokens_fused(B, T, fused_tokens):
+            return self._run_tokens_fused(queries, keys, query_pe, key_pe, B, T, L, keys_b, final_q)
         # token-side projections read the fp32 residual stream directly (ops.gemm_tokens: "+ query_pe" and the 16-bit conversion
         # happen in the operand load; q | k | v of one attention are one launch)
         fused = B * T <= 32 and C % 32 == 0 and sa.internal_dim % 32 == 0 and ia.internal_dim % 32 == 0
@@ -211,14 +240,44 @@ class TwoWayAttentionBlock(nn.Module):
             o = ia.core(q3(q_img, L), q3(ia.proj("k", qb), T), q3(ia.proj("v", to_bf16(queries)), T))
         n4 = self.norm4          # fp32 rows (the residual stream) and their 16-bit copy (the next projections' operand) from one launch
         keys, keys16 = ops.layernorm_dual(ia.out(o, keys), v_f32(wc, "norm4w", n4.weight), v_f32(wc, "norm4b", n4.bias), n4.eps)
-        return queries, keys, keys16
+        return queries, keys, keys16, None
+
+    def _run_tokens_fused(self, queries, keys, query_pe, key_pe, B, T, L, keys_b, final_q):
+        """`run` with the token side in three launches (self block; MLP block in two) instead of eleven; the image side and both cross
+        attentions are the launches of `run`.  Same weights out of the same cache entries."""
+        q3 = lambda t, n: t.view(B, n, -1)
+        sa, ca, ia, wc = self.self_attn, self.cross_attn_token_to_image, self.cross_attn_image_to_token, self._wc
+        ln = lambda name: (v_f32(wc, name + "w", getattr(self, name).weight), v_f32(wc, name + "b", getattr(self, name).bias), getattr(self, name).eps)
+        H = sa.num_heads
+        queries, qp = ops.decoder_tokens_self(
+            queries, query_pe, self.skip_first_layer_pe, w_bf16(wc, "sqkv", sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight),
+            v_f32(wc, "sqkvb", sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias), w_bf16(sa._wc, "ow", sa.out_proj.weight),
+            v_f32(sa._wc, "ob", sa.out_proj.bias), *ln("norm1"), w_bf16(wc, "cqw", ca.q_proj.weight), v_f32(wc, "cqb", ca.q_proj.bias), B, T, H)
+        if keys_b is None:
+            keys_b = to_bf16(keys)
+        Cc, Ci2 = ca.internal_dim, ia.internal_dim
+        kvq = _image_side_projections(wc, "ikvq", keys_b, key_pe, L, [ca.k_proj, ca.v_proj, ia.q_proj], [True, False, True])
+        k_img, v_img, q_img = kvq[:, :Cc], kvq[:, Cc:2 * Cc], kvq[:, 2 * Cc:2 * Cc + Ci2]
+        o = _tokens_to_image_attention(ca, q3(qp, T), q3(k_img, L), q3(v_img, L))
+        l1, l2 = self.mlp.layers
+        fq_w, fq_b = final_q if final_q is not None else (None, None)
+        queries, kv, qp_final = ops.decoder_tokens_mlp(
+            o, queries, w_bf16(ca._wc, "ow", ca.out_proj.weight), v_f32(ca._wc, "ob", ca.out_proj.bias), *ln("norm2"),
+            w_bf16(wc, "m1w", l1.weight), v_f32(wc, "m1b", l1.bias), w_bf16(wc, "m2w", l2.weight), v_f32(wc, "m2b", l2.bias), *ln("norm3"),
+            query_pe, w_bf16(wc, "ikv", ia.k_proj.weight, ia.v_proj.weight), v_f32(wc, "ikvb", ia.k_proj.bias, ia.v_proj.bias), B, T, H,
+            w_fq=fq_w, b_fq=fq_b)
+        kv = kv.view(B, T, 2 * Ci2)
+        o = ia.core(q3(q_img, L), kv[:, :, :Ci2], kv[:, :, Ci2:])
+        n4 = self.norm4
+        keys, keys16 = ops.layernorm_dual(ia.out(o, keys), v_f32(wc, "norm4w", n4.weight), v_f32(wc, "norm4b", n4.bias), n4.eps)
+        return queries, keys, keys16, qp_final
 
     def forward(self, queries, keys, query_pe, key_pe):
         B, T, C = queries.shape
         L = keys.shape[1]
         assert key_pe.shape[0] == 1 or B == 1, "key_pe is the batch-shared dense position encoding"
-        q, k, _ = self.run(queries.to(F32).reshape(B * T, C).contiguous(), keys.to(F32).reshape(B * L, C).contiguous(),
-                           query_pe.to(F32).reshape(B * T, C).contiguous(), key_pe.to(F32).reshape(-1, C)[:L].contiguous(), B, T, L)
+        q, k, _, _ = self.run(queries.to(F32).reshape(B * T, C).contiguous(), keys.to(F32).reshape(B * L, C).contiguous(),
+                              query_pe.to(F32).reshape(B * T, C).contiguous(), key_pe.to(F32).reshape(-1, C)[:L].contiguous(), B, T, L)
         return q.view(B, T, C), k.view(B, L, C)
 
 
@@ -237,27 +296,45 @@ class TwoWayTransformer(nn.Module):
         self.norm_final_attn = nn.LayerNorm(embedding_dim)
         self._wc = WeightCache()
 
-    def run(self, keys, key_pe, tokens, B, T, L):
-        """keys fp32 [B*L, C] tokens of the image embedding; key_pe fp32 [L, C]; tokens fp32 [B*T, C]."""
+    def run(self, keys, key_pe, tokens, B, T, L, fused_tokens=False):
+        """keys fp32 [B*L, C] tokens of the image embedding; key_pe fp32 [L, C]; tokens fp32 [B*T, C].  fused_tokens: the token side as
+        block kernels where they are built (TwoWayAttentionBlock.tokens_fused; the inference decoder asks for it)."""
         C = tokens.shape[1]
         queries, qpe = tokens, tokens
         keys16 = None
-        for layer in self.layers:
-            queries, keys, keys16 = layer.run(queries, keys, qpe, key_pe, B, T, L, keys16)
+        fa = self.final_attn_token_to_image
+        # decided once per call and layer (the gate reads the environment and asks the library)
+        fused = [layer.tokens_fused(B, T, fused_tokens) for layer in self.layers]
+        # the final attention's query projection rides in the last block's kernel when that block AND the tail take the fused path
+        fused_tail = (bool(fused) and fused[-1] and fa.num_heads == self.layers[-1].self_attn.num_heads
+                      and fa.internal_dim == self.layers[-1].cross_attn_token_to_image.internal_dim)
+        qp = None
+        for i, layer in enumerate(self.layers):
+            if fused[i]:
+                final_q = None
+                if fused_tail and i == len(self.layers) - 1:
+                    final_q = (w_bf16(self._wc, "fqw", fa.q_proj.weight), v_f32(self._wc, "fqb", fa.q_proj.bias))
+                queries, keys, keys16, qp = layer._run_tokens_fused(queries, keys, qpe, key_pe, B, T, L, keys16, final_q)
+            else:
+                queries, keys, keys16, qp = layer.run(queries, keys, qpe, key_pe, B, T, L, keys16)
         if keys16 is None:
             keys16 = to_bf16(keys)
         self._keys16 = keys16          # the up-scaling GEMM behind the transformer takes the same operand (MaskDecoder.predict_masks_tokens)
-        fa = self.final_attn_token_to_image
         kv_img = _image_side_projections(self._wc, "fkv", keys16, key_pe, L, [fa.k_proj, fa.v_proj], [True, False])
         Cf = fa.internal_dim
         q3 = lambda t, n: t.view(B, n, -1)
+        n = self.norm_final_attn
+        if fused_tail:
+            o = _tokens_to_image_attention(fa, q3(qp, T), q3(kv_img[:, :Cf], L), q3(kv_img[:, Cf:], L))
+            queries = ops.decoder_tokens_tail(o, queries, w_bf16(fa._wc, "ow", fa.out_proj.weight), v_f32(fa._wc, "ob", fa.out_proj.bias),
+                                              v_f32(self._wc, "nw", n.weight), v_f32(self._wc, "nb", n.bias), n.eps, B, T, fa.num_heads)
+            return queries, keys
         if B * T <= 32 and fa.internal_dim % 32 == 0:
             qp = ops.gemm_tokens(queries, w_bf16(self._wc, "fqw", fa.q_proj.weight), v_f32(self._wc, "fqb", fa.q_proj.bias), addend=qpe,
                                  add_cols=fa.internal_dim)
         else:
             qp = fa.proj("q", ops.add_cast(queries.view(1, B * T, C), qpe.view(1, B * T, C), 1.0, OP16)[0])
         o = fa.core(q3(qp, T), q3(kv_img[:, :Cf], L), q3(kv_img[:, Cf:], L))
-        n = self.norm_final_attn
         queries = ops.layernorm(fa.out(o, queries), v_f32(self._wc, "nw", n.weight), v_f32(self._wc, "nb", n.bias), n.eps, out_dtype=F32)
         return queries, keys
 
@@ -312,17 +389,19 @@ class MaskDecoder(nn.Module):
         return ops.gemm(tokens_bf16, w_bf16(self._wc, f"cs{which}w", c.weight), v_f32(self._wc, f"cs{which}b", c.bias), out_dtype=out_dtype)
 
     def predict_masks_tokens(self, src_tokens: torch.Tensor, pe_tokens: torch.Tensor, sparse: torch.Tensor, feat_s0: torch.Tensor,
-                             feat_s1: torch.Tensor, B: int, h: int, w: int, shared_skips: bool = False):
+                             feat_s1: torch.Tensor, B: int, h: int, w: int, shared_skips: bool = False, fused_tokens: bool = False):
         """src_tokens fp32 [B*h*w, C] (= image embedding + dense prompt); pe_tokens fp32 [h*w, C]; sparse fp32 [B,P,C];
         feat_s0 [B*16hw, C/8], feat_s1 [B*4hw, C/4] token-major, 16-bit or fp32 (shared_skips: ONE image's [16hw, C/8] / [4hw, C/4],
-        read for all B prompt sets).  Returns (masks [B,4,4h,4w] fp32, iou [B,4], mask_tokens_out [B,4,C], object_score_logits [B,1])."""
+        read for all B prompt sets).  fused_tokens: the transformer's token side as block kernels (TwoWayTransformer.run); only the
+        inference entry `predict_masks` asks for it -- the training forwards that call this method, and the backward pass that recomputes
+        them, keep the launches (and the 16-bit roundings) they have.  Returns (masks [B,4,4h,4w] fp32, iou [B,4], mask_tokens_out [B,4,C], object_score_logits [B,1])."""
         wc = self._wc
         C = self.transformer_dim
         out_tok = wc.get("otok", [self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight],
                          lambda: torch.cat([self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight], 0).detach().float())
         T = out_tok.shape[0] + sparse.shape[1]
         tokens = torch.cat([out_tok.unsqueeze(0).expand(B, -1, -1), sparse], 1)          # data movement: the query token list (one launch)
-        hs, keys = self.transformer.run(src_tokens, pe_tokens, tokens.view(B * T, C), B, T, h * w)
+        hs, keys = self.transformer.run(src_tokens, pe_tokens, tokens.view(B * T, C), B, T, h * w, fused_tokens=fused_tokens)
         hs = hs.view(B, T, C)
         up = self.output_upscaling
         dc1_w = wc.get("dc1", [up[0].weight], lambda: up[0].weight.detach().permute(2, 3, 1, 0).reshape(-1, C).to(OP16).contiguous())
@@ -415,7 +494,7 @@ class MaskDecoder(nn.Module):
             pe = tokens_of(image_pe.to(F32))[: h * w]
             f0, f1 = high_res_features
             skip = lambda f: tokens_of(f) if (f.dtype == F32 and f.shape[1] in (32, 64)) else to_bf16(tokens_of(f))
-            return self.predict_masks_tokens(src, pe, sparse_prompt_embeddings.to(F32), skip(f0), skip(f1), B, h, w, shared_skips=True)
+            return self.predict_masks_tokens(src, pe, sparse_prompt_embeddings.to(F32), skip(f0), skip(f1), B, h, w, shared_skips=True, fused_tokens=True)
         if image_embeddings.shape[0] != n_sets:
             if cell_nums is not None:
                 cn = torch.as_tensor(cell_nums, device=image_embeddings.device).reshape(-1).long()
@@ -456,7 +535,7 @@ class MaskDecoder(nn.Module):
         f0, f1 = high_res_features
         # the skip features stay fp32 token-major (the up-scaling tail reads them as they are) when their widths are the kernel's 32 / 64
         skip = lambda f: tokens_of(f) if (f.dtype == F32 and f.shape[1] in (32, 64)) else to_bf16(tokens_of(f))
-        return self.predict_masks_tokens(src, pe, sparse_prompt_embeddings.to(F32), skip(f0), skip(f1), B, h, w)
+        return self.predict_masks_tokens(src, pe, sparse_prompt_embeddings.to(F32), skip(f0), skip(f1), B, h, w, fused_tokens=True)
 
     def forward(self, image_embeddings, image_pe, sparse_prompt_embeddings, dense_prompt_embeddings, multimask_output: bool,
                 repeat_image: bool, cell_nums=None, high_res_features: Optional[List[torch.Tensor]] = None):

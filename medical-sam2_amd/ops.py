@@ -85,6 +85,114 @@ def gemm_tokens(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     return out
 
 
+def decoder_tokens_supported(C: int, heads: int, self_dim: int, cross_dim: int, mlp_hidden: int, mlp_layers: int, mlp_act: int,
+                             B: int, T: int) -> bool:
+    """True when the `decoder_tokens_*` block kernels are built for this two-way block and B images of T tokens."""
+    return bool(lib().msam2_decoder_tokens_supported(C, heads, self_dim, cross_dim, mlp_hidden, mlp_layers, mlp_act, B, T))
+
+
+def _dec_rows(name: str, t: torch.Tensor, rows: int, cols: int, dtype: torch.dtype):
+    _req(t.dtype == dtype and t.shape == (rows, cols) and t.is_contiguous(), f"{name} must be a contiguous {dtype} [{rows}, {cols}]")
+
+
+def attention_fewq_keysplit(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, splits: Optional[int] = None):
+    """Tokens -> image attention of the two-way decoder (head dim 16, q [B, Lq <= 32, C], k / v [B, Lk <= 4096, C], 16-bit) with every (batch,
+    head)'s keys split over `splits` workgroups (default: enough to fill the chip).  Returns (fp32 partials [B*heads*splits, Lq, 18], splits) for
+    `decoder_tokens_mlp` / `decoder_tokens_tail`, which merge them; nothing is normalised here."""
+    B, Lq, C = q.shape
+    Lk = k.shape[1]
+    for t in (q, k, v):
+        _req(t.dtype == OP16 and t.stride(2) == 1, "attention_fewq_keysplit tensors must be 16-bit (ops.OP16), channel-contiguous")
+    if splits is None:
+        splits = int(lib().msam2_attention_fewq_keysplit_splits(B, heads))
+    part = torch.empty(B * heads * splits, Lq, 18, dtype=F32, device=q.device)
+    check(lib().msam2_attention_fewq_keysplit(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1), _p(v), v.stride(0), v.stride(1),
+                                              _p(part), B, heads, Lq, Lk, C // heads, splits, 1.0 / math.sqrt(C // heads), _stream()))
+    return part, splits
+
+
+def _dec_attn_out(name: str, o, R: int, T: int, C: int, heads: int):
+    """the attention output a token kernel takes: 16-bit rows [R, C/2] -> (o, None, 0); (partials, splits) of `attention_fewq_keysplit` -> (None, partials, splits)"""
+    if isinstance(o, tuple):
+        part, splits = o
+        _req(part.dtype == F32 and part.is_contiguous() and part.shape == ((R // T) * heads * splits, T, 18), f"{name}: partials must be fp32 [B*heads*splits, T, 18]")
+        return None, part, splits
+    _dec_rows(f"{name}: o", o, R, C // 2, OP16)
+    return o, None, 0
+
+
+def decoder_tokens_self(queries: torch.Tensor, query_pe: torch.Tensor, skip_first_layer_pe: bool, w_qkv: torch.Tensor, b_qkv: torch.Tensor,
+                        w_out: torch.Tensor, b_out: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float, w_cq: torch.Tensor,
+                        b_cq: torch.Tensor, B: int, T: int, heads: int):
+    """Self-attention half of a two-way block on the token rows (fp32 [B*T, C]) as one launch: returns (queries after norm1, fp32;
+    the tokens -> image query projection of queries + query_pe, 16-bit [B*T, C/2])."""
+    R, C = B * T, queries.shape[1]
+    _dec_rows("decoder_tokens_self: queries", queries, R, C, F32)
+    _dec_rows("decoder_tokens_self: query_pe", query_pe, R, C, F32)
+    _dec_rows("decoder_tokens_self: w_qkv", w_qkv, 3 * C, C, OP16)
+    _dec_rows("decoder_tokens_self: w_out", w_out, C, C, OP16)
+    _dec_rows("decoder_tokens_self: w_cq", w_cq, C // 2, C, OP16)
+    for v, n in ((b_qkv, 3 * C), (b_out, C), (ln_w, C), (ln_b, C), (b_cq, C // 2)):
+        _req(v.dtype == F32 and v.is_contiguous() and v.numel() == n, "decoder_tokens_self: biases and LayerNorm vectors are fp32, contiguous")
+    out = torch.empty(R, C, dtype=F32, device=queries.device)
+    qp = torch.empty(R, C // 2, dtype=OP16, device=queries.device)
+    check(lib().msam2_decoder_tokens_self(_p(queries), _p(query_pe), int(bool(skip_first_layer_pe)), _p(w_qkv), _p(b_qkv), _p(w_out), _p(b_out),
+                                          _p(ln_w), _p(ln_b), eps, _p(w_cq), _p(b_cq), _p(out), _p(qp), B, T, C, heads, _stream()))
+    return out, qp
+
+
+def decoder_tokens_mlp(o, queries: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, ln2_w: torch.Tensor, ln2_b: torch.Tensor,
+                       eps2: float, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, ln3_w: torch.Tensor,
+                       ln3_b: torch.Tensor, eps3: float, query_pe: torch.Tensor, w_kv: torch.Tensor, b_kv: torch.Tensor, B: int, T: int,
+                       heads: int, w_fq: Optional[torch.Tensor] = None, b_fq: Optional[torch.Tensor] = None):
+    """MLP half of a two-way block on the token rows as two launches: o (16-bit [B*T, C/2], the tokens -> image attention's output, or the
+    (partials, splits) pair of `attention_fewq_keysplit`) ->
+    (queries after norm3, fp32; the image -> token k | v projection, 16-bit [B*T, C]; with w_fq / b_fq the final attention's query
+    projection, 16-bit [B*T, C/2], else None).  The workspace of the fc2 partials is allocated per call."""
+    R, C = B * T, queries.shape[1]
+    hidden = w1.shape[0]
+    o, o_part, splits = _dec_attn_out("decoder_tokens_mlp", o, R, T, C, heads)
+    _dec_rows("decoder_tokens_mlp: queries", queries, R, C, F32)
+    _dec_rows("decoder_tokens_mlp: query_pe", query_pe, R, C, F32)
+    _dec_rows("decoder_tokens_mlp: w_out", w_out, C, C // 2, OP16)
+    _dec_rows("decoder_tokens_mlp: w1", w1, hidden, C, OP16)
+    _dec_rows("decoder_tokens_mlp: w2", w2, C, hidden, OP16)
+    _dec_rows("decoder_tokens_mlp: w_kv", w_kv, C, C, OP16)
+    vecs = [(b_out, C), (ln2_w, C), (ln2_b, C), (b1, hidden), (b2, C), (ln3_w, C), (ln3_b, C), (b_kv, C)]
+    _req((w_fq is None) == (b_fq is None), "decoder_tokens_mlp: w_fq and b_fq come together")
+    if w_fq is not None:
+        _dec_rows("decoder_tokens_mlp: w_fq", w_fq, C // 2, C, OP16)
+        vecs.append((b_fq, C // 2))
+    for v, n in vecs:
+        _req(v.dtype == F32 and v.is_contiguous() and v.numel() == n, "decoder_tokens_mlp: biases and LayerNorm vectors are fp32, contiguous")
+    dev = queries.device
+    mid = torch.empty(R, C, dtype=F32, device=dev)
+    out = torch.empty(R, C, dtype=F32, device=dev)
+    kv = torch.empty(R, C, dtype=OP16, device=dev)
+    qp = torch.empty(R, C // 2, dtype=OP16, device=dev) if w_fq is not None else None
+    nbytes = max(int(lib().msam2_decoder_tokens_workspace_bytes(B, T)), 16)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().msam2_decoder_tokens_mlp(_p(o), _p(o_part), splits, _p(queries), _p(w_out), _p(b_out), _p(ln2_w), _p(ln2_b), eps2, _p(w1), _p(b1), _p(w2), _p(b2),
+                                         _p(ln3_w), _p(ln3_b), eps3, _p(query_pe), _p(w_kv), _p(b_kv), _p(w_fq), _p(b_fq), _p(mid), _p(out),
+                                         _p(kv), _p(qp), _p(ws), nbytes, B, T, C, heads, hidden, _stream()))
+    return out, kv, qp
+
+
+def decoder_tokens_tail(o, queries: torch.Tensor, w_out: torch.Tensor, b_out: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor,
+                        eps: float, B: int, T: int, heads: int) -> torch.Tensor:
+    """End of the two-way transformer on the token rows: LayerNorm(queries + o @ w_out^T + b_out), fp32 [B*T, C], one launch; o as
+    `decoder_tokens_mlp` takes it."""
+    R, C = B * T, queries.shape[1]
+    o, o_part, splits = _dec_attn_out("decoder_tokens_tail", o, R, T, C, heads)
+    _dec_rows("decoder_tokens_tail: queries", queries, R, C, F32)
+    _dec_rows("decoder_tokens_tail: w_out", w_out, C, C // 2, OP16)
+    for v in (b_out, ln_w, ln_b):
+        _req(v.dtype == F32 and v.is_contiguous() and v.numel() == C, "decoder_tokens_tail: bias and LayerNorm vectors are fp32 [C], contiguous")
+    out = torch.empty(R, C, dtype=F32, device=queries.device)
+    check(lib().msam2_decoder_tokens_tail(_p(o), _p(o_part), splits, _p(queries), _p(w_out), _p(b_out), _p(ln_w), _p(ln_b), eps, _p(out), B, T, C, heads, _stream()))
+    return out
+
+
 def gemm_pool2x2(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], B: int, H: int, W: int) -> torch.Tensor:
     """fp32 [B*(H/2)*(W/2), N] = maxpool2x2(a @ w^T + bias) over the [B,H,W] token image a [B*H*W, K] (16-bit, K-contiguous)."""
     _req(a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1] and a.shape[0] == B * H * W, "gemm_pool2x2 shapes")
