@@ -30,6 +30,18 @@
 // Rows past M are clamped on load and masked on store.  Every wave runs the same number of barriers.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage): 155 VGPRs, 53 SGPRs in both builds, no scratch, one workgroup per CU by its 112 KB of LDS.
 // Measured inside the benchmark step: K = 384 18.1 us against 17.9 + 9.1 for the pair, K = 1536 43.7 against 36.0 + 9.1.
+//
+// The figures above are those of the N = 384 instance, <384, 0>.  The memory attention's layers run the same tile at
+// N = 256 -- two accumulators per wave, 4 W pieces per wave and stage, a 40 KB stage, the epilogue tile [64][260] -- in two forms:
+//   * <256, 0>: A through the ring as above (K = 64, 256, 2048; nk = 1 runs: no next tile is ever issued);
+//   * <256, 64>, <256, 256> ("merged"): A[M, K] is the merge of split-KV attention partials and exists in LDS only.  Before the main loop
+//     every thread merges the 16-byte chunks it owns with attn_merge_kernel's arithmetic (attention.hip) and stores them into K / 64
+//     RESIDENT 8 KB images in front of the ring; the ring then carries W alone (32 KB stages), so the prefetch's throw-away pieces and
+//     the next W tile never touch an image.  The epilogue tile aliases images and ring behind the barrier that ends the main loop.
+// The arithmetic the new instances restate (the merge, the LayerNorm) is compiled with contraction off and its fused multiply-adds
+// spelled as the restated kernels' listings show them; <384, 0> keeps the source form it was measured and tested with.
+// Registers: <256, 0> 92, <256, 64> 91, <256, 256> 190 VGPRs (a thread's 4 x 8 partial chunks are loaded up front), 53 - 55 SGPRs, 80 / 72
+// / 96 KB of LDS, no scratch in both builds.  In the step: 34.3 -> 17.0 us (K = 256) and 32.5 -> 12.2 us (K = 64) per chain of three launches.
 #include "common.h"
 #include <stdlib.h>
 
@@ -45,21 +57,60 @@ struct RowLnParams {
   int64_t lda, ldw, ldr, ldc, ldy;
   int M, K;
   float eps;
+  // the "merged" A source (MD != 0): split-KV partials in msam2_attention_workspace_bytes' layout with H = 1, rows = M, D = K
+  const op16* P;         // [splits][M][K] each split's normalised output
+  const float* ML;       // [splits][M][2] its (max, sum)
+  int splits;            // 2 .. 8
 };
 
-template <int N>
+// layernorm_kernel's row arithmetic with every rounding WRITTEN OUT, as conv_mfma.hip states it from that kernel's listings (the same in
+// every instance and in both builds): the instances of this file that are new state it instead of leaving the pairing of multiplies and
+// adds to -ffp-contract=fast; the N = 384 instance keeps the source form it was measured and tested with.
+template <int CH, int N>
+__device__ __forceinline__ void rowln_stats(const float (&v)[CH][4], float eps, float& mean, float& rstd) {
+#pragma clang fp contract(off)
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < CH; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += v[j][e];
+  group16_add(s);
+  mean = s / N;
+  const float d0 = v[0][0] - mean, d1 = v[0][1] - mean;
+  float q = d1 * d1;
+  q = __builtin_fmaf(d0, d0, q);
+#pragma unroll
+  for (int i = 2; i < CH * 4; ++i) {
+    const float d = v[i >> 2][i & 3] - mean;
+    q = __builtin_fmaf(d, d, q);
+  }
+  group16_add(q);
+  rstd = 1.0f / sqrtf(q / N + eps);
+}
+__device__ __forceinline__ float rowln_value(float x, float mean, float rstd, float w, float b) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(w, rstd * (x - mean), b);
+}
+
+// MD = 0: A is a 16-bit matrix that goes through the ring with W.  MD = 64 / 256 (= K): A is built in LDS from split-KV partials.
+template <int N, int MD>
 __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Img128 Img;
+  constexpr bool MERGED = MD != 0;
   constexpr int BM = 64, BK = 64, NST = 2, KS = BK / 16;
-  constexpr int A_BYTES = BM * BK * 2, STAGE_BYTES = (BM + N) * BK * 2;    // 8 KB + 48 KB
+  constexpr int A_BYTES = BM * BK * 2;                                     // 8 KB
+  constexpr int RES_BYTES = MERGED ? (MD / BK) * A_BYTES : 0;              // merged: the A images of the whole K, resident in front of the ring
+  constexpr int W_OFF = MERGED ? 0 : A_BYTES;                              // where W starts inside a stage
+  constexpr int STAGE_BYTES = W_OFF + N * BK * 2;                          // N = 384: 8 KB + 48 KB
   constexpr int WPW = N / Img::PIECE_ROWS / 8;       // W pieces per wave and stage: 6
   constexpr int FN = N / 4 / 32;                     // 32-column accumulators per wave: 3
   constexpr int TLD = N + 4;                         // floats per row of the epilogue tile
   constexpr int CH = N / 64;                         // 4-element chunks per lane and row: 6
   static_assert(N % 128 == 0 && WPW * 8 * Img::PIECE_ROWS == N && BM == 8 * Img::PIECE_ROWS, "8 waves share the pieces of a stage evenly");
-  static_assert(BM * TLD * 4 <= NST * STAGE_BYTES, "the epilogue tile aliases the ring");
+  static_assert(BM * TLD * 4 <= RES_BYTES + NST * STAGE_BYTES, "the epilogue tile aliases the A images and the ring");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
+  unsigned char* const ring = lds + RES_BYTES;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int ws = wave >> 2, wq = wave & 3;           // row slab of 32, column quarter of N / 4
@@ -85,18 +136,18 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
   }
   const int nk = p.K / BK;
   auto issue = [&](int kt) {
-    unsigned char* base = lds + (kt % NST) * STAGE_BYTES;
+    unsigned char* base = ring + (kt % NST) * STAGE_BYTES;
     const unsigned so = (unsigned)kt * BK * 2;
-    glds16(a_rsrc, base + wave * 1024, offsA, so);
+    if constexpr (!MERGED) glds16(a_rsrc, base + wave * 1024, offsA, so);
 #pragma unroll
-    for (int i = 0; i < WPW; ++i) glds16(w_rsrc, base + A_BYTES + (wave * WPW + i) * 1024, offsW[i], so);
+    for (int i = 0; i < WPW; ++i) glds16(w_rsrc, base + W_OFF + (wave * WPW + i) * 1024, offsW[i], so);
   };
 
   {
     // this workgroup's share of W (rows 12 j .. 12 j + 11, j = its place among the 32 workgroups of its XCD) into the XCD's L2, through
     // throw-away pieces into the ring's last stage: older than tile 0, so landed before the first barrier lets anybody fill that stage
     const int j = (blockIdx.x >> 3) & 31, cpr = p.K >> 3, n = (N / 32) * cpr;
-    unsigned char* dst = lds + (NST - 1) * STAGE_BYTES + wave * 1024;
+    unsigned char* dst = ring + (NST - 1) * STAGE_BYTES + wave * 1024;
     for (int i = wave; i * 64 < n; i += 8) {
       const int q = min(i * 64 + lane, n - 1);
       const int row = j * (N / 32) + q / cpr, c = q - (q / cpr) * cpr;
@@ -114,21 +165,86 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
 #pragma unroll
   for (int j = 0; j < FN; ++j) {
     const int rb = wq * (N / 4) + j * 32 + r;
-    offB[j] = A_BYTES + rb * Img::ROW_BYTES;
+    offB[j] = W_OFF + rb * Img::ROW_BYTES;
     swzB[j] = Img::swz(rb);
   }
 
   issue(0);
+  if constexpr (MERGED) {
+    // The A tile from the partials, behind the W pieces already in flight: attn_merge_kernel's `splits <= G` branch (attention.hip) for this
+    // workgroup's 64 rows -- every pair and every partial chunk of a thread loaded up front (split index clamped, the upper four only
+    // where there are more than four splits), then its arithmetic in its order with the contraction ITS listings show, in both builds:
+    // w = l * e, L = fma(l, e, L), acc = fma(w, O, acc), o = f2op(acc * (1 / L)).  Thread (row = tid / 8, c8 = tid % 8) owns the 16-byte
+    // chunk c8 of every 64-wide k image of its row.  These loads are the newest on the in-order counter: the compiler's wait for them
+    // covers the DMA pieces too, and the loop's own wait_vmcnt<0> + barrier then orders the image stores for every wave.
+#pragma clang fp contract(off)
+    typedef float f32x2_ __attribute__((ext_vector_type(2)));
+    constexpr int G = 8, KI = MD / BK;
+    const int mrow = tid >> 3, c8 = tid & 7;
+    const int64_t mg = min(m0 + mrow, (int64_t)p.M - 1);
+    f32x2_ ml[G];
+    op16x8 t[G][KI];
+    auto load = [&](int u) {
+      const int64_t at = (int64_t)min(u, p.splits - 1) * p.M + mg;
+      ml[u] = *reinterpret_cast<const f32x2_*>(p.ML + at * 2);
+#pragma unroll
+      for (int i = 0; i < KI; ++i) t[u][i] = *reinterpret_cast<const op16x8*>(p.P + at * MD + i * BK + c8 * 8);
+    };
+#pragma unroll
+    for (int u = 0; u < G / 2; ++u) load(u);
+    if (p.splits > G / 2) {
+#pragma unroll
+      for (int u = G / 2; u < G; ++u) load(u);
+    } else {
+#pragma unroll
+      for (int u = G / 2; u < G; ++u) {
+        ml[u] = ml[0];
+#pragma unroll
+        for (int i = 0; i < KI; ++i) t[u][i] = t[0][i];
+      }
+    }
+    float Mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+      if (u < p.splits) Mx = fmaxf(Mx, ml[u][0]);
+    float L = 0.f, macc[KI][8];
+#pragma unroll
+    for (int i = 0; i < KI; ++i)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) macc[i][e] = 0.f;
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      if (u < p.splits && ml[u][0] != -INFINITY) {
+        const float ex = __builtin_amdgcn_exp2f(ml[u][0] - Mx);
+        const float w = ml[u][1] * ex;
+        L = __builtin_fmaf(ml[u][1], ex, L);
+#pragma unroll
+        for (int i = 0; i < KI; ++i)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) macc[i][e] = __builtin_fmaf(w, op2f(t[u][i][e]), macc[i][e]);
+      }
+    }
+    const float inv = 1.f / L;
+#pragma unroll
+    for (int i = 0; i < KI; ++i) {
+      op16x8 o;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f2op(macc[i][e] * inv);
+      *reinterpret_cast<op16x8*>(lds + i * A_BYTES + mrow * Img::ROW_BYTES + ((c8 ^ Img::swz(mrow)) << 4)) = o;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the image stores have left this wave before it meets the first barrier
+  }
   for (int kt = 0; kt < nk; ++kt) {
     wait_vmcnt<0>();                                     // this wave's 7 pieces of tile kt (and everything older) have landed
     __builtin_amdgcn_s_barrier();                        // tile kt visible to all waves; the stage of tile kt - 1 is no longer read
     if (kt + 1 < nk) issue(kt + 1);
-    const unsigned char* sb = lds + (kt % NST) * STAGE_BYTES;
+    const unsigned char* sb = ring + (kt % NST) * STAGE_BYTES;
+    const unsigned char* sa = MERGED ? lds + kt * A_BYTES : sb;   // merged: the resident image of this k-step
     op16x8 af[KS], bfr[KS][FN];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int c = 2 * ks + h;
-      af[ks] = *reinterpret_cast<const op16x8*>(sb + offA + ((c ^ swzA) << 4));
+      af[ks] = *reinterpret_cast<const op16x8*>(sa + offA + ((c ^ swzA) << 4));
 #pragma unroll
       for (int j = 0; j < FN; ++j) bfr[ks][j] = *reinterpret_cast<const op16x8*>(sb + offB[j] + ((c ^ swzB[j]) << 4));
     }
@@ -187,23 +303,28 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
   // layernorm_kernel's arithmetic on the row (C = N, every chunk inside the row)
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
-    float s = 0.f;
+    float mean, rstd;
+    if constexpr (N == 384) {
+      float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < CH; ++j)
+      for (int j = 0; j < CH; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s += v[ps][j][e];
-    group16_add(s);
-    const float mean = s / N;
-    float q = 0.f;
+        for (int e = 0; e < 4; ++e) s += v[ps][j][e];
+      group16_add(s);
+      mean = s / N;
+      float q = 0.f;
 #pragma unroll
-    for (int j = 0; j < CH; ++j)
+      for (int j = 0; j < CH; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[ps][j][e] - mean;
-        q += d * d;
-      }
-    group16_add(q);
-    const float rstd = 1.0f / sqrtf(q / N + p.eps);
+        for (int e = 0; e < 4; ++e) {
+          const float d = v[ps][j][e] - mean;
+          q += d * d;
+        }
+      group16_add(q);
+      rstd = 1.0f / sqrtf(q / N + p.eps);
+    } else {
+      rowln_stats<CH, N>(v[ps], p.eps, mean, rstd);
+    }
     if (grow[ps] < p.M) {
       op16* yr = p.Y + grow[ps] * p.ldy;
 #pragma unroll
@@ -211,7 +332,9 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
         op16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float u = (v[ps][j][e] - mean) * rstd * ww[j][e] + bb[j][e];
+          float u;
+          if constexpr (N == 384) u = (v[ps][j][e] - mean) * rstd * ww[j][e] + bb[j][e];
+          else u = rowln_value(v[ps][j][e], mean, rstd, ww[j][e], bb[j][e]);
           o[e] = f2out<op16>(u);
         }
         *reinterpret_cast<op16x4*>(yr + (l16 + 16 * j) * 4) = o;
@@ -221,14 +344,29 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
 #endif
 }
 
-extern "C" int msam2_gemm_residual_layernorm_supported(int64_t N, int64_t K) { return (N == 384 && K > 0 && K % 64 == 0) ? 1 : 0; }
+template <int N, int MD>
+static int launch_rowln(const RowLnParams& p, void* stream, const char* what) {
+  constexpr int LDS = (MD / 64) * 8192 + 2 * ((MD ? 0 : 64) + N) * 64 * 2;   // resident A images (merged) + the two stages of the ring
+  ensure_dyn_lds<gemm_rowln_kernel<N, MD>>(LDS);
+  hipLaunchKernelGGL((gemm_rowln_kernel<N, MD>), dim3(cdiv(p.M, 64)), dim3(512), LDS, (hipStream_t)stream, p);
+  return msam2_check_launch(what);
+}
+
+// N = 384: every K % 64 == 0 (Hiera stage 3).  N = 256: the three reduction lengths of the memory attention's layers (the attention
+// out-projection, the value-folded one, linear2); other K at this width are not instantiated paths of the product and stay refused.
+extern "C" int msam2_gemm_residual_layernorm_supported(int64_t N, int64_t K) {
+  if (N == 384) return (K > 0 && K % 64 == 0) ? 1 : 0;
+  if (N == 256) return (K == 64 || K == 256 || K == 2048) ? 1 : 0;
+  return 0;
+}
 
 extern "C" int msam2_gemm_residual_layernorm(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* R32,
                                              int64_t ldr, float* C32, int64_t ldc, const float* ln_w, const float* ln_b, float eps, void* Y16,
                                              int64_t ldy, int64_t M, int64_t N, int64_t K, void* stream) {
   MSAM2_REQUIRE(A && W && R32 && C32 && ln_w && ln_b && Y16, "gemm_residual_layernorm: null operand");
-  MSAM2_REQUIRE(msam2_gemm_residual_layernorm_supported(N, K), "gemm_residual_layernorm: N=%lld K=%lld is not built (N = 384, K %% 64 == 0)",
-                (long long)N, (long long)K);
+  MSAM2_REQUIRE(msam2_gemm_residual_layernorm_supported(N, K),
+                "gemm_residual_layernorm: N=%lld K=%lld is not built (N = 384 with K %% 64 == 0; N = 256 with K = 64, 256 or 2048)", (long long)N,
+                (long long)K);
   MSAM2_REQUIRE(M > 0 && M < (1ll << 31) - 64, "gemm_residual_layernorm: M=%lld", (long long)M);
   MSAM2_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "gemm_residual_layernorm: lda, ldw must be multiples of 8 (16-byte rows), >= K");
   MSAM2_REQUIRE(ldr % 4 == 0 && ldc % 4 == 0 && ldy % 4 == 0 && ldr >= N && ldc >= N && ldy >= N,
@@ -237,12 +375,48 @@ extern "C" int msam2_gemm_residual_layernorm(const void* A, int64_t lda, const v
                     vec_ok(4, 2, (const void*)Y16),
                 "gemm_residual_layernorm: A, W, bias, R32, C32, ln_w, ln_b must be 16-byte aligned, Y16 8-byte");
   MSAM2_REQUIRE(M * lda * 2 < (1ll << 31) && N * ldw * 2 < (1ll << 31), "gemm_residual_layernorm: A / W beyond the 2 GB of a buffer descriptor's offsets");
-  RowLnParams p;
+  RowLnParams p = {};
   p.A = (const op16*)A; p.W = (const op16*)W; p.bias = bias; p.R = R32; p.C = C32; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = (op16*)Y16;
   p.lda = lda; p.ldw = ldw; p.ldr = ldr; p.ldc = ldc; p.ldy = ldy;
   p.M = (int)M; p.K = (int)K; p.eps = eps;
-  constexpr int LDS = 2 * (64 + 384) * 64 * 2;
-  ensure_dyn_lds<gemm_rowln_kernel<384>>(LDS);
-  hipLaunchKernelGGL((gemm_rowln_kernel<384>), dim3(cdiv(M, 64)), dim3(512), LDS, (hipStream_t)stream, p);
-  return msam2_check_launch("gemm_residual_layernorm");
+  if (N == 384) return launch_rowln<384, 0>(p, stream, "gemm_residual_layernorm");
+  return launch_rowln<256, 0>(p, stream, "gemm_residual_layernorm");
+}
+
+extern "C" size_t msam2_attention_workspace_bytes(int64_t Bz, int64_t H, int64_t Lq, int64_t D, int splits);
+
+extern "C" int msam2_gemm_merged_residual_layernorm_supported(int64_t N, int64_t D, int splits) {
+  return (N == 256 && (D == 64 || D == 256) && splits >= 2 && splits <= 8) ? 1 : 0;
+}
+
+// msam2_gemm_residual_layernorm whose A[M, D] is the merge of `splits` split-KV partials: `workspace` is what an attention call with a
+// negative split count left behind for one head and M = B * Lq query rows (msam2_attention_workspace_bytes(B, 1, Lq, D, splits), splits =
+// the EFFECTIVE count).  The merged rows exist in LDS only.
+extern "C" int msam2_gemm_merged_residual_layernorm(const void* workspace, size_t workspace_bytes, int splits, int64_t D, const void* W,
+                                                    int64_t ldw, const float* bias, const float* R32, int64_t ldr, float* C32, int64_t ldc,
+                                                    const float* ln_w, const float* ln_b, float eps, void* Y16, int64_t ldy, int64_t M,
+                                                    int64_t N, void* stream) {
+  MSAM2_REQUIRE(workspace && W && R32 && C32 && ln_w && ln_b && Y16, "gemm_merged_residual_layernorm: null operand");
+  MSAM2_REQUIRE(splits >= 2 && splits <= 8, "gemm_merged_residual_layernorm: splits=%d outside [2, 8]", splits);
+  MSAM2_REQUIRE(D == 64 || D == 256, "gemm_merged_residual_layernorm: D=%lld is not built (64, 256)", (long long)D);
+  MSAM2_REQUIRE(N == 256, "gemm_merged_residual_layernorm: N=%lld is not built (256)", (long long)N);
+  MSAM2_REQUIRE(M > 0 && M < (1ll << 31) - 64, "gemm_merged_residual_layernorm: M=%lld", (long long)M);
+  const size_t need = msam2_attention_workspace_bytes(1, 1, M, D, splits);
+  MSAM2_REQUIRE(workspace_bytes >= need, "gemm_merged_residual_layernorm: workspace too small (%zu of %zu bytes)", workspace_bytes, need);
+  MSAM2_REQUIRE(ldw % 8 == 0 && ldw >= D, "gemm_merged_residual_layernorm: ldw must be a multiple of 8 (16-byte rows), >= D");
+  MSAM2_REQUIRE(ldr % 4 == 0 && ldc % 4 == 0 && ldy % 4 == 0 && ldr >= N && ldc >= N && ldy >= N,
+                "gemm_merged_residual_layernorm: ldr, ldc, ldy must be multiples of 4, >= N");
+  MSAM2_REQUIRE(vec_ok(8, 2, workspace, W) && vec_ok(4, 4, (const void*)bias, (const void*)R32, (const void*)C32, (const void*)ln_w, (const void*)ln_b) &&
+                    vec_ok(4, 2, (const void*)Y16),
+                "gemm_merged_residual_layernorm: workspace, W, bias, R32, C32, ln_w, ln_b must be 16-byte aligned, Y16 8-byte");
+  MSAM2_REQUIRE(N * ldw * 2 < (1ll << 31), "gemm_merged_residual_layernorm: W beyond the 2 GB of a buffer descriptor's offsets");
+  RowLnParams p = {};
+  p.W = (const op16*)W; p.bias = bias; p.R = R32; p.C = C32; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = (op16*)Y16;
+  p.ldw = ldw; p.ldr = ldr; p.ldc = ldc; p.ldy = ldy;
+  p.M = (int)M; p.K = (int)D; p.eps = eps;
+  p.P = (const op16*)workspace;
+  p.ML = reinterpret_cast<const float*>(p.P + (size_t)splits * M * D);
+  p.splits = splits;
+  if (D == 64) return launch_rowln<256, 64>(p, stream, "gemm_merged_residual_layernorm");
+  return launch_rowln<256, 256>(p, stream, "gemm_merged_residual_layernorm");
 }

@@ -37,6 +37,29 @@ def _stage_list(text: str) -> frozenset:
 _FUSED_MASK_DS_STAGES = _stage_list(_os.environ.get("MSAM2_FUSED_MASK_DS_STAGES", "2,3,4"))
 
 
+# A/B switch: the tails of a memory-attention layer as the launches they were -- split-KV merge, out-projection with fp32 residual, the next
+# LayerNorm -- instead of one gemm_rowln_kernel each, and the list of the parts that take the fusion: "sa" (self-attention
+# merge + out_proj + norm2), "ca" (cross-attention merge + folded out_proj + norm3), "ffn" (linear2 + the next layer's norm1).  A part that
+# does not beat its launches inside the step is taken off the default list
+_FUSED_TAIL = _os.environ.get("MSAM2_NO_FUSED_MEMATTN_TAIL") is None
+_FUSED_TAIL_PARTS = frozenset(k.strip() for k in _os.environ.get("MSAM2_FUSED_MEMATTN_TAIL_PARTS", "sa,ca").split(",") if k.strip())
+
+
+def _tail_form(part: str, N: int, K: int, splits: int, kv_split: bool, training: bool) -> str:
+    """How the tail `part` ("sa", "ca", "ffn") of a memory-attention layer runs: "merged" (split-KV partials -> out-projection -> residual ->
+    LayerNorm in one kernel), "plain" (the same kernel reading a 16-bit A: nothing to merge) or "" (the launches it would replace).
+    N: model width; K: reduction length of the GEMM (the attention's value width for sa / ca); splits: EFFECTIVE split-KV count of the
+    attention in front (1 for ffn); kv_split: a cross-GPU key split is active (its partial + exchange + merge launches stay); training:
+    the module is in train mode.  Per-slice quantities only: never the batch."""
+    if not _FUSED_TAIL or part not in _FUSED_TAIL_PARTS or training:
+        return ""
+    if part == "ca" and kv_split:
+        return ""
+    if part != "ffn" and splits > 1:
+        return "merged" if ops.gemm_merged_residual_layernorm_supported(N, K, splits) else ""
+    return "plain" if ops.gemm_residual_layernorm_supported(N, K) else ""
+
+
 def _mask_ds_dispatched(stage: int, cin: int, cout: int) -> bool:
     """Does stage `stage` (2 .. 4) of the mask down-sampler, cin -> cout channels, run as one kernel?"""
     return _FUSED_MASK_DS and stage in _FUSED_MASK_DS_STAGES and ops.conv3x3s2_mfma_ln_gelu_supported(cin, cout)
@@ -93,6 +116,22 @@ class Attention(nn.Module):
         sp = lambda t: t.view(B, t.shape[1], H, D).permute(0, 2, 1, 3)
         o = ops.attention(sp(q), sp(k), sp(v), splits=attn_splits(B, H, Lq, k.shape[1]))
         return o.permute(0, 2, 1, 3).reshape(B * Lq, C)
+
+    def core_deferred(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: int) -> torch.Tensor:
+        """core() for one head with `splits` > 1 effective splits, stopped before the merge: the workspace with the partials."""
+        B, Lq, C = q.shape
+        sp = lambda t: t.view(B, t.shape[1], 1, C).permute(0, 2, 1, 3)
+        ws = ops.attention_workspace(B, 1, Lq, C, splits, q.device)
+        ops.attention(sp(q), sp(k), sp(v), splits=splits, workspace=ws, defer_merge=True)
+        return ws
+
+    def out_ln(self, o, residual: torch.Tensor, ln, splits: int = 1):
+        """out(o, residual) and the LayerNorm `ln` = (weight, bias, eps) of its rows from one kernel: (x fp32, rows 16-bit).  o: the
+        attention output [M, internal], or with splits > 1 the workspace core_deferred left."""
+        w, b = w_bf16(self._wc, "ow", self.out_proj.weight), v_f32(self._wc, "ob", self.out_proj.bias)
+        if splits > 1:
+            return ops.gemm_merged_residual_layernorm(o, splits, self.internal_dim, w, b, residual, *ln)
+        return ops.gemm_residual_layernorm(o, w, b, residual, *ln)
 
     def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
         assert not (self.training and self.dropout_p > 0.0), "attention dropout (train mode) is outside the forward hot path"
@@ -161,22 +200,41 @@ class RoPEAttention(Attention):
         themselves (ops.attention_kv64) and v_proj rides in the out-projection (out_folded)."""
         return _FOLD_V and self.kv_in_dim == 64 and self.internal_dim == 256 and self.num_heads == 1
 
-    def out_folded(self, o64: torch.Tensor, residual: Optional[torch.Tensor], out_dtype=F32) -> torch.Tensor:
-        """out_proj(o64 W_v^T + b_v) as ONE K = 64 GEMM: weight W_o W_v and bias W_o b_v + b_o composed in fp32."""
+    def _folded_wb(self):
+        """W_o W_v and W_o b_v + b_o composed in fp32: weight (16-bit) and bias of the value-folded out-projection"""
         ps = [self.out_proj.weight, self.out_proj.bias, self.v_proj.weight, self.v_proj.bias]
         w = self._wc.get("ovw", ps, lambda: (self.out_proj.weight.detach().float() @ self.v_proj.weight.detach().float()).to(OP16).contiguous())
         b = self._wc.get("ovb", ps, lambda: (self.out_proj.weight.detach().float() @ self.v_proj.bias.detach().float()
                                              + self.out_proj.bias.detach().float()).contiguous())
+        return w, b
+
+    def out_folded(self, o64: torch.Tensor, residual: Optional[torch.Tensor], out_dtype=F32) -> torch.Tensor:
+        """out_proj(o64 W_v^T + b_v) as ONE K = 64 GEMM: weight W_o W_v and bias W_o b_v + b_o composed in fp32."""
+        w, b = self._folded_wb()
         return ops.gemm(o64, w, b, residual=residual, out_dtype=out_dtype)
 
-    def core_folded(self, q: torch.Tensor, k: torch.Tensor, mem_v: torch.Tensor, key_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def out_folded_ln(self, o, residual: torch.Tensor, ln, splits: int = 1):
+        """out_folded(o, residual) and the LayerNorm `ln` = (weight, bias, eps) of its rows from one kernel: (x fp32, rows 16-bit).  o: the
+        attention output [M, 64], or with splits > 1 the workspace core_folded(..., defer_splits=splits) left."""
+        w, b = self._folded_wb()
+        if splits > 1:
+            return ops.gemm_merged_residual_layernorm(o, splits, 64, w, b, residual, *ln)
+        return ops.gemm_residual_layernorm(o, w, b, residual, *ln)
+
+    def core_folded(self, q: torch.Tensor, k: torch.Tensor, mem_v: torch.Tensor, key_count: Optional[torch.Tensor] = None,
+                    defer_splits: int = 0) -> torch.Tensor:
         """rotated q [B, Lq, 256], rotated k [B, Lk, 256], un-projected values mem_v [B, Lk, 64] -> 16-bit [B*Lq, 64].  key_count: int32
-        device scalar, the number of leading keys attended to when the bank is padded to a capacity Lk (ops.attention_kv64)."""
+        device scalar, the number of leading keys attended to when the bank is padded to a capacity Lk (ops.attention_kv64).
+        defer_splits > 1 (the effective split count, single rank only): stop before the merge and return the workspace with the partials."""
         from .. import parallel
         B, Lq, C = q.shape
         Lk = k.shape[1]
         q4, k4, v4 = (q.view(B, Lq, 1, C).permute(0, 2, 1, 3), k.view(B, Lk, 1, C).permute(0, 2, 1, 3),
                       mem_v.reshape(B, Lk, 1, 64).permute(0, 2, 1, 3))
+        if defer_splits > 1:
+            ws = ops.attention_workspace(B, 1, Lq, 64, defer_splits, q.device)
+            ops.attention_kv64(q4, k4, v4, splits=defer_splits, key_count=key_count, workspace=ws, defer_merge=True)
+            return ws
         splits = attn_splits(B, 1, Lq, Lk)
         kvs = parallel.current_kv_split()
         eff = ops.attention_effective_splits(Lk, splits) if kvs is not None else 1
@@ -229,22 +287,30 @@ class MemoryAttentionLayer(nn.Module):
         self.pos_enc_at_cross_attn_queries = pos_enc_at_cross_attn_queries
         self.pos_enc_at_cross_attn_keys = pos_enc_at_cross_attn_keys
         self._wc = WeightCache()
+        self.next_xn = None              # the next layer's norm1 rows, when run() was handed that norm and linear2 produced them
+
+    def _ln_args(self, name: str):
+        n = getattr(self, name)
+        return v_f32(self._wc, name + "w", n.weight), v_f32(self._wc, name + "b", n.bias), n.eps
 
     def _ln(self, name: str, x: torch.Tensor) -> torch.Tensor:
-        n = getattr(self, name)
-        return ops.layernorm(x, v_f32(self._wc, name + "w", n.weight), v_f32(self._wc, name + "b", n.bias), n.eps)
+        return ops.layernorm(x, *self._ln_args(name))
 
     def run(self, x: torch.Tensor, mem_k: torch.Tensor, mem_v: torch.Tensor, B: int, L: int, n_ptr_tokens: int,
-            key_count: Optional[torch.Tensor] = None, kk: Optional[torch.Tensor] = None) -> torch.Tensor:
+            key_count: Optional[torch.Tensor] = None, kk: Optional[torch.Tensor] = None, xn: Optional[torch.Tensor] = None,
+            next_norm=None) -> torch.Tensor:
         """x fp32 [B*L, C]; mem_k (= memory + pos) / mem_v (= memory) bf16 [B, Nk, 64]; key_count: see RoPEAttention.core_folded.
         kk: this layer's rotated key projection [B, Nk, 256] (row stride free) when the caller projected all layers' keys in one GEMM
-        (MemoryAttention.forward)."""
+        (MemoryAttention.forward).  xn: norm1(x) in 16 bits when the layer in front produced it; next_norm = (weight, bias, eps) of the
+        next layer's norm1: where linear2 takes the fused form (_tail_form "ffn") its rows are left in self.next_xn."""
+        from .. import parallel
         wc, sa, ca = self._wc, self.self_attn, self.cross_attn_image
         C = self.d_model
         Nk = mem_k.shape[1]
         tab = sa.table(L, x.device)
+        kvs = parallel.current_kv_split()
         # self attention: fused q|k|v projection, RoPE on q and k rows in place
-        t = self._ln("norm1", x)
+        t = xn if xn is not None else self._ln("norm1", x)
         w_qkv = w_bf16(wc, "sqkv", sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight)
         b_qkv = v_f32(wc, "sqkvb", sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias)
         fused_rope = _FUSED_ROPE and B * L >= 256 and L >= 128 and sa.num_heads == 1 and B * L * 3 * C * 4 < 2 ** 31
@@ -256,12 +322,18 @@ class MemoryAttentionLayer(nn.Module):
         if not fused_rope:
             ops.rope_(q, L, tab)
             ops.rope_(k, L, tab)
-        x = sa.out(sa.core(q, k, v), x)
+        # the merge of the split-KV partials, out_proj + residual and norm2 as one kernel where _tail_form says so
+        sa_splits = ops.attention_effective_splits(L, attn_splits(B, sa.num_heads, L, L))
+        form = _tail_form("sa", C, sa.internal_dim, sa_splits, kvs is not None, self.training) if sa.num_heads == 1 else ""
+        if form == "merged":
+            x, t = sa.out_ln(sa.core_deferred(q, k, v, sa_splits), x, self._ln_args("norm2"), sa_splits)
+        elif form == "plain":
+            x, t = sa.out_ln(sa.core(q, k, v), x, self._ln_args("norm2"))
+        else:
+            x = sa.out(sa.core(q, k, v), x)
+            t = self._ln("norm2", x)
         # cross attention to the memory bank (keys carry the position encoding, values do not)
-        t = self._ln("norm2", x)
         q = ca.proj_rope("q", t, B, L, L, tab)
-        from .. import parallel
-        kvs = parallel.current_kv_split()
         eff = ops.attention_effective_splits(Nk, attn_splits(B, 1, L, Nk)) if (kvs is not None and ca.folds_values()) else 1
         valid = Nk if key_count is None else (kvs.host_key_count if kvs is not None else None)
         if kk is not None:
@@ -273,16 +345,29 @@ class MemoryAttentionLayer(nn.Module):
             kk = ca.proj_rope("k", mem_k.reshape(B * Nk, -1), B, Nk, Nk - n_ptr_tokens, tab)
         if ca.folds_values():
             # O' = softmax(q k^T) M on the 64-channel memory rows; v_proj is folded into the out-projection (5/8 of the MFMA work)
-            x = ca.out_folded(ca.core_folded(q, kk, mem_v, key_count), x)
+            ca_splits = ops.attention_effective_splits(Nk, attn_splits(B, 1, L, Nk))
+            form = _tail_form("ca", C, 64, ca_splits, kvs is not None, self.training)
+            if form == "merged":
+                x, t = ca.out_folded_ln(ca.core_folded(q, kk, mem_v, key_count, defer_splits=ca_splits), x, self._ln_args("norm3"), ca_splits)
+            elif form == "plain":
+                x, t = ca.out_folded_ln(ca.core_folded(q, kk, mem_v, key_count), x, self._ln_args("norm3"))
+            else:
+                x = ca.out_folded(ca.core_folded(q, kk, mem_v, key_count), x)
+                t = self._ln("norm3", x)
         else:
             if key_count is not None:
                 raise RuntimeError("a padded memory bank (key_count) needs the value-folded cross-attention (MSAM2_NO_VALUE_FOLD is set)")
             vv = ca.proj("v", mem_v.reshape(B * Nk, -1)).view(B, Nk, C)
             x = ca.out(ca.core(q, kk, vv), x)
-        # FFN
-        t = self._ln("norm3", x)
+            t = self._ln("norm3", x)
+        # FFN; linear2 + residual and the NEXT layer's norm1 as one kernel where the caller handed that norm over and _tail_form says so
         h = ops.gemm(t, w_bf16(wc, "f1", self.linear1.weight), v_f32(wc, "f1b", self.linear1.bias), act=ops.ACT_RELU)
-        return ops.gemm(h, w_bf16(wc, "f2", self.linear2.weight), v_f32(wc, "f2b", self.linear2.bias), residual=x, out_dtype=F32)
+        w2, b2 = w_bf16(wc, "f2", self.linear2.weight), v_f32(wc, "f2b", self.linear2.bias)
+        self.next_xn = None
+        if next_norm is not None and _tail_form("ffn", C, self.dim_feedforward, 1, kvs is not None, self.training) == "plain":
+            x, self.next_xn = ops.gemm_residual_layernorm(h, w2, b2, x, *next_norm)
+            return x
+        return ops.gemm(h, w2, b2, residual=x, out_dtype=F32)
 
     def forward(self, tgt, memory, pos: Optional[torch.Tensor] = None, query_pos: Optional[torch.Tensor] = None,
                 num_k_exclude_rope: int = 0) -> torch.Tensor:
@@ -387,8 +472,13 @@ class MemoryAttention(nn.Module):
         mem_k = ops.add_cast(mem_bf, memory_pos.transpose(0, 1), 1.0, OP16)
         mem_v = ops.add_cast(mem_bf, None, 1.0, OP16)
         kk_all = self._project_all_keys(mem_k, B, L, num_obj_ptr_tokens)
+        xn = None
         for i, layer in enumerate(self.layers):
-            x = layer.run(x, mem_k, mem_v, B, L, num_obj_ptr_tokens, key_count, None if kk_all is None else kk_all[:, :, i])
+            # a layer is handed the norm1 of the one behind it (the rows linear2's kernel can leave) and the rows the one in front left
+            nxt = self.layers[i + 1]._ln_args("norm1") if i + 1 < len(self.layers) else None
+            x = layer.run(x, mem_k, mem_v, B, L, num_obj_ptr_tokens, key_count, None if kk_all is None else kk_all[:, :, i], xn=xn,
+                          next_norm=nxt)
+            xn, layer.next_xn = layer.next_xn, None
         y = ops.layernorm(x, v_f32(self._wc, "nw", self.norm.weight), v_f32(self._wc, "nb", self.norm.bias), self.norm.eps,
                           out_dtype=F32)
         return y.view(B, L, C).transpose(0, 1)

@@ -274,7 +274,8 @@ def gemm_residual_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[tor
     _req(a.dtype == OP16 and w.dtype == OP16 and a.stride(1) == 1 and w.stride(1) == 1, "gemm_residual_layernorm operands: 16-bit, K-contiguous")
     M, K = a.shape
     N = w.shape[0]
-    _req(gemm_residual_layernorm_supported(N, K), f"gemm_residual_layernorm: N = {N}, K = {K} is not built (N = 384, K % 64 == 0)")
+    _req(gemm_residual_layernorm_supported(N, K),
+         f"gemm_residual_layernorm: N = {N}, K = {K} is not built (N = 384 with K % 64 == 0; N = 256 with K = 64, 256 or 2048)")
     _req(residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1, "gemm_residual_layernorm: residual must be fp32 [M, N]")
     _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
          and (bias is None or (bias.dtype == F32 and bias.numel() == N and bias.is_contiguous())),
@@ -287,6 +288,38 @@ def gemm_residual_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[tor
          "gemm_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
     check(lib().msam2_gemm_residual_layernorm(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(residual), residual.stride(0), _p(out),
                                               out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16), out16.stride(0), M, N, K, _stream()))
+    return out, out16
+
+
+def gemm_merged_residual_layernorm_supported(N: int, D: int, splits: int) -> bool:
+    """True when `gemm_merged_residual_layernorm` is built for this output width, head dim and (effective) split count."""
+    return bool(lib().msam2_gemm_merged_residual_layernorm_supported(N, D, splits))
+
+
+def gemm_merged_residual_layernorm(workspace: torch.Tensor, splits: int, D: int, w: torch.Tensor, bias: Optional[torch.Tensor],
+                                   residual: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float, *,
+                                   out: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None):
+    """`gemm_residual_layernorm` on the rows `attention_merge` would write: `workspace` holds the partials of an attention call made
+    with defer_merge=True for one head and M = residual.shape[0] query rows, `splits` is the EFFECTIVE count (attention_effective_splits).
+    (c32, y16) have the bits of attention_merge -> gemm(fp32 + residual) -> layernorm; the merged rows are written nowhere."""
+    _req(w.dim() == 2 and w.dtype == OP16 and w.stride(1) == 1 and w.shape[1] == D, f"gemm_merged_residual_layernorm: w is 16-bit [N, {D}], K-contiguous")
+    _req(workspace.dtype == torch.uint8 and workspace.is_contiguous(), "gemm_merged_residual_layernorm: workspace is a contiguous uint8 buffer")
+    N = w.shape[0]
+    _req(residual.dim() == 2 and residual.dtype == F32 and residual.shape[1] == N and residual.stride(1) == 1,
+         "gemm_merged_residual_layernorm: residual must be fp32 [M, N]")
+    M = residual.shape[0]
+    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
+         and (bias is None or (bias.dtype == F32 and bias.numel() == N and bias.is_contiguous())),
+         "gemm_merged_residual_layernorm: bias, ln_w, ln_b are fp32 [N]")
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=w.device)
+    if out16 is None:
+        out16 = torch.empty(M, N, dtype=OP16, device=w.device)
+    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
+         "gemm_merged_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    check(lib().msam2_gemm_merged_residual_layernorm(_p(workspace), workspace.numel(), int(splits), int(D), _p(w), w.stride(0), _p(bias), _p(residual),
+                                                     residual.stride(0), _p(out), out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16),
+                                                     out16.stride(0), M, N, _stream()))
     return out, out16
 
 
