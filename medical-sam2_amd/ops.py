@@ -1410,6 +1410,49 @@ def label_overlap(pred: torch.Tensor, gt: torch.Tensor, ids) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# measurements: per-organ geometry, surface and intensity tables of a label volume and its image (csrc/measure.hip)
+MEASURE_MAX_BINS = 65536          # csrc/measure.hip MS_MAX_BINS
+MEASURE_IMAGE_TYPES = {torch.uint8: 0, torch.int16: 1}
+
+
+def label_measure(labels: torch.Tensor, ids, image: Optional[torch.Tensor] = None, hist_lo: Optional[int] = None, bins: int = 0,
+                  faces: bool = True, out=None):
+    """uint8 [D, H, W] label volume (+ the int16 / uint8 image of that shape) -> (moments int64 [n, 14], extent int32 [n, 6], vrange int32
+    [n, 2], faces int64 [n, 6] | None, hist int32 [n, bins] | None) on the device, one pass: moments = (count, Sz, Sy, Sx, Szz, Syy, Sxx, Szy,
+    Szx, Syx, Sv, Svv, below, above) over the voxels equal to ids[j] (indices z, y, x; image value v; below / above = voxels with v < hist_lo /
+    v >= hist_lo + bins; columns 10 - 13 are 0 without an image); extent = inclusive (z0, z1, y0, y1, x0, x1), -1 when absent; vrange =
+    (min v, max v), (2^31 - 1, -2^31) when absent or without an image; faces (faces=True) = interior faces per axis z, y, x (axis neighbours of
+    which exactly one is the organ), then the faces on the volume's frame per axis; hist (bins >= 1, needs the image) = voxels with
+    v == hist_lo + b.  hist_lo: None = 0.  Voxels that are 0 or not in ids belong to no organ.
+    out: the five tables of an earlier call (None where skipped), filled in place: with it the call allocates nothing and can be captured.
+    ids: host integers (checked: distinct, 1 .. 255), or the device tensor of label_ids() taken as is.  Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_measure", labels, ids, max_voxels=True)
+    dev = labels.device
+    bins, lo = int(bins), 0 if hist_lo is None else int(hist_lo)
+    _req(0 <= bins <= MEASURE_MAX_BINS, f"label_measure: bins = {bins} (0 = no histogram, else 1 .. {MEASURE_MAX_BINS})")
+    _req(-2 ** 31 <= lo < 2 ** 31, f"label_measure: hist_lo = {lo} (an int32)")
+    itype = 0
+    if image is not None:
+        _device_table("label_measure: image", image, (torch.int16, torch.uint8), (D, H, W), dev, "labels'", "int16 or uint8")
+        itype = MEASURE_IMAGE_TYPES[image.dtype]
+    _req(bins == 0 or image is not None, "label_measure: a histogram needs an image")
+    shapes = ((torch.int64, (n, 14)), (torch.int32, (n, 6)), (torch.int32, (n, 2)), (torch.int64, (n, 6)) if faces else None,
+              (torch.int32, (n, bins)) if bins else None)
+    names = ("moments", "extent", "vrange", "faces", "hist")
+    if out is None:
+        out = tuple(None if s is None else torch.empty(s[1], dtype=s[0], device=dev) for s in shapes)
+    _req(isinstance(out, (tuple, list)) and len(out) == 5, "label_measure: out must be the five tables (moments, extent, vrange, faces, hist)")
+    for name, s, t in zip(names, shapes, out):
+        if s is None:
+            _req(t is None, f"label_measure: out's {name} must be None (the table is not asked for)")
+        else:
+            _device_table(f"label_measure: out's {name}", t, s[0], s[1], dev, "labels'")
+    m, e, v, f, h = out
+    check(lib().msam2_label_measure(_p(labels), _p(ids_d), _p(image), itype, D, H, W, n, lo, bins, _p(m), _p(e), _p(v), _p(f), _p(h), _stream()))
+    return m, e, v, f, h
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # after the overlap scores: exact distance transforms and surface distances of label volumes (csrc/surface.hip)
 EDT_FEATURES = {"surface": 0, "outside": 1}
 SURFACE_WORKSPACE_BYTES = 512 << 20    # an interface default, not a measured optimum

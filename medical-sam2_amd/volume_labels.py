@@ -14,8 +14,16 @@ volume (`exclusive=True`).
 Between the label volume and its scores sits the usual post-processing, on the device as well: `clean_labels` keeps the largest component of
 every organ and drops islands (csrc/components.hip), `fill_holes` fills the cavities enclosed by an organ, 3-D or slice by slice
 (csrc/holes.hip: scipy.ndimage.binary_fill_holes per organ), and `postprocess_labels` runs the two in that order; `morph_labels` erodes,
-dilates, opens or closes every organ with a ball of a radius in millimetres (csrc/morph.hip)."""
+dilates, opens or closes every organ with a ball of a radius in millimetres (csrc/morph.hip).
+
+Where no ground truth exists the organs are measured: `organ_measurements` (csrc/measure.hip: one pass over the label volume and the
+image, five small integer tables) gives volume, extent, centroid, covariance and principal axes, the voxel-face surface area and the
+intensity statistics inside every organ (mean, spread, range, percentiles, histogram); `measurements_from_tables` is its host half,
+`measurement_errors` compares two such reports (relative volume difference, centroid distance)."""
 from __future__ import annotations
+
+import math
+from fractions import Fraction
 
 from typing import Dict, Optional, Sequence, Union
 
@@ -296,3 +304,149 @@ def surface_scores(pred: torch.Tensor, gt: torch.Tensor, obj_ids, spacing=(1.0, 
     segments = [[(torch.sort(dist[offs[j][d]: offs[j][d] + caps[j][d]]).values, counts64[j, d]) for d in range(2)]   # +inf beyond the count sorts last
                 for j in range(len(offs))]
     return _scores(segments, percentile, tolerances)
+
+
+# ---- measurements: volume, shape, surface, intensity per organ ---------------------------------------------------------------
+DEFAULT_HIST_RANGE = {torch.int16: (-1024, 3072), torch.uint8: (0, 256)}     # [lo, hi): Hounsfield units / the grey of the intake
+
+
+def _order_statistic(cum: np.ndarray, below: int, hist_lo: int, k: int) -> float:
+    """the k-th smallest value (k from 0) of an organ from its cumulative histogram (cum[b] = voxels with v <= hist_lo + b inside the range);
+    NaN when it lies in a clipped tail"""
+    k -= below
+    if k < 0 or len(cum) == 0 or k >= int(cum[-1]):
+        return float("nan")
+    return float(hist_lo + int(np.searchsorted(cum, k, side="right")))
+
+
+def measurements_from_tables(moments, extent, vrange=None, faces=None, hist=None, hist_lo: int = 0, spacing=(1.0, 1.0, 1.0),
+                             percentiles=(5, 25, 50, 75, 95)) -> dict:
+    """The report from `ops.label_measure`'s tables as numpy arrays (vrange None: no image; faces / hist None: skipped), all indexed by organ.
+
+    Geometry: "voxels" int64; "volume_mm3", "volume_ml"; "bbox" int64 [n, 6] = inclusive (z0, z1, y0, y1, x0, x1), -1 when absent; "extent_mm"
+    [n, 3]; "centroid_vox", "centroid_mm" [n, 3]: the mean of the voxel centres in (z, y, x), in indices and times the spacing;
+    "covariance_mm2" [n, 3, 3] (population covariance of the voxel centres); "principal_lengths_mm" [n, 3] = 4 sqrt(eigenvalue), descending,
+    and "principal_axes" [n, 3, 3]: row k = the unit vector (z, y, x) of the k-th longest axis, its largest component positive
+    (np.linalg.eigh of the covariance).  With faces: "surface_mm2" = interior faces times the face area per axis -- the VOXEL-FACE area: it
+    over-estimates a smooth surface (by up to sqrt(3); 1.5 on a large sphere) and depends neither on scheduling nor on a mesher;
+    "frame_faces" int64 [n, 3] = the organ's faces on the volume's frame per axis z, y, x, "touches_frame" = any of them: the field of view
+    cuts the organ, its volume is a lower bound.
+    Intensity (vrange given): "mean", "std" (population), "min", "max", "clipped" int64 [n, 2] = voxels (below, at or above) the histogram
+    range; with hist: "percentiles" [n, len(percentiles)], "percentile_bounds" [n, len(percentiles), 2] (the two order statistics each one
+    interpolates), "hist", "hist_lo".
+    Means, variances and covariances come from the integer sums in exact rational arithmetic and are rounded to float64 once (the variance
+    is (count Svv - Sv^2) / count^2; Svv / count - mean^2 cancels and is not used).  A percentile follows numpy's "linear" definition:
+    virtual index q / 100 (count - 1), the two order statistics read exactly from the cumulative histogram, interpolated in float64; it
+    is NaN if either order statistic lies in a clipped tail -- nothing is clamped.  Absent organs: NaN for float figures, 0 for counts,
+    -1 for boxes."""
+    M = np.asarray(moments).astype(np.int64).reshape(-1, 14)
+    E = np.asarray(extent).astype(np.int64).reshape(-1, 6)
+    n = M.shape[0]
+    sp = tuple(float(s) for s in spacing)
+    assert len(sp) == 3 and all(s > 0.0 for s in sp), "spacing: three positive values (sz, sy, sx)"
+    nan = float("nan")
+    count = M[:, 0].copy()
+    out = {"voxels": count, "volume_mm3": count.astype(np.float64) * (sp[0] * sp[1] * sp[2]), "bbox": E.copy()}
+    out["volume_ml"] = out["volume_mm3"] / 1000.0
+    ext_mm, cen, cov = np.full((n, 3), nan), np.full((n, 3), nan), np.full((n, 3, 3), nan)
+    plen, pax = np.full((n, 3), nan), np.full((n, 3, 3), nan)
+    second = {(0, 0): 4, (1, 1): 5, (2, 2): 6, (0, 1): 7, (0, 2): 8, (1, 2): 9}
+    for j in range(n):
+        c = int(count[j])
+        if c == 0:
+            continue
+        s1 = [int(M[j, 1 + a]) for a in range(3)]
+        for a in range(3):
+            ext_mm[j, a] = float(int(E[j, 2 * a + 1]) - int(E[j, 2 * a]) + 1) * sp[a]
+            cen[j, a] = s1[a] / c                                         # int / int: correctly rounded
+            for b in range(a, 3):
+                cov[j, a, b] = cov[j, b, a] = float(Fraction(c * int(M[j, second[(a, b)]]) - s1[a] * s1[b], c * c)) * sp[a] * sp[b]
+        w, v = np.linalg.eigh(cov[j])
+        order = np.argsort(-w, kind="stable")
+        plen[j] = 4.0 * np.sqrt(np.maximum(w[order], 0.0))
+        axes = v[:, order].T
+        for k in range(3):
+            if axes[k, int(np.argmax(np.abs(axes[k])))] < 0.0:
+                axes[k] = -axes[k]
+        pax[j] = axes
+    out.update(extent_mm=ext_mm, centroid_vox=cen, centroid_mm=cen * np.array(sp), covariance_mm2=cov, principal_lengths_mm=plen,
+               principal_axes=pax)
+    if faces is not None:
+        Fc = np.asarray(faces).astype(np.int64).reshape(n, 6)
+        out["surface_mm2"] = (Fc[:, 0].astype(np.float64) * (sp[1] * sp[2]) + Fc[:, 1].astype(np.float64) * (sp[0] * sp[2])
+                              + Fc[:, 2].astype(np.float64) * (sp[0] * sp[1]))
+        out["surface_mm2"][count == 0] = nan
+        out["frame_faces"] = Fc[:, 3:6].copy()
+        out["touches_frame"] = (Fc[:, 3:6] > 0).any(axis=1)
+    if vrange is None:
+        return out
+    V = np.asarray(vrange).astype(np.int64).reshape(n, 2)
+    mean, std, vmin, vmax = (np.full(n, nan) for _ in range(4))
+    for j in range(n):
+        c = int(count[j])
+        if c == 0:
+            continue
+        sv, svv = int(M[j, 10]), int(M[j, 11])
+        mean[j] = sv / c
+        std[j] = math.sqrt(float(Fraction(c * svv - sv * sv, c * c)))
+        vmin[j], vmax[j] = float(V[j, 0]), float(V[j, 1])
+    out.update(mean=mean, std=std, min=vmin, max=vmax, clipped=M[:, 12:14].copy())
+    if hist is None:
+        return out
+    Hh = np.asarray(hist).astype(np.int64).reshape(n, -1)
+    qs = [float(q) for q in percentiles]
+    assert all(0.0 <= q <= 100.0 for q in qs), "percentiles: 0 .. 100"
+    pct, bounds = np.full((n, len(qs)), nan), np.full((n, len(qs), 2), nan)
+    for j in range(n):
+        c = int(count[j])
+        if c == 0:
+            continue
+        cum = np.cumsum(Hh[j])
+        for i, q in enumerate(qs):
+            pos = (c - 1) * (q / 100.0)                                   # numpy's virtual index
+            lo = int(math.floor(pos))
+            hi = min(lo + 1, c - 1)
+            t = pos - lo
+            a, b = (_order_statistic(cum, int(M[j, 12]), int(hist_lo), k) for k in (lo, hi))
+            bounds[j, i] = (a, b)
+            pct[j, i] = a + (b - a) * t if t < 0.5 else b - (b - a) * (1.0 - t)   # numpy's linear interpolation, both of its branches
+    out.update(percentiles=pct, percentile_bounds=bounds, hist=Hh, hist_lo=int(hist_lo))
+    return out
+
+
+@torch.no_grad()
+def organ_measurements(labels: torch.Tensor, image: Optional[torch.Tensor] = None, obj_ids: Optional[Sequence[int]] = None,
+                       spacing=(1.0, 1.0, 1.0), percentiles=(5, 25, 50, 75, 95), hist_range=None, n: Optional[int] = None) -> dict:
+    """Per-organ measurements of the uint8 [T, H, W] label volume on the device and, with `image` (int16 Hounsfield units or uint8 grey, same
+    shape and device), the intensity statistics inside every organ: one `ops.label_measure` call, one device-to-host copy of its small
+    tables, then `measurements_from_tables` (keys and arithmetic: see there).  spacing = (sz, sy, sx) in millimetres.  hist_range = (lo, hi):
+    the histogram behind the percentiles has one bin per integer in [lo, hi) (at most 65536); default (-1024, 3072) for int16, (0, 256) for
+    uint8; values outside are counted in "clipped", and a percentile that falls among them is NaN.  obj_ids / n: as `clean_labels` takes
+    them."""
+    ids = _resolve_ids("organ_measurements", labels, obj_ids, n)
+    lo = bins = 0
+    if image is not None:
+        assert image.dtype in DEFAULT_HIST_RANGE, "organ_measurements: the image must be int16 or uint8"
+        lo, hi = (int(x) for x in (DEFAULT_HIST_RANGE[image.dtype] if hist_range is None else hist_range))
+        assert 1 <= hi - lo <= ops.MEASURE_MAX_BINS, f"organ_measurements: hist_range [{lo}, {hi}) must hold 1 .. {ops.MEASURE_MAX_BINS} values"
+        bins = hi - lo
+    tables = ops.label_measure(labels, ids, image, lo, bins, faces=True)
+    k = ids.numel()
+    flat = torch.cat([t.reshape(-1).to(torch.int64) for t in tables if t is not None]).cpu().numpy()      # the one device-to-host copy
+    sizes = [k * 14, k * 6, k * 2, k * 6, k * bins]
+    m, e, v, f, h = (flat[sum(sizes[:i]): sum(sizes[:i + 1])] for i in range(5))
+    if image is None:
+        return measurements_from_tables(m, e, None, f, None, 0, spacing, percentiles)
+    return measurements_from_tables(m, e, v, f, h.reshape(k, bins), lo, spacing, percentiles)
+
+
+def measurement_errors(pred_m: dict, gt_m: dict) -> dict:
+    """Two reports of `organ_measurements` / `measurements_from_tables` on the same organs -> "volume_rel_diff" = (Vp - Vg) / Vg per organ
+    (signed; NaN where the organ is absent from the ground truth) and "centroid_distance_mm" (NaN where it is absent from either): the
+    figures usually reported beside Dice, with no further device work."""
+    vp, vg = (np.asarray(m["volume_mm3"], dtype=np.float64) for m in (pred_m, gt_m))
+    assert vp.shape == vg.shape, "measurement_errors: the two reports must list the same organs"
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rel = np.where(vg > 0.0, (vp - vg) / vg, np.nan)
+    d = np.asarray(pred_m["centroid_mm"], dtype=np.float64) - np.asarray(gt_m["centroid_mm"], dtype=np.float64)
+    return {"volume_rel_diff": rel, "centroid_distance_mm": np.sqrt((d * d).sum(axis=1))}
