@@ -446,7 +446,8 @@ template <typename... A>
 static inline bool vec_ok(int n, int s, A... a) { return (vec_ok1(a, n, s) && ...); }
 
 // ---- building blocks of the label-volume and mask post-processing kernels (amg.hip, bank.hip, cc.hip, volume_labels.hip, prompts.hip,
-// components.hip, surface.hip, volume_prep.hip): one definition each ----
+// components.hip, holes.hip, surface.hip, morph.hip, clicks.hip, measure.hip, volume_prep.hip): one definition each.  What only the
+// entries that work per organ inside a bounding box share (surface.hip, holes.hip, morph.hip) is in label_boxes.h ----
 
 // integer siblings of wave_max: the result in all 64 lanes
 __device__ __forceinline__ int wave_min(int v) {
@@ -460,7 +461,7 @@ __device__ __forceinline__ int wave_max(int v) {
   return v;
 }
 
-// Lock-free union-find over int parents in global memory (cc.hip, components.hip).  A parent only ever points to a lower index, so a
+// Lock-free union-find over int parents in global memory (cc.hip, components.hip, holes.hip).  A parent only ever points to a lower index, so a
 // find follows strictly decreasing indices and ends whatever other threads do; a union lowers the larger root with atomicMin and goes
 // on from the value it found there when somebody lowered that parent first.  No thread waits for another.
 __device__ __forceinline__ int uf_find(const int* parent, int n) {

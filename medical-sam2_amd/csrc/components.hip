@@ -28,7 +28,7 @@
 // (size << 32 | 0x7fffffff - canonical index): the greatest size, ties to the smaller index -- gathered in LDS per workgroup and merged
 // with one atomic per workgroup and counter; a second pass keeps or clears every voxel and counts what is kept, a last one writes info.
 // msam2_label_overlap: (|P & G|, |P|, |G|) per slice and listed value from two label volumes, ballots and popcounts per wave.
-#include "common.h"
+#include "label_boxes.h"
 
 namespace {
 
@@ -36,15 +36,6 @@ constexpr int CMP_THREADS = 256, CMP_ITER = 4;              // a workgroup owns 
 
 // voxel of this lane in round `it`: consecutive lanes hold consecutive voxels, a wave's 64 never straddle two rounds
 __device__ __forceinline__ int64_t cmp_voxel(int it) { return ((int64_t)blockIdx.x * CMP_ITER + it) * CMP_THREADS + threadIdx.x; }
-
-// Lane of the first voxel of this lane's run among the wave's 64 voxels: a run starts where the value differs from the left neighbour's,
-// at column 0 and at lane 0 (background voxels are runs of their own).  *heads: the lanes that start a run.  All 64 lanes call it.
-__device__ __forceinline__ int cmp_run_first(int b, int col, int lane, unsigned long long* heads) {
-  const int pb = __shfl_up(b, 1);
-  const bool head = lane == 0 || b == 0 || col == 0 || b != pb;
-  *heads = __ballot(head);                                  // bit 0 is always set
-  return 63 - __clzll((long long)(*heads & (~0ull >> (63 - lane))));
-}
 
 __global__ __launch_bounds__(CMP_THREADS) void cmp_runs_kernel(const uint8_t* __restrict__ labels, int* __restrict__ parent,
                                                                int* __restrict__ size, int W, int64_t N) {
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_runs_kernel(const uint8_t* __
     const int i = live ? (int)gi : 0;
     const int b = live ? labels[i] : 0;
     unsigned long long heads;
-    const int first = cmp_run_first(b, i % W, lane, &heads);
+    const int first = label_run_first(b, i % W, lane, &heads, [&](int left) { return b != left; });
     if (live) {
       if (b != 0) parent[i] = i - lane + first;             // nothing ever reads the parent of a background voxel
       size[i] = 0;
@@ -64,13 +55,10 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_runs_kernel(const uint8_t* __
   }
 }
 
-struct CmpRows {                                            // the backward neighbour rows of a connectivity
-  int count;
-  int dd[4], dr[4], wide[4];                                // slice and row offset; wide: the overlap reaches one column further
-};
-
+// holes.hip's hol_merge_kernel is this text with the class "labels != v" in place of the label byte and a box in place of the volume,
+// kept as a text of its own so that neither listing moves: a fix to either belongs in the other too.
 __global__ __launch_bounds__(CMP_THREADS) void cmp_merge_kernel(const uint8_t* __restrict__ labels, int* __restrict__ parent, int H, int W,
-                                                                int64_t N, CmpRows rows) {
+                                                                int64_t N, LabelRows rows) {
   const int lane = threadIdx.x & 63;
   const int HW = H * W;
 #pragma unroll 1
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(CMP_THREADS) void cmp_flatten_kernel(const uint8_t*
       continue;
     }
     unsigned long long heads;
-    const int first = cmp_run_first(b, i % W, lane, &heads);
+    const int first = label_run_first(b, i % W, lane, &heads, [&](int left) { return b != left; });
     const bool walks = b != 0 && first == lane;
     const int root = walks ? uf_find(parent, i) + 1 : 0;
     const int y = __shfl(root, first);                      // a background voxel is its own run: 0
@@ -308,29 +296,13 @@ extern "C" size_t msam2_label_components_workspace_bytes(int64_t D, int64_t H, i
 extern "C" int msam2_label_components(const uint8_t* labels, int64_t D, int64_t H, int64_t W, int connectivity, int32_t* comp, int32_t* size,
                                       void* workspace, size_t workspace_bytes, void* stream) {
   MSAM2_REQUIRE(labels && comp && size && workspace, "label_components: null labels / comp / size / workspace");
-  MSAM2_REQUIRE(connectivity == 4 || connectivity == 8 || connectivity == 6 || connectivity == 18 || connectivity == 26,
-                "label_components: connectivity %d (6, 18 or 26 in 3-D; 4 or 8 slice by slice)", connectivity);
+  MSAM2_REQUIRE(label_connectivity_ok(connectivity), "label_components: connectivity %d (6, 18 or 26 in 3-D; 4 or 8 slice by slice)", connectivity);
   LABEL_REQUIRE_SIZES("label_components", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(workspace_bytes >= msam2_label_components_workspace_bytes(D, H, W), "label_components: workspace too small (%zu of %zu bytes)",
                 workspace_bytes, msam2_label_components_workspace_bytes(D, H, W));
   MSAM2_REQUIRE(((uintptr_t)workspace & 3) == 0 && ((uintptr_t)comp & 3) == 0 && ((uintptr_t)size & 3) == 0,
                 "label_components: comp / size / workspace must be 4-byte aligned");
-  // backward neighbour rows (slice offset, row offset, widened by a column): in plane first
-  CmpRows rows = {};
-  const bool diag2 = connectivity == 8 || connectivity == 18 || connectivity == 26;     // offsets that differ in two coordinates
-  const bool three_d = connectivity == 6 || connectivity == 18 || connectivity == 26;
-  auto add = [&](int dd, int dr, bool wide) {
-    rows.dd[rows.count] = dd, rows.dr[rows.count] = dr, rows.wide[rows.count] = wide ? 1 : 0;
-    ++rows.count;
-  };
-  add(0, -1, diag2);
-  if (three_d) {
-    add(-1, 0, diag2);
-    if (diag2) {
-      add(-1, -1, connectivity == 26);
-      add(-1, 1, connectivity == 26);
-    }
-  }
+  const LabelRows rows = label_rows(connectivity);
   hipStream_t s = (hipStream_t)stream;
   const int64_t N = D * H * W;
   int* parent = (int*)workspace;

@@ -36,15 +36,14 @@
 // every launch reads the input from there: in place gives the bytes of the out-of-place call.
 // Every loop of every thread ends whatever other threads do: a find follows strictly decreasing indices, a union retries only after
 // another thread lowered the parent it wanted to lower; no thread waits for another, no grid barrier, no cooperative launch.
-#include "common.h"
+#define LABEL_BOXES_OUT
+#include "label_boxes.h"
 
 namespace {
 
 constexpr int HOL_THREADS = 256, HOL_ITER = 4;              // a workgroup owns HOL_ITER x 256 consecutive box voxels, a wave 64 at a time
-constexpr int HOL_FIXED_BYTES = 16;                         // the workspace is never empty
 
-struct HoleOrgan {
-  int z0, y0, x0, bd, bh, bw;                               // the box: first voxel and extent
+struct HoleOrgan : LabelBox {                               // the box
   int value, j;                                             // label value and index in ids / max_voxels / info
   long long ws;                                             // byte offset of the organ's tables in the workspace
 };
@@ -53,27 +52,15 @@ struct HoleJobs {
   HoleOrgan o[LABEL_MAX_OBJ];
 };
 
-static inline int64_t hol_vox(const int32_t* b) { return (int64_t)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) * (b[5] - b[4] + 1); }
-static inline bool hol_box_ok(const int32_t* b, int64_t D, int64_t H, int64_t W) {
-  return b[0] >= 0 && b[0] <= b[1] && b[1] < D && b[2] >= 0 && b[2] <= b[3] && b[3] < H && b[4] >= 0 && b[4] <= b[5] && b[5] < W;
-}
 // a box that can hold a hole: the hole and the organ around it need 3 voxels along every axis the flood moves along
-static inline bool hol_box_live(const int32_t* b, bool plane) {
-  return b[3] - b[2] >= 2 && b[5] - b[4] >= 2 && (plane || b[1] - b[0] >= 2);
+static inline bool hol_box_live(const LabelBox& b, bool plane) { return b.bh >= 3 && b.bw >= 3 && (plane || b.bd >= 3); }
+// the tables of a box: 9 bytes per voxel; none for a box that holds no hole
+static inline size_t hol_box_bytes(const int32_t* bx, bool plane) {
+  const LabelBox b = label_box(bx);
+  return hol_box_live(b, plane) ? label_round16((size_t)label_box_voxels(b) * 9) : 0;
 }
-static inline size_t hol_box_bytes(int64_t vox) { return ((size_t)vox * 9 + 15) & ~(size_t)15; }
-static inline size_t hol_snapshot_bytes(int64_t N) { return ((size_t)N + 15) & ~(size_t)15; }
 
-struct HoleVoxel {                                          // box voxel `li` of an organ: position in the box, index in the volume
-  int dz, dr, dc, g;
-  __device__ __forceinline__ HoleVoxel(const HoleOrgan& o, int li, int H, int W) {
-    const int row = li / o.bw;
-    dc = li - row * o.bw;
-    dz = row / o.bh;
-    dr = row - dz * o.bh;
-    g = ((o.z0 + dz) * H + o.y0 + dr) * W + o.x0 + dc;      // a voxel of the volume: below 2^31 - 2
-  }
-};
+typedef LabelBoxVoxel<int> HoleVoxel;                       // in int: a voxel of the volume is below 2^31 - 2
 __device__ __forceinline__ int hol_voxels(const HoleOrgan& o) { return o.bd * o.bh * o.bw; }
 __device__ __forceinline__ int* hol_parent(char* ws, const HoleOrgan& o) { return (int*)(ws + o.ws); }
 __device__ __forceinline__ int* hol_size(char* ws, const HoleOrgan& o) { return (int*)(ws + o.ws) + hol_voxels(o); }
@@ -81,30 +68,6 @@ __device__ __forceinline__ uint8_t* hol_ext(char* ws, const HoleOrgan& o) { retu
 
 // box voxel of this lane in round `it`: consecutive lanes hold consecutive box voxels, a wave's 64 never straddle two rounds
 __device__ __forceinline__ int64_t hol_voxel(int it) { return ((int64_t)blockIdx.x * HOL_ITER + it) * HOL_THREADS + threadIdx.x; }
-
-// Lane of the first voxel of this lane's run among the wave's 64 box voxels: a run of complement voxels starts where the left lane is
-// of the organ, at column 0 of the box and at lane 0 (organ voxels are runs of their own).  All 64 lanes call it.
-__device__ __forceinline__ int hol_run_first(int cls, int col, int lane, unsigned long long* heads) {
-  const int pc = __shfl_up(cls, 1);
-  const bool head = lane == 0 || cls == 0 || col == 0 || pc == 0;
-  *heads = __ballot(head);                                  // bit 0 is always set
-  return 63 - __clzll((long long)(*heads & (~0ull >> (63 - lane))));
-}
-
-// (kernels, not hipMemcpyAsync / hipMemsetAsync: cc.hip found memset nodes of a captured graph unreliable against neighbouring kernel nodes)
-__global__ void hol_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int vec) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x, t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vec) {                                                // both 16-byte aligned: the tail by bytes
-    const int64_t n16 = n / 16;
-    for (int64_t i = t; i < n16; i += step) ((int4*)dst)[i] = ((const int4*)src)[i];
-    for (int64_t i = n16 * 16 + t; i < n; i += step) dst[i] = src[i];
-  } else {
-    for (int64_t i = t; i < n; i += step) dst[i] = src[i];
-  }
-}
-__global__ void hol_zero_kernel(int* __restrict__ x, int n) {
-  if ((int)threadIdx.x < n) x[threadIdx.x] = 0;
-}
 
 __global__ __launch_bounds__(HOL_THREADS) void hol_runs_kernel(const uint8_t* __restrict__ src, HoleJobs jobs, char* __restrict__ ws) {
   const HoleOrgan& o = jobs.o[blockIdx.y];
@@ -119,10 +82,10 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_runs_kernel(const uint8_t* __
     const int64_t gi = hol_voxel(it);
     const bool live = gi < V;
     const int li = live ? (int)gi : 0;
-    const HoleVoxel x(o, li, jobs.H, jobs.W);
+    const HoleVoxel x(li, o, jobs.H, jobs.W);
     const int cls = live && src[x.g] != o.value;
     unsigned long long heads;
-    const int first = hol_run_first(cls, x.dc, lane, &heads);
+    const int first = label_run_first(cls, x.xb, lane, &heads, [](int left) { return left == 0; });
     if (live) {
       if (cls) parent[li] = li - lane + first;              // nothing ever reads the parent of an organ voxel
       size[li] = 0;
@@ -131,13 +94,10 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_runs_kernel(const uint8_t* __
   }
 }
 
-struct HoleRows {                                           // the backward neighbour rows of a connectivity
-  int count;
-  int dd[4], dr[4], wide[4];                                // slice and row offset; wide: the overlap reaches one column further
-};
-
+// The text of components.hip's cmp_merge_kernel with the class "labels != v" in place of the label byte and the box in place of the
+// volume, kept as a text of its own so that neither listing moves: a fix to either belongs in the other too.
 __global__ __launch_bounds__(HOL_THREADS) void hol_merge_kernel(const uint8_t* __restrict__ src, HoleJobs jobs, char* __restrict__ ws,
-                                                                HoleRows rows) {
+                                                                LabelRows rows) {
   const HoleOrgan& o = jobs.o[blockIdx.y];
   const int V = hol_voxels(o);
   if ((int64_t)blockIdx.x * HOL_ITER * HOL_THREADS >= V) return;
@@ -149,10 +109,10 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_merge_kernel(const uint8_t* _
     const int64_t gi = hol_voxel(it);
     const bool live = gi < V;
     const int li = live ? (int)gi : 0;
-    const HoleVoxel x(o, li, jobs.H, W);
+    const HoleVoxel x(li, o, jobs.H, W);
     const int b = live && src[x.g] != v;
     if (__ballot(b != 0) == 0ull) continue;                 // wave-uniform: the shuffles below see whole waves
-    const int col = x.dc;
+    const int col = x.xb;
     int pb = __shfl_up(b, 1);
     if (lane == 0) pb = (live && col > 0) ? src[x.g - 1] != v : 0;
     const bool left_same = col > 0 && b != 0 && pb != 0;    // the voxel to the left belongs to the same run
@@ -161,7 +121,7 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_merge_kernel(const uint8_t* _
     int ni[4], M[4], L[4], R[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const bool valid = live && k < rows.count && x.dz + rows.dd[k] >= 0 && x.dr + rows.dr[k] >= 0 && x.dr + rows.dr[k] < bh;
+      const bool valid = live && k < rows.count && x.zb + rows.dd[k] >= 0 && x.yb + rows.dr[k] >= 0 && x.yb + rows.dr[k] < bh;
       ni[k] = valid ? li + rows.dd[k] * bh * bw + rows.dr[k] * bw : -1;   // same column of the neighbour row, in the box
       const int ng = x.g + rows.dd[k] * HW + rows.dr[k] * W;              // and in the volume
       M[k] = valid ? src[ng] != v : 0;
@@ -203,12 +163,12 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_mark_kernel(const uint8_t* __
     const int64_t gi = hol_voxel(it);
     const bool live = gi < V;
     const int li = live ? (int)gi : 0;
-    const HoleVoxel x(o, li, jobs.H, jobs.W);
-    const bool edge = x.dr == 0 || x.dr == o.bh - 1 || x.dc == 0 || x.dc == o.bw - 1 || (!jobs.plane && (x.dz == 0 || x.dz == o.bd - 1));
+    const HoleVoxel x(li, o, jobs.H, jobs.W);
+    const bool edge = x.yb == 0 || x.yb == o.bh - 1 || x.xb == 0 || x.xb == o.bw - 1 || (!jobs.plane && (x.zb == 0 || x.zb == o.bd - 1));
     const int cls = live && src[x.g] != o.value;
     const int pc = __shfl_up(cls, 1);
-    const bool head = lane == 0 || x.dc == 0 || pc == 0;    // a row of the boundary marks once per run, not once per voxel
-    if (cls && edge && (head || x.dc == o.bw - 1)) ext[uf_find(parent, li)] = 1;
+    const bool head = lane == 0 || x.xb == 0 || pc == 0;    // a row of the boundary marks once per run, not once per voxel
+    if (cls && edge && (head || x.xb == o.bw - 1)) ext[uf_find(parent, li)] = 1;
   }
 }
 
@@ -226,11 +186,11 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_size_kernel(const uint8_t* __
     const int64_t gi = hol_voxel(it);
     const bool live = gi < V;
     const int li = live ? (int)gi : 0;
-    const HoleVoxel x(o, li, jobs.H, jobs.W);
+    const HoleVoxel x(li, o, jobs.H, jobs.W);
     const int cls = live && src[x.g] != o.value;
     if (__ballot(cls != 0) == 0ull) continue;               // wave-uniform
     unsigned long long heads;
-    const int first = hol_run_first(cls, x.dc, lane, &heads);
+    const int first = label_run_first(cls, x.xb, lane, &heads, [](int left) { return left == 0; });
     const bool walks = cls && first == lane;
     const int root = walks ? uf_find(parent, li) : -1;
     const bool hole = walks && ext[root] == 0;
@@ -265,12 +225,12 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_apply_kernel(const uint8_t* _
     const int64_t gi = hol_voxel(it);
     const bool live = gi < V;
     const int li = live ? (int)gi : 0;
-    const HoleVoxel x(o, li, H, W);
+    const HoleVoxel x(li, o, H, W);
     const int in = live ? src[x.g] : o.value;
     const int cls = in != o.value;
     if (__ballot(cls != 0) == 0ull) continue;               // wave-uniform
     unsigned long long heads;
-    const int first = hol_run_first(cls, x.dc, lane, &heads);
+    const int first = label_run_first(cls, x.xb, lane, &heads, [](int left) { return left == 0; });
     const bool walks = cls && first == lane;
     const int root = walks ? uf_find(parent, li) : -1;
     const bool hole = walks && ext[root] == 0;
@@ -297,19 +257,13 @@ __global__ __launch_bounds__(HOL_THREADS) void hol_apply_kernel(const uint8_t* _
 // the entry takes (its largest box alone); 1: what lets every organ go through one group.
 extern "C" size_t msam2_label_fill_holes_workspace_bytes(int64_t D, int64_t H, int64_t W, const int32_t* boxes, int64_t n, int connectivity,
                                                          int in_place, int all_at_once) {
-  if (!boxes || n < 1 || n > LABEL_MAX_OBJ || !label_sizes_ok(D, H, W, 1, LABEL_MAX_VOXELS)) return 0;
-  if (connectivity != 4 && connectivity != 8 && connectivity != 6 && connectivity != 18 && connectivity != 26) return 0;
-  const bool plane = connectivity == 4 || connectivity == 8;
-  size_t sum = 0, largest = 0;
+  if (!boxes || n < 1 || n > LABEL_MAX_OBJ || !label_sizes_ok(D, H, W, 1, LABEL_MAX_VOXELS) || !label_connectivity_ok(connectivity)) return 0;
+  size_t bytes[LABEL_MAX_OBJ];
   for (int64_t j = 0; j < n; ++j) {
-    const int32_t* bx = boxes + 6 * j;
-    if (!hol_box_ok(bx, D, H, W)) return 0;
-    if (!hol_box_live(bx, plane)) continue;
-    const size_t one = hol_box_bytes(hol_vox(bx));
-    sum += one;
-    if (one > largest) largest = one;
+    if (!label_box_ok(boxes + 6 * j, D, H, W)) return 0;
+    bytes[j] = hol_box_bytes(boxes + 6 * j, label_connectivity_in_plane(connectivity));
   }
-  return HOL_FIXED_BYTES + (in_place ? hol_snapshot_bytes(D * H * W) : 0) + (all_at_once ? sum : largest);
+  return label_input_bytes(D * H * W, in_place != 0) + label_tables_bytes(bytes, n, all_at_once != 0);
 }
 
 extern "C" int msam2_label_fill_holes(const uint8_t* labels, int64_t D, int64_t H, int64_t W, const uint8_t* ids, const int32_t* boxes, int64_t n,
@@ -318,75 +272,39 @@ extern "C" int msam2_label_fill_holes(const uint8_t* labels, int64_t D, int64_t 
   MSAM2_REQUIRE(labels && ids && boxes && out && info && workspace, "label_fill_holes: null labels / ids / boxes / out / info / workspace");
   LABEL_REQUIRE_OBJECTS("label_fill_holes", n);
   LABEL_REQUIRE_SIZES("label_fill_holes", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
-  MSAM2_REQUIRE(connectivity == 4 || connectivity == 8 || connectivity == 6 || connectivity == 18 || connectivity == 26,
+  MSAM2_REQUIRE(label_connectivity_ok(connectivity),
                 "label_fill_holes: connectivity %d of the background flood (6, 18 or 26 in 3-D; 4 or 8 slice by slice)", connectivity);
   MSAM2_REQUIRE(claim == 0 || claim == 1, "label_fill_holes: claim %d (0: background voxels only, 1: any voxel of a hole)", claim);
+  const bool plane = label_connectivity_in_plane(connectivity);
+  size_t bytes[LABEL_MAX_OBJ];                              // 0: a box that holds no hole
   for (int j = 0; j < (int)n; ++j) {                        // ids: HOST bytes, like the boxes
-    MSAM2_REQUIRE(ids[j] != 0, "label_fill_holes: ids[%d] is 0, the background", j);
-    for (int k = 0; k < j; ++k) MSAM2_REQUIRE(ids[k] != ids[j], "label_fill_holes: ids[%d] and ids[%d] are both %d", k, j, (int)ids[j]);
-    const int32_t* bx = boxes + 6 * j;
-    MSAM2_REQUIRE(hol_box_ok(bx, D, H, W), "label_fill_holes: box %d (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", j,
-                  bx[0], bx[1], bx[2], bx[3], bx[4], bx[5], (long long)D, (long long)H, (long long)W);
+    LABEL_REQUIRE_DISTINCT_ID("label_fill_holes", "ids", ids, j);
+    LABEL_REQUIRE_BOX("label_fill_holes", j, boxes + 6 * j, D, H, W);
+    bytes[j] = hol_box_bytes(boxes + 6 * j, plane);
   }
   const int64_t N = D * H * W;
-  const bool in_place = out == labels;
-  MSAM2_REQUIRE(in_place || out + N <= labels || labels + N <= out, "label_fill_holes: out overlaps labels without being labels");
-  const size_t need = msam2_label_fill_holes_workspace_bytes(D, H, W, boxes, n, connectivity, in_place, 0);
+  LABEL_REQUIRE_OUT("label_fill_holes", labels, out, N);
+  const size_t fixed = label_input_bytes(N, out == labels), need = fixed + label_tables_bytes(bytes, n, false);
   MSAM2_REQUIRE(workspace_bytes >= need, "label_fill_holes: workspace too small (%zu of %zu bytes)", workspace_bytes, need);
   MSAM2_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)info & 3) == 0 && ((uintptr_t)max_voxels & 3) == 0,
                 "label_fill_holes: the workspace must be 16-byte aligned, info and max_voxels 4-byte");
-  // backward neighbour rows (slice offset, row offset, widened by a column): in plane first
-  HoleRows rows = {};
-  const bool diag2 = connectivity == 8 || connectivity == 18 || connectivity == 26;     // offsets that differ in two coordinates
-  const bool plane = connectivity == 4 || connectivity == 8;
-  auto add = [&](int dd, int dr, bool wide) {
-    rows.dd[rows.count] = dd, rows.dr[rows.count] = dr, rows.wide[rows.count] = wide ? 1 : 0;
-    ++rows.count;
-  };
-  add(0, -1, diag2);
-  if (!plane) {
-    add(-1, 0, diag2);
-    if (diag2) {
-      add(-1, -1, connectivity == 26);
-      add(-1, 1, connectivity == 26);
-    }
-  }
+  const LabelRows rows = label_rows(connectivity);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const dim3 blk(HOL_THREADS);
-  // the input every launch reads: labels, or its snapshot when the call is in place
-  const uint8_t* src = labels;
-  size_t fixed = HOL_FIXED_BYTES;
-  uint8_t* copy_to = out;
-  if (in_place) {
-    copy_to = (uint8_t*)(ws + fixed);
-    src = copy_to;
-    fixed += hol_snapshot_bytes(N);
-  }
-  hipLaunchKernelGGL(hol_copy_kernel, dim3(grid1d(N, 4096, HOL_THREADS * 16)), blk, 0, s, labels, copy_to, N,
-                     (int)((((uintptr_t)labels | (uintptr_t)copy_to) & 15) == 0));
-  hipLaunchKernelGGL(hol_zero_kernel, dim3(1), dim3(LABEL_MAX_OBJ * 4), 0, s, info, (int)n * 4);
-  const size_t room = workspace_bytes - fixed;
-  int j = 0;
-  while (j < (int)n) {
+  const uint8_t* src = label_begin_out(labels, out, N, ws, info, n, s);
+  for (int j = 0; j < (int)n;) {
     HoleJobs jobs = {};
     jobs.H = (int)H, jobs.W = (int)W, jobs.plane = plane ? 1 : 0;
-    size_t used = 0;
     int64_t vox = 0;
-    for (; j < (int)n; ++j) {                               // the organs that follow, as long as their boxes fit
-      const int32_t* bx = boxes + 6 * j;
-      if (!hol_box_live(bx, plane)) continue;
-      const size_t one = hol_box_bytes(hol_vox(bx));
-      if (jobs.n > 0 && used + one > room) break;           // (one alone fits: `need` covers the largest box)
+    j = label_next_group(bytes, (int)n, j, workspace_bytes - fixed, [&](int m, size_t at) {
       HoleOrgan& o = jobs.o[jobs.n++];
-      o.z0 = bx[0], o.y0 = bx[2], o.x0 = bx[4];
-      o.bd = bx[1] - bx[0] + 1, o.bh = bx[3] - bx[2] + 1, o.bw = bx[5] - bx[4] + 1;
-      o.value = ids[j], o.j = j;
-      o.ws = (long long)(fixed + used);
-      used += one;
-      if (hol_vox(bx) > vox) vox = hol_vox(bx);
-    }
-    if (jobs.n == 0) break;
+      static_cast<LabelBox&>(o) = label_box(boxes + 6 * m);
+      o.value = ids[m], o.j = m;
+      o.ws = (long long)(fixed + at);
+      vox = std::max(vox, label_box_voxels(o));
+    });
+    if (jobs.n == 0) break;                                 // no box is left that can hold a hole
     const dim3 grid(cdiv(vox, HOL_THREADS * HOL_ITER), jobs.n);
     hipLaunchKernelGGL(hol_runs_kernel, grid, blk, 0, s, src, jobs, ws);
     hipLaunchKernelGGL(hol_merge_kernel, grid, blk, 0, s, src, jobs, ws, rows);
@@ -394,7 +312,7 @@ extern "C" int msam2_label_fill_holes(const uint8_t* labels, int64_t D, int64_t 
     hipLaunchKernelGGL(hol_size_kernel, grid, blk, 0, s, src, jobs, ws);
     for (int k = 0; k < jobs.n; ++k) {
       const HoleOrgan& o = jobs.o[k];
-      hipLaunchKernelGGL(hol_apply_kernel, dim3(cdiv((int64_t)o.bd * o.bh * o.bw, HOL_THREADS * HOL_ITER)), blk, 0, s, src, o, (int)H, (int)W,
+      hipLaunchKernelGGL(hol_apply_kernel, dim3(cdiv(label_box_voxels(o), HOL_THREADS * HOL_ITER)), blk, 0, s, src, o, (int)H, (int)W,
                          (const char*)ws, max_voxels, claim, out, info);
     }
   }

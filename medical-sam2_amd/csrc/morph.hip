@@ -34,23 +34,20 @@
 // from there.  No thread waits for another: no spin, no grid barrier, no cooperative launch.
 #include <cmath>
 
-#include "common.h"
 #include "edt_passes.h"
+#define LABEL_BOXES_OUT
+#include "label_boxes.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int MOR_THREADS = 256;
-constexpr int MOR_FIXED_BYTES = 16;                         // the workspace is never empty
 enum { MOR_ERODE = 0, MOR_DILATE = 1, MOR_OPEN = 2, MOR_CLOSE = 3 };
 // a stage: what it does, and whether its input set is the organ in the label bytes or the mask of the stage before
 enum { MOR_STAGE_ERODE = 1, MOR_STAGE_FROM_MASK = 2, MOR_STAGE_KEEP_D = 4, MOR_STAGE_LAST = 8, MOR_STAGE_CLEAR = 16 };
-// The row pass runs one wave per row of the box in one launch: 64 threads per row must stay below 2^32 in all (surface.hip's limit).
-constexpr int64_t MOR_MAX_ROWS = 1ll << 25;
 
-struct MorOrgan {
-  int z0, y0, x0, bd, bh, bw;                               // the grown box: first voxel and extent
+struct MorOrgan : LabelBox {                                // the grown box
   int value, j;                                             // label value and index in ids / r2 / info
   double r2, cap;                                           // the ball, and the scans' bound: the float64 after r2
   long long ws;                                             // byte offset of the organ's tables in the workspace
@@ -63,11 +60,9 @@ struct MorListed {                                          // bit v: v is one o
   uint32_t w[8];
 };
 
-static inline size_t mor_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ __forceinline__ long long mor_round8(long long b) { return (b + 7) & ~7ll; }
 // per box voxel: t float64, the first-stage distance float64 (keep), g uint16, the mask byte
 static inline size_t mor_box_bytes(int64_t vox, bool keep) {
-  return mor_round16((size_t)vox * (keep ? 16 : 8) + (size_t)mor_round8(vox * 2) + (size_t)mor_round8(vox));
+  return label_round16((size_t)vox * (keep ? 16 : 8) + (size_t)label_round8(vox * 2) + (size_t)label_round8(vox));
 }
 
 struct MorBufs {
@@ -76,40 +71,14 @@ struct MorBufs {
   uint16_t* g;
   uint8_t* mask;
 };
-__device__ __forceinline__ int64_t mor_vox(const MorOrgan& o) { return (int64_t)o.bd * o.bh * o.bw; }
 __device__ __forceinline__ MorBufs mor_bufs(char* ws, const MorOrgan& o, int keep) {
-  const int64_t vox = mor_vox(o);
+  const int64_t vox = label_box_voxels(o);
   char* base = ws + o.ws;
   char* g = base + vox * (keep ? 16 : 8);
-  return {(double*)base, (double*)(base + vox * 8), (uint16_t*)g, (uint8_t*)(g + mor_round8(vox * 2))};
+  return {(double*)base, (double*)(base + vox * 8), (uint16_t*)g, (uint8_t*)(g + label_round8(vox * 2))};
 }
 
-struct MorVoxel {                                           // box voxel i: position in the box, index in the volume
-  int zb, yb, xb;
-  int64_t g;
-  __device__ __forceinline__ MorVoxel(int64_t i, const MorOrgan& o, int H, int W) {
-    const int64_t r = i / o.bw;
-    xb = (int)(i - r * o.bw);
-    zb = (int)(r / o.bh);
-    yb = (int)(r - (int64_t)zb * o.bh);
-    g = ((int64_t)(o.z0 + zb) * H + o.y0 + yb) * W + o.x0 + xb;
-  }
-};
-
-// (kernels, not hipMemcpyAsync / hipMemsetAsync: cc.hip found memset nodes of a captured graph unreliable against neighbouring kernel nodes)
-__global__ void mor_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int vec) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x, t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (vec) {                                                // both 16-byte aligned: the tail by bytes
-    const int64_t n16 = n / 16;
-    for (int64_t i = t; i < n16; i += step) ((int4*)dst)[i] = ((const int4*)src)[i];
-    for (int64_t i = n16 * 16 + t; i < n; i += step) dst[i] = src[i];
-  } else {
-    for (int64_t i = t; i < n; i += step) dst[i] = src[i];
-  }
-}
-__global__ void mor_zero_kernel(int* __restrict__ x, int n) {
-  if ((int)threadIdx.x < n) x[threadIdx.x] = 0;
-}
+typedef LabelBoxVoxel<int64_t> MorVoxel;
 
 // the features of a stage: erosion looks for the voxels outside its input set, dilation for the set itself
 __global__ __launch_bounds__(MOR_THREADS) void mor_row_kernel(const uint8_t* __restrict__ src, MorJobs jobs, char* __restrict__ ws, int stage) {
@@ -129,9 +98,9 @@ __global__ __launch_bounds__(MOR_THREADS) void mor_row_kernel(const uint8_t* __r
 __global__ __launch_bounds__(MOR_THREADS) void mor_col_kernel(MorJobs jobs, char* __restrict__ ws, double sx2, double sy2) {
   const MorOrgan& o = jobs.o[blockIdx.y];
   const int64_t i = (int64_t)blockIdx.x * MOR_THREADS + threadIdx.x;
-  if (i >= mor_vox(o)) return;
+  if (i >= label_box_voxels(o)) return;
   const MorBufs bufs = mor_bufs(ws, o, jobs.keep);
-  const int64_t r = i / o.bw;
+  const int64_t r = i / o.bw;                               // (LabelBoxVoxel's position, spelled out: with it the listing changes)
   const int xb = (int)(i - r * o.bw);
   const int zb = (int)(r / o.bh), yb = (int)(r - (int64_t)zb * o.bh);
   bufs.t[i] = edt_scan_y(bufs.g + (int64_t)zb * o.bh * o.bw + xb, o.bw, yb, o.bh, sx2, sy2, o.cap);
@@ -144,7 +113,7 @@ __global__ __launch_bounds__(MOR_THREADS) void mor_z_kernel(const uint8_t* __res
                                                             int stage, uint8_t* __restrict__ out, int* __restrict__ info) {
   __shared__ int cnt[2];
   const MorOrgan& o = jobs.o[blockIdx.y];
-  const int64_t vox = mor_vox(o);
+  const int64_t vox = label_box_voxels(o);
   if ((int64_t)blockIdx.x * MOR_THREADS >= vox) return;     // the whole workgroup: the grid is sized for the largest box
   const bool last = stage & MOR_STAGE_LAST;
   if (last) {
@@ -186,7 +155,7 @@ __global__ __launch_bounds__(MOR_THREADS) void mor_claim_kernel(const uint8_t* _
                                                                 MorListed listed, int claim_any, uint8_t* __restrict__ out,
                                                                 double* __restrict__ best) {
   const int64_t i = (int64_t)blockIdx.x * MOR_THREADS + threadIdx.x;
-  if (i >= mor_vox(o)) return;
+  if (i >= label_box_voxels(o)) return;
   const MorBufs bufs = mor_bufs(ws, o, 1);
   if (!bufs.mask[i]) return;
   const MorVoxel x(i, o, H, W);
@@ -206,7 +175,7 @@ __global__ __launch_bounds__(MOR_THREADS) void mor_count_kernel(const uint8_t* _
                                                                 int* __restrict__ info) {
   __shared__ int cnt[2];
   const MorOrgan& o = jobs.o[blockIdx.y];
-  const int64_t vox = mor_vox(o);
+  const int64_t vox = label_box_voxels(o);
   if ((int64_t)blockIdx.x * MOR_THREADS >= vox) return;
   if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -230,11 +199,6 @@ __global__ __launch_bounds__(MOR_THREADS) void mor_count_kernel(const uint8_t* _
   }
 }
 
-bool mor_box_ok(const int32_t* b, int64_t D, int64_t H, int64_t W) {
-  return b[0] >= 0 && b[0] <= b[1] && b[1] < D && b[2] >= 0 && b[2] <= b[3] && b[3] < H && b[4] >= 0 && b[4] <= b[5] && b[5] < W;
-}
-// as surface.hip's srf_spacing_ok: the square a normal float64, 2^36 times it finite
-bool mor_spacing_ok(double s) { return s > 0.0 && s * s >= 2.2250738585072014e-308 && s * s <= 1.7976931348623157e308 / 68719476736.0; }
 bool mor_r2_ok(double r2) { return r2 >= 0.0 && r2 < (double)INFINITY; }   // false for NaN; finite: the +inf of "no feature" is never inside
 
 // the ball's extent along an axis of spacing s: the largest k in 0 .. lim with s^2 k^2 <= r2, in the arithmetic of the scans
@@ -257,14 +221,10 @@ void mor_grow(const int32_t* b, int op, double r2, double sz, double sy, double 
     g[2 * a + 1] = (int32_t)std::min<int64_t>(dim[a] - 1, b[2 * a + 1] + by);
   }
 }
-int64_t mor_box_vox(const int32_t* g) { return (int64_t)(g[1] - g[0] + 1) * (g[3] - g[2] + 1) * (g[5] - g[4] + 1); }
-int64_t mor_box_rows(const int32_t* g) { return (int64_t)(g[1] - g[0] + 1) * (g[3] - g[2] + 1); }
 bool mor_op_ok(int op) { return op >= MOR_ERODE && op <= MOR_CLOSE; }
 bool mor_keeps(int op) { return op == MOR_DILATE || op == MOR_CLOSE; }
-// what every call holds beside the organs' tables: the snapshot of the input (in place), the best distance per voxel (dilate / close)
-size_t mor_fixed_bytes(int64_t N, int op, bool in_place) {
-  return MOR_FIXED_BYTES + (in_place ? mor_round16((size_t)N) : 0) + (mor_keeps(op) ? mor_round16((size_t)N * 8) : 0);
-}
+// the best distance per voxel of the volume (dilate / close), behind the snapshot
+size_t mor_best_bytes(int64_t N, int op) { return mor_keeps(op) ? label_round16((size_t)N * 8) : 0; }
 
 }  // namespace
 
@@ -273,18 +233,16 @@ size_t mor_fixed_bytes(int64_t N, int op, bool in_place) {
 extern "C" size_t msam2_label_morph_workspace_bytes(int64_t D, int64_t H, int64_t W, const int32_t* boxes, int64_t n, int op, const double* r2,
                                                     double sz, double sy, double sx, int in_place, int all_at_once) {
   if (!boxes || !r2 || n < 1 || n > LABEL_MAX_OBJ || !label_sizes_ok(D, H, W, 2, LABEL_MAX_VOXELS) || !mor_op_ok(op)) return 0;
-  if (!mor_spacing_ok(sz) || !mor_spacing_ok(sy) || !mor_spacing_ok(sx)) return 0;
-  size_t sum = 0, largest = 0;
+  if (!label_spacing_ok(sz) || !label_spacing_ok(sy) || !label_spacing_ok(sx)) return 0;
+  size_t bytes[LABEL_MAX_OBJ];
   for (int64_t j = 0; j < n; ++j) {
-    if (!mor_box_ok(boxes + 6 * j, D, H, W) || !mor_r2_ok(r2[j])) return 0;
+    if (!label_box_ok(boxes + 6 * j, D, H, W) || !mor_r2_ok(r2[j])) return 0;
     int32_t g[6];
     mor_grow(boxes + 6 * j, op, r2[j], sz, sy, sx, D, H, W, g);
-    if (mor_box_rows(g) > MOR_MAX_ROWS) return 0;
-    const size_t one = mor_box_bytes(mor_box_vox(g), mor_keeps(op));
-    sum += one;
-    if (one > largest) largest = one;
+    if (label_box_rows(label_box(g)) > LABEL_MAX_BOX_ROWS) return 0;
+    bytes[j] = mor_box_bytes(label_box_voxels(label_box(g)), mor_keeps(op));
   }
-  return mor_fixed_bytes(D * H * W, op, in_place != 0) + (all_at_once ? sum : largest);
+  return label_input_bytes(D * H * W, in_place != 0) + mor_best_bytes(D * H * W, op) + label_tables_bytes(bytes, n, all_at_once != 0);
 }
 
 extern "C" int msam2_label_morph(const uint8_t* labels, int64_t D, int64_t H, int64_t W, const uint8_t* values, const int32_t* boxes, int64_t n, int op,
@@ -295,55 +253,37 @@ extern "C" int msam2_label_morph(const uint8_t* labels, int64_t D, int64_t H, in
   LABEL_REQUIRE_SIZES("label_morph", D, H, W, 2, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   MSAM2_REQUIRE(mor_op_ok(op), "label_morph: op %d (0: erode, 1: dilate, 2: open, 3: close)", op);
   MSAM2_REQUIRE(claim == 0 || claim == 1, "label_morph: claim %d (0: background voxels only, 1: any voxel whose value is not in values)", claim);
-  MSAM2_REQUIRE(mor_spacing_ok(sz) && mor_spacing_ok(sy) && mor_spacing_ok(sx),
-                "label_morph: spacing (%g, %g, %g): every value must be positive with a square in 2.3e-308 .. 2.6e297", sz, sy, sx);
+  LABEL_REQUIRE_SPACING("label_morph", sz, sy, sx);
   MorJobs all = {};                                         // every organ with its grown box, in the order of values
   all.n = (int)n, all.H = (int)H, all.W = (int)W, all.keep = mor_keeps(op) ? 1 : 0;
   MorListed listed = {};
-  size_t largest = 0;
+  size_t bytes[LABEL_MAX_OBJ];
   for (int j = 0; j < (int)n; ++j) {                        // values, boxes, r2: HOST arrays
-    MSAM2_REQUIRE(values[j] != 0, "label_morph: values[%d] is 0, the background", j);
-    for (int k = 0; k < j; ++k) MSAM2_REQUIRE(values[k] != values[j], "label_morph: values[%d] and values[%d] are both %d", k, j, (int)values[j]);
+    LABEL_REQUIRE_DISTINCT_ID("label_morph", "values", values, j);
     MSAM2_REQUIRE(mor_r2_ok(r2[j]), "label_morph: r2[%d] = %g (a squared radius: >= 0 and finite)", j, r2[j]);
-    const int32_t* bx = boxes + 6 * j;
-    MSAM2_REQUIRE(mor_box_ok(bx, D, H, W), "label_morph: box %d (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", j, bx[0],
-                  bx[1], bx[2], bx[3], bx[4], bx[5], (long long)D, (long long)H, (long long)W);
+    LABEL_REQUIRE_BOX("label_morph", j, boxes + 6 * j, D, H, W);
     int32_t g[6];
-    mor_grow(bx, op, r2[j], sz, sy, sx, D, H, W, g);
-    MSAM2_REQUIRE(mor_box_rows(g) <= MOR_MAX_ROWS, "label_morph: the grown box %d has more than 2^25 rows (slices x rows: %lld)", j,
-                  (long long)mor_box_rows(g));
+    mor_grow(boxes + 6 * j, op, r2[j], sz, sy, sx, D, H, W, g);
     MorOrgan& o = all.o[j];
-    o.z0 = g[0], o.y0 = g[2], o.x0 = g[4];
-    o.bd = g[1] - g[0] + 1, o.bh = g[3] - g[2] + 1, o.bw = g[5] - g[4] + 1;
+    static_cast<LabelBox&>(o) = label_box(g);
+    MSAM2_REQUIRE(label_box_rows(o) <= LABEL_MAX_BOX_ROWS, "label_morph: the grown box %d has more than 2^25 rows (slices x rows: %lld)", j,
+                  (long long)label_box_rows(o));
     o.value = values[j], o.j = j;
     o.r2 = r2[j], o.cap = std::nextafter(r2[j], (double)INFINITY);
     listed.w[values[j] >> 5] |= 1u << (values[j] & 31);
-    largest = std::max(largest, mor_box_bytes(mor_box_vox(g), mor_keeps(op)));
+    bytes[j] = mor_box_bytes(label_box_voxels(o), mor_keeps(op));
   }
   const int64_t N = D * H * W;
-  const bool in_place = out == labels;
-  MSAM2_REQUIRE(in_place || out + N <= labels || labels + N <= out, "label_morph: out overlaps labels without being labels");
-  const size_t fixed = mor_fixed_bytes(N, op, in_place), need = fixed + largest;
+  LABEL_REQUIRE_OUT("label_morph", labels, out, N);
+  const size_t fixed = label_input_bytes(N, out == labels) + mor_best_bytes(N, op), need = fixed + label_tables_bytes(bytes, n, false);
   MSAM2_REQUIRE(workspace_bytes >= need, "label_morph: workspace too small (%zu of %zu bytes)", workspace_bytes, need);
   MSAM2_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)info & 3) == 0, "label_morph: the workspace must be 16-byte aligned, info 4-byte");
 
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   const dim3 blk(MOR_THREADS);
-  // the input every launch reads: labels, or its snapshot when the call is in place
-  const uint8_t* src = labels;
-  size_t at = MOR_FIXED_BYTES;
-  uint8_t* copy_to = out;
-  if (in_place) {
-    copy_to = (uint8_t*)(ws + at);
-    src = copy_to;
-    at += mor_round16((size_t)N);
-  }
-  double* best = (double*)(ws + at);                        // (dilate / close; never read before it is written: see mor_claim_kernel)
-  hipLaunchKernelGGL(mor_copy_kernel, dim3(grid1d(N, 4096, MOR_THREADS * 16)), blk, 0, s, labels, copy_to, N,
-                     (int)((((uintptr_t)labels | (uintptr_t)copy_to) & 15) == 0));
-  hipLaunchKernelGGL(mor_zero_kernel, dim3(1), dim3(LABEL_MAX_OBJ * 4), 0, s, info, (int)n * 4);
-  const size_t room = workspace_bytes - fixed;
+  const uint8_t* src = label_begin_out(labels, out, N, ws, info, n, s);
+  double* best = (double*)(ws + label_input_bytes(N, out == labels));   // (dilate / close; never read before it is written: see mor_claim_kernel)
   const double sx2 = sx * sx, sy2 = sy * sy, sz2 = sz * sz;
   // the stages: (first, second or -1), as flags of the row and z kernels
   const int first = (op == MOR_ERODE || op == MOR_OPEN ? MOR_STAGE_ERODE : 0) | (mor_keeps(op) ? MOR_STAGE_KEEP_D : 0) |
@@ -352,22 +292,16 @@ extern "C" int msam2_label_morph(const uint8_t* labels, int64_t D, int64_t H, in
                      : op == MOR_CLOSE ? MOR_STAGE_FROM_MASK | MOR_STAGE_ERODE | MOR_STAGE_LAST
                                        : -1;
   int64_t all_vox = 1;
-  int j = 0;
-  while (j < (int)n) {
+  for (int j = 0; j < (int)n;) {
     MorJobs jobs = {};
     jobs.H = (int)H, jobs.W = (int)W, jobs.keep = all.keep;
-    size_t used = 0;
     int64_t vox = 1, rows = 1;
-    for (; j < (int)n; ++j) {                               // the organs that follow, as long as their boxes fit
-      MorOrgan o = all.o[j];
-      const int64_t v = (int64_t)o.bd * o.bh * o.bw;
-      const size_t one = mor_box_bytes(v, mor_keeps(op));
-      if (jobs.n > 0 && used + one > room) break;           // (one alone fits: `need` covers the largest box)
-      o.ws = (long long)(fixed + used);
-      jobs.o[jobs.n++] = o;
-      used += one;
-      vox = std::max(vox, v), rows = std::max(rows, (int64_t)o.bd * o.bh);
-    }
+    j = label_next_group(bytes, (int)n, j, workspace_bytes - fixed, [&](int m, size_t at) {
+      MorOrgan& o = jobs.o[jobs.n++];
+      o = all.o[m];
+      o.ws = (long long)(fixed + at);
+      vox = std::max(vox, label_box_voxels(o)), rows = std::max(rows, label_box_rows(o));
+    });
     all_vox = std::max(all_vox, vox);
     const dim3 by_row(cdiv(rows, MOR_THREADS / 64), jobs.n), by_voxel(cdiv(vox, MOR_THREADS), jobs.n);
     for (int stage : {first, second}) {
@@ -379,8 +313,8 @@ extern "C" int msam2_label_morph(const uint8_t* labels, int64_t D, int64_t H, in
     if (mor_keeps(op))
       for (int k = 0; k < jobs.n; ++k) {
         const MorOrgan& o = jobs.o[k];
-        hipLaunchKernelGGL(mor_claim_kernel, dim3(cdiv((int64_t)o.bd * o.bh * o.bw, MOR_THREADS)), blk, 0, s, src, o, (int)H, (int)W, ws, listed,
-                           claim, out, best);
+        hipLaunchKernelGGL(mor_claim_kernel, dim3(cdiv(label_box_voxels(o), MOR_THREADS)), blk, 0, s, src, o, (int)H, (int)W, ws, listed, claim, out,
+                           best);
       }
   }
   if (mor_keeps(op))

@@ -19,8 +19,8 @@
 //     order inside a segment depends on scheduling, the multiset does not: the wrapper sorts.
 // Boxes are host integers and travel to the kernels by value (SrfJobs).  Apart from the workgroup barrier around that one add no thread waits
 // for another: no spin, no grid barrier, no cooperative launch.
-#include "common.h"
 #include "edt_passes.h"
+#include "label_boxes.h"
 
 #pragma clang fp contract(off)
 
@@ -29,8 +29,7 @@ namespace {
 constexpr int SRF_THREADS = 256;
 enum { SRF_SURFACE = 0, SRF_OUTSIDE = 1 };
 
-struct SrfOrgan {
-  int z0, y0, x0, bd, bh, bw;                               // the box: origin in the volume and sizes
+struct SrfOrgan : LabelBox {                                // the box
   int value;
   int cap[2];                                               // per direction: elements of the segment
   int pad_;
@@ -42,10 +41,9 @@ struct SrfJobs {                                            // a kernel argument
   SrfOrgan o[LABEL_MAX_OBJ];
 };
 
-__host__ __device__ __forceinline__ long long srf_round8(long long b) { return (b + 7) & ~7ll; }
 // one direction's share: t float64 per voxel, g uint16 per voxel, one int32 flag per slice of the box
 __host__ __device__ __forceinline__ long long srf_dir_bytes(long long bd, long long vox) {
-  return vox * 8 + srf_round8(vox * 2) + srf_round8(bd * 4);
+  return vox * 8 + label_round8(vox * 2) + label_round8(bd * 4);
 }
 
 struct SrfBufs {
@@ -54,9 +52,9 @@ struct SrfBufs {
   int* flag;
 };
 __device__ __forceinline__ SrfBufs srf_bufs(char* ws, const SrfOrgan& o, int dir) {
-  const long long vox = (long long)o.bd * o.bh * o.bw;
+  const long long vox = label_box_voxels(o);
   char* base = ws + o.ws + dir * srf_dir_bytes(o.bd, vox);
-  return {(double*)base, (uint16_t*)(base + vox * 8), (int*)(base + vox * 8 + srf_round8(vox * 2))};
+  return {(double*)base, (uint16_t*)(base + vox * 8), (int*)(base + vox * 8 + label_round8(vox * 2))};
 }
 
 // Is voxel (z, y, x) of the volume on the surface of v?  Nothing is read outside the volume.
@@ -70,6 +68,8 @@ __device__ __forceinline__ bool srf_on_surface(const uint8_t* __restrict__ vol, 
   const int64_t HW = (int64_t)H * W;
   return vol[i - HW] != v || vol[i + HW] != v;
 }
+
+typedef LabelBoxVoxel<int64_t> SrfVoxel;                   // (the kernels here use the position in the box only)
 
 // blockIdx.y = 2 * organ + direction.  Direction 0: queries from a, features from b; direction 1 the other way round.
 __global__ __launch_bounds__(SRF_THREADS) void srf_zero_kernel(SrfJobs jobs, char* __restrict__ ws, int* __restrict__ counts) {
@@ -101,11 +101,11 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_row_kernel(const uint8_t* __r
 __global__ __launch_bounds__(SRF_THREADS) void srf_col_kernel(SrfJobs jobs, char* __restrict__ ws, double sx2, double sy2) {
   const SrfOrgan& o = jobs.o[blockIdx.y >> 1];
   const int dir = blockIdx.y & 1;
-  const int64_t vox = (int64_t)o.bd * o.bh * o.bw;
+  const int64_t vox = label_box_voxels(o);
   const int64_t i = (int64_t)blockIdx.x * SRF_THREADS + threadIdx.x;
   if (i >= vox) return;
   const SrfBufs bufs = srf_bufs(ws, o, dir);
-  const int64_t r = i / o.bw;
+  const int64_t r = i / o.bw;                               // (LabelBoxVoxel's position, spelled out: with it the listing changes)
   const int xb = (int)(i - r * o.bw);
   const int zb = (int)(r / o.bh), yb = (int)(r - (int64_t)zb * o.bh);
   double best = __builtin_huge_val();
@@ -118,22 +118,11 @@ __device__ __forceinline__ double srf_scan_z(const double* __restrict__ t, const
   return edt_scan_z(t + (int64_t)yb * o.bw + xb, (int64_t)o.bh * o.bw, zb, o.bd, sz2, __builtin_huge_val());
 }
 
-// box voxel i -> (zb, yb, xb)
-struct SrfVoxel {
-  int zb, yb, xb;
-  __device__ __forceinline__ SrfVoxel(int64_t i, const SrfOrgan& o) {
-    const int64_t r = i / o.bw;
-    xb = (int)(i - r * o.bw);
-    zb = (int)(r / o.bh);
-    yb = (int)(r - (int64_t)zb * o.bh);
-  }
-};
-
 __global__ __launch_bounds__(SRF_THREADS) void srf_z_dense_kernel(SrfJobs jobs, char* __restrict__ ws, double sz2, double* __restrict__ out) {
   const SrfOrgan& o = jobs.o[0];
   const int64_t i = (int64_t)blockIdx.x * SRF_THREADS + threadIdx.x;
-  if (i >= (int64_t)o.bd * o.bh * o.bw) return;
-  const SrfVoxel v(i, o);
+  if (i >= label_box_voxels(o)) return;
+  const SrfVoxel v(i, o, jobs.H, jobs.W);
   out[i] = srf_scan_z(srf_bufs(ws, o, 0).t, o, v.zb, v.yb, v.xb, sz2);
 }
 
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
   const SrfOrgan& o = jobs.o[blockIdx.y >> 1];
   const int dir = blockIdx.y & 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t vox = (int64_t)o.bd * o.bh * o.bw;
+  const int64_t vox = label_box_voxels(o);
   const int64_t first = (int64_t)blockIdx.x * (SRF_Z_ITER * SRF_THREADS);
   if (first >= vox) return;                                 // the whole workgroup: the grid is sized for the largest box
   const uint8_t* __restrict__ q = dir ? b : a;
@@ -161,7 +150,7 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
     const int64_t i = first + it * SRF_THREADS + threadIdx.x;
     bool query = false;
     if (i < vox) {
-      const SrfVoxel v(i, o);
+      const SrfVoxel v(i, o, jobs.H, jobs.W);
       query = srf_on_surface(q, jobs.D, jobs.H, jobs.W, o.z0 + v.zb, o.y0 + v.yb, o.x0 + v.xb, o.value);
     }
     mine |= (query ? 1u : 0u) << it;
@@ -186,7 +175,7 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
     if (query) {
       const int64_t slot = at + lanes_below(qm, lane);
       if (slot < o.cap[dir]) {                              // past the capacity: counted, not stored
-        const SrfVoxel v(first + it * SRF_THREADS + threadIdx.x, o);
+        const SrfVoxel v(first + it * SRF_THREADS + threadIdx.x, o, jobs.H, jobs.W);
         out[o.seg[dir] + slot] = srf_scan_z(t, o, v.zb, v.yb, v.xb, sz2);
       }
     }
@@ -194,38 +183,15 @@ __global__ __launch_bounds__(SRF_THREADS) void srf_z_query_kernel(const uint8_t*
   }
 }
 
-// A box is six host integers (z0, z1, y0, y1, x0, x1), inclusive.  Is it upright and inside a D x H x W volume?
-bool srf_box_ok(const int32_t* box, int64_t D, int64_t H, int64_t W) {
-  return box[0] >= 0 && box[0] <= box[1] && box[1] < D && box[2] >= 0 && box[2] <= box[3] && box[3] < H && box[4] >= 0 && box[4] <= box[5] &&
-         box[5] < W;
-}
-// its sizes (of a box that srf_box_ok accepted)
-struct SrfExtent {
-  int bd, bh, bw;
-  int64_t rows() const { return (int64_t)bd * bh; }
-};
-SrfExtent srf_extent(const int32_t* box) { return {box[1] - box[0] + 1, box[3] - box[2] + 1, box[5] - box[4] + 1}; }
-// A spacing is usable iff its square is a normal float64 and 2^36 times it is finite: the largest squared index difference is below 2^33, so
-// no product or sum overflows (inf * 0 would be NaN at a feature voxel) and no square flushes to 0 or loses bits as a subnormal.  False for NaN.
-constexpr double SRF_MIN_SPACING2 = 2.2250738585072014e-308, SRF_MAX_SPACING2 = 1.7976931348623157e308 / 68719476736.0;
-bool srf_spacing_ok(double s) { return s > 0.0 && s * s >= SRF_MIN_SPACING2 && s * s <= SRF_MAX_SPACING2; }
-// The row pass runs one wave per row of the box in one launch: 64 threads per row must stay below 2^32 in all (2^25 rows: half of that).
-constexpr int64_t SRF_MAX_ROWS = 1ll << 25;
-bool srf_rows_ok(const int32_t* box) { return srf_extent(box).rows() <= SRF_MAX_ROWS; }
-
-void srf_set_box(SrfOrgan& o, const int32_t* box) {
-  const SrfExtent e = srf_extent(box);
-  o.z0 = box[0], o.y0 = box[2], o.x0 = box[4];
-  o.bd = e.bd, o.bh = e.bh, o.bw = e.bw;
-}
-int64_t srf_vox(const SrfOrgan& o) { return (int64_t)o.bd * o.bh * o.bw; }
+bool srf_rows_ok(const int32_t* box) { return label_box_rows(label_box(box)) <= LABEL_MAX_BOX_ROWS; }
+void srf_set_box(SrfOrgan& o, const int32_t* box) { static_cast<LabelBox&>(o) = label_box(box); }
 
 // the three passes up to t, for jobs.n organs and `dirs` directions
 void srf_launch_fields(const uint8_t* a, const uint8_t* b, int mode, const SrfJobs& jobs, int dirs, char* ws, double sy, double sx, int* counts,
                        hipStream_t s) {
   int64_t rows = 1, vox = 1;
   for (int j = 0; j < jobs.n; ++j) {
-    const int64_t r = (int64_t)jobs.o[j].bd * jobs.o[j].bh, v = srf_vox(jobs.o[j]);
+    const int64_t r = label_box_rows(jobs.o[j]), v = label_box_voxels(jobs.o[j]);
     if (r > rows) rows = r;
     if (v > vox) vox = v;
   }
@@ -238,7 +204,7 @@ void srf_launch_fields(const uint8_t* a, const uint8_t* b, int mode, const SrfJo
 }  // namespace
 
 extern "C" size_t msam2_label_edt_workspace_bytes(int64_t bd, int64_t bh, int64_t bw) {
-  if (!label_sizes_ok(bd, bh, bw, 1, LABEL_MAX_VOXELS) || bd * bh > SRF_MAX_ROWS) return 0;   // a box may be one row or column thin
+  if (!label_sizes_ok(bd, bh, bw, 1, LABEL_MAX_VOXELS) || bd * bh > LABEL_MAX_BOX_ROWS) return 0;   // a box may be one row or column thin
   return (size_t)srf_dir_bytes(bd, bd * bh * bw);
 }
 
@@ -249,13 +215,12 @@ extern "C" int msam2_label_edt(const uint8_t* labels, int64_t D, int64_t H, int6
   MSAM2_REQUIRE(value >= 0 && value <= 255, "label_edt: value %d (0 .. 255)", value);
   MSAM2_REQUIRE(features == SRF_SURFACE || features == SRF_OUTSIDE, "label_edt: features %d (0: the surface of value, 1: the voxels != value)",
                 features);
-  MSAM2_REQUIRE(srf_spacing_ok(sz) && srf_spacing_ok(sy) && srf_spacing_ok(sx), "label_edt: spacing (%g, %g, %g): every value must be positive with a square in 2.3e-308 .. 2.6e297", sz,
-                sy, sx);
+  LABEL_REQUIRE_SPACING("label_edt", sz, sy, sx);
   const int32_t whole[6] = {0, (int32_t)D - 1, 0, (int32_t)H - 1, 0, (int32_t)W - 1};
   if (!box) box = whole;                                    // host integers (z0, z1, y0, y1, x0, x1), inclusive
-  MSAM2_REQUIRE(srf_box_ok(box, D, H, W), "label_edt: box (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", box[0],
+  MSAM2_REQUIRE(label_box_ok(box, D, H, W), "label_edt: box (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", box[0],
                 box[1], box[2], box[3], box[4], box[5], (long long)D, (long long)H, (long long)W);
-  MSAM2_REQUIRE(srf_rows_ok(box), "label_edt: the box has more than 2^25 rows (slices x rows: %lld)", (long long)srf_extent(box).rows());
+  MSAM2_REQUIRE(srf_rows_ok(box), "label_edt: the box has more than 2^25 rows (slices x rows: %lld)", (long long)label_box_rows(label_box(box)));
   SrfJobs jobs = {};
   jobs.n = 1, jobs.D = (int)D, jobs.H = (int)H, jobs.W = (int)W;
   srf_set_box(jobs.o[0], box);
@@ -265,7 +230,7 @@ extern "C" int msam2_label_edt(const uint8_t* labels, int64_t D, int64_t H, int6
   MSAM2_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)d2 & 7) == 0, "label_edt: d2 / workspace must be 8-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   srf_launch_fields(labels, labels, features, jobs, 1, (char*)workspace, sy, sx, nullptr, s);
-  hipLaunchKernelGGL(srf_z_dense_kernel, dim3(cdiv(srf_vox(jobs.o[0]), SRF_THREADS)), dim3(SRF_THREADS), 0, s, jobs, (char*)workspace, sz * sz,
+  hipLaunchKernelGGL(srf_z_dense_kernel, dim3(cdiv(label_box_voxels(jobs.o[0]), SRF_THREADS)), dim3(SRF_THREADS), 0, s, jobs, (char*)workspace, sz * sz,
                      d2);
   return msam2_check_launch("label_edt");
 }
@@ -276,8 +241,8 @@ extern "C" size_t msam2_label_surface_distances_workspace_bytes(const int32_t* b
   size_t total = 0;
   for (int64_t j = 0; j < n; ++j) {
     const int32_t* bx = boxes + 6 * j;
-    if (!srf_box_ok(bx, LABEL_MAX_SLICES, LABEL_MAX_SIDE, LABEL_MAX_SIDE)) return 0;
-    const SrfExtent e = srf_extent(bx);
+    if (!label_box_ok(bx, LABEL_MAX_SLICES, LABEL_MAX_SIDE, LABEL_MAX_SIDE)) return 0;
+    const LabelBox e = label_box(bx);
     const size_t one = msam2_label_edt_workspace_bytes(e.bd, e.bh, e.bw);
     if (!one) return 0;
     total += 2 * one;
@@ -293,24 +258,21 @@ extern "C" int msam2_label_surface_distances(const uint8_t* pred, const uint8_t*
                 "label_surface_distances: null pred / gt / ids / boxes / seg_offsets / capacity / dist / counts / workspace");
   LABEL_REQUIRE_OBJECTS("label_surface_distances", n);
   LABEL_REQUIRE_SIZES("label_surface_distances", D, H, W, 2, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
-  MSAM2_REQUIRE(srf_spacing_ok(sz) && srf_spacing_ok(sy) && srf_spacing_ok(sx),
-                "label_surface_distances: spacing (%g, %g, %g): every value must be positive with a square in 2.3e-308 .. 2.6e297", sz, sy, sx);
+  LABEL_REQUIRE_SPACING("label_surface_distances", sz, sy, sx);
   MSAM2_REQUIRE(dist_len >= 0, "label_surface_distances: dist_len %lld", (long long)dist_len);
   SrfJobs jobs = {};
   jobs.n = (int)n, jobs.D = (int)D, jobs.H = (int)H, jobs.W = (int)W;
   long long at = 0;
   for (int j = 0; j < (int)n; ++j) {
     const int32_t* bx = boxes + 6 * j;
-    MSAM2_REQUIRE(srf_box_ok(bx, D, H, W),
-                  "label_surface_distances: box %d (%d..%d, %d..%d, %d..%d) is inverted or outside the %lld x %lld x %lld volume", j, bx[0], bx[1],
-                  bx[2], bx[3], bx[4], bx[5], (long long)D, (long long)H, (long long)W);
+    LABEL_REQUIRE_BOX("label_surface_distances", j, bx, D, H, W);
     MSAM2_REQUIRE(srf_rows_ok(bx), "label_surface_distances: box %d has more than 2^25 rows (slices x rows: %lld)", j,
-                  (long long)srf_extent(bx).rows());
+                  (long long)label_box_rows(label_box(bx)));
     SrfOrgan& o = jobs.o[j];
     srf_set_box(o, bx);
     o.value = ids[j];                                       // ids: HOST bytes, like the boxes
     o.ws = at;
-    at += 2 * srf_dir_bytes(o.bd, srf_vox(o));
+    at += 2 * srf_dir_bytes(o.bd, label_box_voxels(o));
     for (int d = 0; d < 2; ++d) {
       o.cap[d] = capacity[2 * j + d];
       o.seg[d] = seg_offsets[2 * j + d];
@@ -326,7 +288,7 @@ extern "C" int msam2_label_surface_distances(const uint8_t* pred, const uint8_t*
   srf_launch_fields(pred, gt, SRF_SURFACE, jobs, 2, (char*)workspace, sy, sx, counts, s);
   int64_t vox = 1;
   for (int j = 0; j < jobs.n; ++j)
-    if (srf_vox(jobs.o[j]) > vox) vox = srf_vox(jobs.o[j]);
+    if (label_box_voxels(jobs.o[j]) > vox) vox = label_box_voxels(jobs.o[j]);
   hipLaunchKernelGGL(srf_z_query_kernel, dim3(cdiv(vox, SRF_Z_ITER * SRF_THREADS), 2 * (unsigned)n), dim3(SRF_THREADS), 0, s, pred, gt, jobs,
                      (char*)workspace, sz * sz, dist, counts);
   return msam2_check_launch("label_surface_distances");

@@ -1507,6 +1507,42 @@ def _organ_extents(stats: "torch.Tensor"):
     return out
 
 
+def _organ_boxes(what: str, volumes, ids_d: torch.Tensor, distinct: bool = True):
+    """The preparation of the entries that work per organ inside a box -> (values, per volume: `_organ_extents`' list).  One `label_stats`
+    call per volume (z extent: the slices with count > 0; rows and columns: the stats' min / max), then ONE device-to-host copy of those
+    small tables with the ids: the only synchronisation on the way in.  distinct: ids taken from the device as they are must still be
+    distinct values in 1 .. 255."""
+    D, n = volumes[0].shape[0], ids_d.numel()
+    tables = [label_stats(v, ids_d)[0].reshape(-1) for v in volumes]
+    host = torch.cat(tables + [ids_d.to(torch.int32)]).cpu().numpy().astype("int64")                       # the one copy
+    m = D * n * 5
+    values = host[len(volumes) * m:].tolist()
+    _req(not distinct or (len(set(values)) == n and all(1 <= v <= 255 for v in values)), f"{what}: ids must be distinct values in 1 .. 255")
+    return values, [_organ_extents(host[k * m: (k + 1) * m].reshape(D, n, 5)) for k in range(len(volumes))]
+
+
+def _boxes_or_empty(extents):
+    """`_organ_extents`' list -> a box per organ, the voxel (0, 0, 0) for an absent one"""
+    return [list(box) if box is not None else [0, 0, 0, 0, 0, 0] for _, box in extents]
+
+
+def _out_volume(what: str, labels: torch.Tensor, out: Optional[torch.Tensor]):
+    """out=None (a new volume) or a uint8 volume to fill, labels itself for in place -> (out, in_place as the library's int)"""
+    if out is None:
+        out = torch.empty_like(labels)
+    _device_table(f"{what}: out", out, torch.uint8, labels.shape, labels.device, "labels'")
+    return out, int(out.data_ptr() == labels.data_ptr())
+
+
+def _box_workspace(what: str, values, per_box_need, all_at_once_need: int, workspace_bytes: int, dev):
+    """per_box_need[j]: what the box of values[j] alone needs -- refused above workspace_bytes -> (workspace, its bytes): what all organs need
+    at once, at most workspace_bytes (the library then goes through them in groups), 16-byte granular"""
+    for v, nb in zip(values, per_box_need):
+        _req(nb <= workspace_bytes, f"{what}: the box of id {v} alone needs a workspace of {nb} bytes, workspace_bytes is {workspace_bytes}")
+    nb = min(int(all_at_once_need), int(workspace_bytes))
+    return torch.empty((nb + 15) // 16 * 2, dtype=torch.int64, device=dev), nb                           # (the caching allocator aligns to 512 bytes)
+
+
 def label_surface_distances(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.0, 1.0), workspace_bytes: int = SURFACE_WORKSPACE_BYTES):
     """`surface_segments` with offsets int64 [n, 2] and capacity int32 [n, 2] as device tensors beside dist and counts: everything on the
     device (the two small tables go there in one asynchronous copy each)."""
@@ -1524,21 +1560,15 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
     rest of the segment up to its capacity (the organ's voxel count there) is +inf, so a sort of the whole segment puts the values first.
     An organ absent from either volume stores nothing (capacity 0; the count of the side that has it is still reported).
 
-    The boxes and capacities come from two `label_stats` calls (z extent: the slices with count > 0; rows and columns: the stats' min / max;
-    box = the union over pred and gt; capacity = the summed count).  One device-to-host copy of those two small tables (with the ids) is the
-    only synchronisation on the way in; nothing else is copied to the host.
+    The boxes and capacities come from `_organ_boxes` over pred and gt (box = the union of the two extents; capacity = the summed count): its
+    one device-to-host copy is the only synchronisation on the way in; nothing else is copied to the host.
     Organs are processed in groups whose workspace (20 bytes per box voxel) stays below `workspace_bytes`; an organ whose box alone needs more
     raises with the needed size in the message."""
     ids_d, D, H, W, n = _label_volume_args("label_surface_distances", pred, ids, min_side=2, max_voxels=True)
     _device_table("label_surface_distances: gt", gt, torch.uint8, pred.shape, pred.device, "labels'")
     sz, sy, sx = _spacing("label_surface_distances", spacing)
     dev = pred.device
-    sp, _ = label_stats(pred, ids_d)
-    sg, _ = label_stats(gt, ids_d)
-    host = torch.cat([sp.reshape(-1), sg.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")   # the one copy
-    m = D * n * 5
-    ext_p, ext_g = _organ_extents(host[:m].reshape(D, n, 5)), _organ_extents(host[m: 2 * m].reshape(D, n, 5))
-    values = host[2 * m:].tolist()
+    values, (ext_p, ext_g) = _organ_boxes("label_surface_distances", (pred, gt), ids_d, distinct=False)   # (an id listed twice is scored twice)
     boxes, caps, offs, total = [], [], [], 0
     for (cp, bp), (cg, bg) in zip(ext_p, ext_g):
         both = bp is not None and bg is not None
@@ -1553,9 +1583,6 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
     counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
     L = lib()
     need = [L.msam2_label_surface_distances_workspace_bytes((ctypes.c_int32 * 6)(*b), 1) for b in boxes]
-    for j, nb in enumerate(need):
-        _req(nb <= workspace_bytes, f"label_surface_distances: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
-                                    f"workspace_bytes is {workspace_bytes}")
     groups, cur, used = [], [], 0
     for j, nb in enumerate(need):
         if cur and used + nb > workspace_bytes:
@@ -1564,7 +1591,7 @@ def surface_segments(pred: torch.Tensor, gt: torch.Tensor, ids, spacing=(1.0, 1.
         cur.append(j)
         used += nb
     groups.append(cur)
-    ws = _workspace8(max(sum(need[j] for j in g) for g in groups), dev)
+    ws, _ = _box_workspace("label_surface_distances", values, need, max(sum(need[j] for j in g) for g in groups), workspace_bytes, dev)
     for g in groups:
         k = len(g)
         flat = lambda rows: [v for j in g for v in rows[j]]                                                 # noqa: E731
@@ -1594,8 +1621,8 @@ def label_fill_holes(labels: torch.Tensor, ids, connectivity: int = 6, max_voxel
     for in place (a D*H*W-byte snapshot of the input then rides in the workspace).  info = (holes found, voxels in them, holes that
     qualify, voxels of out that are ids[j] and were not in labels).
 
-    The boxes come from one `label_stats` call; one device-to-host copy of that small table (with the ids) is the only synchronisation,
-    nothing else is copied to the host.  Organs go through in groups whose workspace (9 bytes per box voxel, and the snapshot) stays below
+    The boxes come from `_organ_boxes`: its one device-to-host copy is the only synchronisation, nothing else is copied to the host.
+    Organs go through in groups whose workspace (9 bytes per box voxel, and the snapshot) stays below
     `workspace_bytes`; an organ whose box alone needs more raises with the needed size in the message."""
     ids_d, D, H, W, n = _label_volume_args("label_fill_holes", labels, ids, max_voxels=True)
     _req(int(connectivity) in LABEL_CONNECTIVITIES, f"label_fill_holes: connectivity {connectivity} (one of {LABEL_CONNECTIVITIES})")
@@ -1609,24 +1636,14 @@ def label_fill_holes(labels: torch.Tensor, ids, connectivity: int = 6, max_voxel
         vals = [int(max_voxels)] * n if isinstance(max_voxels, int) else [int(v) for v in max_voxels]
         _req(len(vals) == n and all(0 <= v < 2 ** 31 for v in vals), f"label_fill_holes: max_voxels must be {n} counts in 0 .. 2^31 - 1")
         mv = torch.tensor(vals, dtype=torch.int32).to(dev) if any(vals) else None
-    if out is None:
-        out = torch.empty_like(labels)
-    _device_table("label_fill_holes: out", out, torch.uint8, labels.shape, dev, "labels'")
-    in_place = int(out.data_ptr() == labels.data_ptr())
-    st, _ = label_stats(labels, ids_d)
-    host = torch.cat([st.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")              # the one copy
-    m = D * n * 5
-    values = host[m:].tolist()
-    _req(len(set(values)) == n and all(1 <= v <= 255 for v in values), "label_fill_holes: ids must be distinct values in 1 .. 255")
-    boxes = [list(box) if box is not None else [0, 0, 0, 0, 0, 0] for _, box in _organ_extents(host[:m].reshape(D, n, 5))]
+    out, in_place = _out_volume("label_fill_holes", labels, out)
+    values, (extents,) = _organ_boxes("label_fill_holes", (labels,), ids_d)
+    boxes = _boxes_or_empty(extents)
     L = lib()
     c, flat = int(connectivity), (ctypes.c_int32 * (6 * n))(*[v for b in boxes for v in b])
-    for j, b in enumerate(boxes):
-        nb = L.msam2_label_fill_holes_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, c, in_place, 0)
-        _req(nb <= workspace_bytes, f"label_fill_holes: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
-                                    f"workspace_bytes is {workspace_bytes}")
-    nb = min(L.msam2_label_fill_holes_workspace_bytes(D, H, W, flat, n, c, in_place, 1), int(workspace_bytes))
-    ws = torch.empty((nb + 15) // 16 * 2, dtype=torch.int64, device=dev)                                  # (the caching allocator aligns to 512 bytes)
+    need = [L.msam2_label_fill_holes_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, c, in_place, 0) for b in boxes]
+    ws, nb = _box_workspace("label_fill_holes", values, need, L.msam2_label_fill_holes_workspace_bytes(D, H, W, flat, n, c, in_place, 1),
+                            workspace_bytes, dev)
     info = torch.empty(n, 4, dtype=torch.int32, device=dev)
     check(L.msam2_label_fill_holes(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), flat, n, c, _p(mv), HOLE_CLAIMS[claim], _p(out), _p(info),
                                    _p(ws), nb, _stream()))
@@ -1668,8 +1685,8 @@ def label_morph(labels: torch.Tensor, ids, op: str, radius=None, radius2=None, s
     workspace).  info = (voxels before, voxels in the organ's own result set, voxels after, voxels taken from non-zero values); an absent organ
     gives a row of zeros and changes nothing.
 
-    The boxes come from one `label_stats` call; one device-to-host copy of that small table (with the ids) is the only synchronisation,
-    nothing else is copied to the host.  Organs go through in groups whose workspace (19 bytes per voxel of the organ's box grown by the ball,
+    The boxes come from `_organ_boxes`: its one device-to-host copy is the only synchronisation, nothing else is copied to the host.
+    Organs go through in groups whose workspace (19 bytes per voxel of the organ's box grown by the ball,
     11 for erode / open; dilate / close also 8 bytes per voxel of the volume) stays below `workspace_bytes`; an organ whose box alone needs more
     raises with the needed size in the message.  The result depends on neither the grouping nor the boxes."""
     ids_d, D, H, W, n = _label_volume_args("label_morph", labels, ids, min_side=2, max_voxels=True)
@@ -1678,25 +1695,17 @@ def label_morph(labels: torch.Tensor, ids, op: str, radius=None, radius2=None, s
     sz, sy, sx = _spacing("label_morph", spacing)
     r2 = _radius2("label_morph", radius, radius2, n)
     dev = labels.device
-    if out is None:
-        out = torch.empty_like(labels)
-    _device_table("label_morph: out", out, torch.uint8, labels.shape, dev, "labels'")
-    in_place = int(out.data_ptr() == labels.data_ptr())
-    st, _ = label_stats(labels, ids_d)
-    host = torch.cat([st.reshape(-1), ids_d.to(torch.int32)]).cpu().numpy().astype("int64")              # the one copy
-    m = D * n * 5
-    values = host[m:].tolist()
-    _req(len(set(values)) == n and all(1 <= v <= 255 for v in values), "label_morph: ids must be distinct values in 1 .. 255")
-    boxes = [list(box) if box is not None else [0, 0, 0, 0, 0, 0] for _, box in _organ_extents(host[:m].reshape(D, n, 5))]
+    out, in_place = _out_volume("label_morph", labels, out)
+    values, (extents,) = _organ_boxes("label_morph", (labels,), ids_d)
+    boxes = _boxes_or_empty(extents)
     L = lib()
     o, flat, r2s = MORPH_OPS[op], (ctypes.c_int32 * (6 * n))(*[v for b in boxes for v in b]), (ctypes.c_double * n)(*r2)
-    for j, b in enumerate(boxes):
-        nb = L.msam2_label_morph_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, o, (ctypes.c_double * 1)(r2[j]), sz, sy, sx, in_place, 0)
-        _req(nb > 0, f"label_morph: the box of id {values[j]} grown by its ball has more than 2^25 rows (slices x rows)")
-        _req(nb <= workspace_bytes, f"label_morph: the box of id {values[j]} alone needs a workspace of {nb} bytes, "
-                                    f"workspace_bytes is {workspace_bytes}")
-    nb = min(L.msam2_label_morph_workspace_bytes(D, H, W, flat, n, o, r2s, sz, sy, sx, in_place, 1), int(workspace_bytes))
-    ws = torch.empty((nb + 15) // 16 * 2, dtype=torch.int64, device=dev)                                  # (the caching allocator aligns to 512 bytes)
+    need = [L.msam2_label_morph_workspace_bytes(D, H, W, (ctypes.c_int32 * 6)(*b), 1, o, (ctypes.c_double * 1)(r2[j]), sz, sy, sx, in_place, 0)
+            for j, b in enumerate(boxes)]
+    for v, nb in zip(values, need):
+        _req(nb > 0, f"label_morph: the box of id {v} grown by its ball has more than 2^25 rows (slices x rows)")
+    ws, nb = _box_workspace("label_morph", values, need, L.msam2_label_morph_workspace_bytes(D, H, W, flat, n, o, r2s, sz, sy, sx, in_place, 1),
+                            workspace_bytes, dev)
     info = torch.empty(n, 4, dtype=torch.int32, device=dev)
     check(L.msam2_label_morph(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), flat, n, o, r2s, sz, sy, sx, HOLE_CLAIMS[claim], _p(out),
                               _p(info), _p(ws), nb, _stream()))

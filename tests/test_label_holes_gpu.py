@@ -134,6 +134,19 @@ def test_in_place_gives_the_out_of_place_bytes(name):
             assert np.array_equal(labels.cpu().numpy(), got[0])
 
 
+@pytest.mark.parametrize("shift", (0, 1))
+def test_in_place_on_an_odd_volume_inside_a_guarded_buffer(shift):
+    """5 x 6 x 7 = 210 bytes, no multiple of 16, as labels AND out: the snapshot is copied 16 bytes at a time and its last two bytes singly
+    (shift 0), or byte by byte from an odd address (shift 1); the canvas around the volume keeps its 0xEE on both sides"""
+    fx = BY_NAME["odd_sizes"]
+    want = reference("odd_sizes", 6, fx.max_voxels is not None, "any")
+    canvas, labels = padded(fx.vol, 0xEE, shift)
+    labels.copy_(torch.from_numpy(fx.vol))
+    got = fill(labels, fx.ids, 6, fx.max_voxels, "any", out=labels)
+    assert same(got, want) and np.array_equal(labels.cpu().numpy(), want[0])
+    assert intact(canvas, labels, 0xEE)
+
+
 @pytest.mark.parametrize("name", ["random", "size_limits", "absent_and_unordered", "nested_inner_first"])
 def test_workspace_budget(name):
     """a budget that holds one box at a time gives the same result; one below the largest box raises and names the needed size"""

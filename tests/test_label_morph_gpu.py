@@ -176,6 +176,22 @@ def test_in_place_gives_the_out_of_place_bytes(name):
             assert np.array_equal(labels.cpu().numpy(), got[0])
 
 
+@pytest.mark.parametrize("shift", (0, 1))
+def test_in_place_on_an_odd_volume_inside_a_guarded_buffer(shift):
+    """5 x 11 x 67 = 3685 bytes, no multiple of 16, as labels AND out: the snapshot is copied 16 bytes at a time and its last five bytes
+    singly (shift 0), or byte by byte from an odd address (shift 1); the canvas around the volume keeps its 0xEE on both sides"""
+    name = "odd_5x11x67"
+    fx = BY_NAME[name]
+    ri = len(fx.radii) - 1
+    for op in ("erode", "close"):
+        want = reference(name, op, 1, ri, "any")
+        canvas, labels = padded(fx.vol, 0xEE, shift)
+        labels.copy_(torch.from_numpy(fx.vol))
+        got = morph(labels, fx, op, 1, ri, "any", out=labels)
+        assert same(got, want) and np.array_equal(labels.cpu().numpy(), want[0]), op
+        assert intact(canvas, labels, 0xEE), op
+
+
 @pytest.mark.parametrize("op", R.OPS)
 @pytest.mark.parametrize("name", ["blobs_7x24x40", "facing_plates", "lesion_and_absent", "organs32"])
 def test_workspace_budget(name, op):
