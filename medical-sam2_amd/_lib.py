@@ -30,6 +30,8 @@ SIGNATURES = {
     "msam2_gemm_residual_layernorm": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_gemm_merged_residual_layernorm_supported": (c_i, [c_l, c_l, c_i]),
     "msam2_gemm_merged_residual_layernorm": (c_i, [c_p, c_z, c_i, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_l, c_l, c_p]),
+    "msam2_mlp_residual_layernorm_supported": (c_i, [c_l, c_l]),
+    "msam2_mlp_residual_layernorm_fwd": (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_f, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_ln_mlp_residual_supported": (c_i, [c_l]),
     "msam2_mlp_fused_permute_w2": (c_i, [c_p, c_p, c_l, c_l, c_p]),
     "msam2_ln_mlp_residual_fwd": (c_i, [c_p, c_l, c_l, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),

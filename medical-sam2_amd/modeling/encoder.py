@@ -27,6 +27,11 @@ _FUSED_GEMM_LN = _os.environ.get("MSAM2_NO_FUSED_GEMM_LN") is None   # A/B switc
 # per-shape switch of that fusion: the reduction lengths that are dispatched (384: the proj GEMM of a stage-3 block, 1536: its fc2).  A shape
 # that does not beat its two launches inside the step is taken off this list and stays in the library
 _FUSED_GEMM_LN_K = frozenset(int(k) for k in _os.environ.get("MSAM2_FUSED_GEMM_LN_K", "384,1536").split(",") if k.strip())
+# A/B switch: fc1 + GELU, fc2 + residual and the next block's norm1 of a stage-3 block as ONE kernel (ops.mlp_residual_layernorm, DESIGN.md
+# 3.12); MSAM2_NO_FUSED_MLP_LN=1 restores the two launches.  The form is dispatched from _FUSED_MLP_LN_MIN_TOKENS tokens per slice upward (the
+# one-kernel MLP's own gate): the product's 64 x 64 map is the shape it was measured at, smaller maps keep the pair of launches
+_FUSED_MLP_LN = _os.environ.get("MSAM2_NO_FUSED_MLP_LN") is None
+_FUSED_MLP_LN_MIN_TOKENS = 1024
 # A/B switch: the proj GEMM, the one-kernel MLP and the next block's norm1 of a stage 1-2 block as the launches they were
 _FUSED_PROJ_MLP = _os.environ.get("MSAM2_NO_FUSED_PROJ_MLP") is None
 # per-shape switches of that fusion: the widths at which the proj GEMM is folded into the MLP kernel, and those at which that kernel also
@@ -55,6 +60,11 @@ class two_launch_qkv_attention:
 def _gemm_ln_dispatched(N: int, K: int) -> bool:
     """Does a residual GEMM [*, K] -> [*, N] that was handed a LayerNorm run both as one kernel?  (per-slice quantities only, never B)"""
     return _FUSED_GEMM_LN and K in _FUSED_GEMM_LN_K and ops.gemm_residual_layernorm_supported(N, K)
+
+
+def _mlp_ln_dispatched(N: int, H: int) -> bool:
+    """Does a two-layer GELU MLP [*, N] -> [*, H] -> [*, N] that was handed a LayerNorm run as one kernel?  (per-slice quantities only, never B)"""
+    return _FUSED_GEMM_LN and _FUSED_MLP_LN and ops.mlp_residual_layernorm_supported(N, H)
 
 
 def _proj_mlp_dispatched(dim_out: int, width: int) -> bool:
@@ -127,11 +137,19 @@ class MLP(nn.Module):
         self._act_code = ops.ACT_GELU if isinstance(self.act, nn.GELU) else ops.ACT_RELU
         self._wc = WeightCache()
 
-    def run(self, x_bf16: torch.Tensor, residual: Optional[torch.Tensor] = None, out_dtype=F32, ln=None):
+    def run(self, x_bf16: torch.Tensor, residual: Optional[torch.Tensor] = None, out_dtype=F32, ln=None, one_kernel: bool = False):
         """x [rows, in] bf16 -> [rows, out]; hidden activations bf16, last layer (+ residual) in out_dtype.
         ln = (weight, bias, eps) of the LayerNorm that follows (only the inference trunk passes one): the result is then the pair
-        (rows, LayerNorm(rows) in the 16-bit operand type, or None where the last GEMM could not produce it in the same kernel)."""
+        (rows, LayerNorm(rows) in the 16-bit operand type, or None where the last GEMM could not produce it in the same kernel).
+        one_kernel (the inference trunk, with ln): a two-layer GELU MLP whose shape is built runs both GEMMs, the residual add and the
+        LayerNorm as one launch, the hidden activations never written (same bits as the two launches)."""
         h = x_bf16
+        if (one_kernel and ln is not None and residual is not None and out_dtype == F32 and self.num_layers == 2 and not self.sigmoid_output
+                and self._act_code == ops.ACT_GELU and _mlp_ln_dispatched(self.layers[1].out_features, self.layers[0].out_features)
+                and self.layers[0].in_features == self.layers[1].out_features):
+            l0, l1 = self.layers
+            return ops.mlp_residual_layernorm(h, w_bf16(self._wc, "w0", l0.weight), v_f32(self._wc, "b0", l0.bias),
+                                              w_bf16(self._wc, "w1", l1.weight), v_f32(self._wc, "b1", l1.bias), residual, *ln)
         for i, layer in enumerate(self.layers):
             last = i == self.num_layers - 1
             last_act = ops.ACT_SIGMOID if self.sigmoid_output else ops.ACT_NONE
@@ -318,7 +336,7 @@ class MultiScaleBlock(nn.Module):
         if xn2 is None:
             xn2 = ops.layernorm(t, v_f32(wc, "n2w", self.norm2.weight), v_f32(wc, "n2b", self.norm2.bias), 1e-6)
         if fused_gemm_ln and next_norm is not None:   # fc2 writes the next block's norm1 rows as well, where that form is dispatched
-            t, self.next_xn = mlp.run(xn2, residual=t, out_dtype=F32, ln=next_norm)
+            t, self.next_xn = mlp.run(xn2, residual=t, out_dtype=F32, ln=next_norm, one_kernel=Hq * Wq >= _FUSED_MLP_LN_MIN_TOKENS)
         else:
             t = mlp.run(xn2, residual=t, out_dtype=F32)
         return t, Hq, Wq

@@ -291,6 +291,42 @@ def gemm_residual_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[tor
     return out, out16
 
 
+def mlp_residual_layernorm_supported(N: int, H: int) -> bool:
+    """True when `mlp_residual_layernorm` is built for this width and hidden width (per-slice quantities only)."""
+    return bool(lib().msam2_mlp_residual_layernorm_supported(N, H))
+
+
+def mlp_residual_layernorm(a: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor],
+                           residual: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, eps: float, *, out: Optional[torch.Tensor] = None,
+                           out16: Optional[torch.Tensor] = None):
+    """(c32, y16) = (gelu(a @ w1^T + b1) @ w2^T + b2 + residual in fp32, LayerNorm(c32 rows) in the 16-bit operand type) from one kernel;
+    the hidden activations are rounded to the operand type and never leave the chip: the bits of `gemm(a, w1, b1, act=ACT_GELU)` followed
+    by `gemm_residual_layernorm(h, w2, b2, residual, ...)`.  a [M, N], w1 [H, N], w2 [N, H] 16-bit as stored, residual fp32 [M, N].  A form
+    that is not built (`mlp_residual_layernorm_supported`) is an error."""
+    _req(a.dim() == 2 and w1.dim() == 2 and w2.dim() == 2 and a.shape[1] == w1.shape[1] and w2.shape == (w1.shape[1], w1.shape[0]),
+         f"mlp_residual_layernorm shapes {tuple(a.shape)} x {tuple(w1.shape)} x {tuple(w2.shape)}")
+    _req(a.dtype == OP16 and w1.dtype == OP16 and w2.dtype == OP16 and a.stride(1) == 1 and w1.stride(1) == 1 and w2.stride(1) == 1,
+         "mlp_residual_layernorm operands: 16-bit, reduction dimension contiguous")
+    M, N = a.shape
+    H = w1.shape[0]
+    _req(mlp_residual_layernorm_supported(N, H), f"mlp_residual_layernorm: N = {N}, H = {H} is not built (N = 384 with H % 128 == 0)")
+    _req(residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1, "mlp_residual_layernorm: residual must be fp32 [M, N]")
+    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
+         and (b1 is None or (b1.dtype == F32 and b1.numel() == H and b1.is_contiguous()))
+         and (b2 is None or (b2.dtype == F32 and b2.numel() == N and b2.is_contiguous())),
+         "mlp_residual_layernorm: b1 is fp32 [H]; b2, ln_w, ln_b are fp32 [N]")
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=a.device)
+    if out16 is None:
+        out16 = torch.empty(M, N, dtype=OP16, device=a.device)
+    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
+         "mlp_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    check(lib().msam2_mlp_residual_layernorm_fwd(_p(a), a.stride(0), _p(w1), w1.stride(0), _p(b1), _p(w2), w2.stride(0), _p(b2), _p(residual),
+                                                 residual.stride(0), _p(out), out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16),
+                                                 out16.stride(0), M, N, H, _stream()))
+    return out, out16
+
+
 def gemm_merged_residual_layernorm_supported(N: int, D: int, splits: int) -> bool:
     """True when `gemm_merged_residual_layernorm` is built for this output width, head dim and (effective) split count."""
     return bool(lib().msam2_gemm_merged_residual_layernorm_supported(N, D, splits))
