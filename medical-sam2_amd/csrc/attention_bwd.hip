@@ -233,7 +233,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
     op16x8 wf[2];
     const int row0 = tile * C::BK;
     if constexpr (ROLE == ROLE_DQ) {
-      // (rows past the end of the keys hold zeros in LDS: whatever weight they get multiplies a zero K^T column)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float pe = __builtin_amdgcn_exp2f(s[e] * p.scale_log2 - lse_own);
@@ -241,6 +240,14 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_kernel(AttnBwdParams p) {
         if constexpr (DROP)                              // owner = query oi, streamed row = key: the forward's mask on dP
           dpe = dropout_keep(drop_seed, drop_own + (uint64_t)(row0 + (e & 3) + 8 * (e >> 2) + 4 * h), p.drop.thr) ? dpe * p.drop.inv_keep : 0.f;
         wf[e >> 3][e & 7] = f2op(pe * (dpe - delta_own));
+      }
+      // rows past the end of the keys hold zeros in LDS, but their weight 2^(0 - lse) (0 - delta) is inf or NaN for a row whose scores
+      // are all far below zero (lse <= -128), and inf * 0 poisons the row: the partial last tile zeroes them (a wave-uniform branch,
+      // so the full tiles keep their instruction stream)
+      if (row0 + C::BK > n_str) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          if (row0 + (e & 3) + 8 * (e >> 2) + 4 * h >= n_str) wf[e >> 3][e & 7] = (op16)0.f;
       }
     } else {
       const float* st_lse = stats + cur * 2 * C::BK;

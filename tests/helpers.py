@@ -160,7 +160,9 @@ def _mangled_template_args(rest: str):
 def kernel_key(name: str) -> str:
     """'void gemm_kernel<128, 32, 4, 1>(GemmParams)' or its mangled form '_Z11gemm_kernelILi128ELi32ELi4ELi1EEv10GemmParams' ->
     'gemm_kernel<128,32,4,1>'; type arguments keep their demangled spelling: 'void layernorm_kernel<float, _Float16, 2>(...)' and
-    '_Z16layernorm_kernelIfDF16_Li2EEv...' -> 'layernorm_kernel<float,_Float16,2>' (__bf16 in the bf16 build)"""
+    '_Z16layernorm_kernelIfDF16_Li2EEv...' -> 'layernorm_kernel<float,_Float16,2>' (__bf16 in the bf16 build); a kernel of an unnamed
+    namespace ('(anonymous namespace)::attn_bwd_kernel<...>', '_ZN12_GLOBAL__N_115attn_bwd_kernel...') is keyed by its own name"""
+    name = re.sub(r"^_ZN12_GLOBAL__N_1", "_Z", name.strip().replace("(anonymous namespace)::", ""))
     m = re.match(r"_Z(\d+)", name)
     if m:
         n = int(m.group(1))

@@ -28,7 +28,7 @@ LOG = os.path.join(ROOT, "gpurun_out", "bf16_suite.log")
 # 512-slice volume (half a minute of CPU oracle that would compete with the fp16 session's own) and the multi-process files, which spawn
 # their own children.
 FILES = ["tests/test_kernels_gpu.py", "tests/test_gemm_variants_gpu.py", "tests/test_attention_variants_gpu.py", "tests/test_pointwise_variants_gpu.py",
-         "tests/test_backward_variants_gpu.py",
+         "tests/test_backward_variants_gpu.py", "tests/test_attention_bwd_variants_gpu.py",
          "tests/test_modules_gpu.py",
          "tests/test_e2e_gpu.py", "tests/test_operand_rounding_gpu.py", "tests/test_properties_gpu.py", "tests/test_graphs_gpu.py", "tests/test_eval_seg.py",
          "tests/test_backward_gpu.py", "tests/test_backward_encoder_gpu.py", "tests/test_grads_golden.py", "tests/test_bptt_gpu.py",
