@@ -382,6 +382,43 @@ __device__ __forceinline__ float group16_sum(float v) {
   return v;
 }
 
+// layernorm_kernel's row arithmetic (elementwise.hip) with every rounding WRITTEN OUT, for the kernels that hold whole rows and finish
+// them in their epilogue (conv_mfma.hip, and through rowtile.h gemm_rowln.hip and mlp_rowln.hip): the one statement of it outside that
+// kernel.  layernorm_kernel's source leaves the choice of which multiply meets which add in one fma to the compiler
+// (-ffp-contract=fast); the forms below are the ones its listings show, the same in every instance and in both builds, and contraction is
+// switched off here so that no caller can be given other ones (conv3x3s2_mfma_kernel's 16-bit conversions invite the vectoriser to pair
+// the multiplies first, which had split the GELU's `1 + 0.3275911 ax` into a product and a sum at C = 256: one output in 230 000 an ulp off).
+//   A row of C elements lies in LPR lanes, CPL chunks of four per lane.  Sum and sum of squares: a lane adds its elements in order,
+//   q = d1 d1, then fma(d0, d0, q), fma(d2, d2, q), ...; lanes meet through xor-shuffles, widest first (group16_add at LPR = 16; with
+//   fewer live lanes the wider steps of that kernel add zeros and are left out);  value: fma(w, rstd (x - mean), b).
+template <int CPL, int LPR, int C>
+__device__ __forceinline__ void ln_row_stats(const float (&v)[CPL][4], float eps, float& mean, float& rstd) {
+#pragma clang fp contract(off)
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < CPL; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s += v[j][e];
+#pragma unroll
+  for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  mean = s / C;
+  const float d0 = v[0][0] - mean, d1 = v[0][1] - mean;
+  float q = d1 * d1;
+  q = __builtin_fmaf(d0, d0, q);
+#pragma unroll
+  for (int i = 2; i < CPL * 4; ++i) {
+    const float d = v[i >> 2][i & 3] - mean;
+    q = __builtin_fmaf(d, d, q);
+  }
+#pragma unroll
+  for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  rstd = 1.0f / sqrtf(q / C + eps);
+}
+__device__ __forceinline__ float ln_row_value(float x, float mean, float rstd, float w, float b) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(w, rstd * (x - mean), b);
+}
+
 // the two pieces of the bicubic convolution kernel (A = -0.75 in torch): |x| <= 1 and 1 < |x| < 2 -- the position-table resize and its adjoint
 __device__ __forceinline__ float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
 __device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }

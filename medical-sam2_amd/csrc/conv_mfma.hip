@@ -16,8 +16,8 @@
 //     here runs the four quarters one after the other);
 //   * acc + bias goes as fp32 into one row-major LDS tile [32 WR][COUT + 4], which is walked in layernorm_kernel's geometry (16 lanes per
 //     row, lane chunks l + 16 j; 4 lanes per row at COUT = 16, where 12 of that kernel's 16 lanes hold zeros): sum, centred second pass,
-//     rstd, gelu_erf_as, f2op -- its arithmetic in its order, RESTATED with every fma written out (ln_row_stats, ln_gelu_value below;
-//     layernorm_kernel is left as it is).
+//     rstd, gelu_erf_as, f2op -- its arithmetic in its order, RESTATED with every fma written out (ln_row_stats, ln_row_value in common.h, which
+//     the full-row GEMM kernels share; ln_gelu_value below; layernorm_kernel is left as it is).
 // Operands come straight from global memory into the fragment registers, two groups of k-steps in flight (the next group's loads are
 // issued before the MFMAs of the current one): the input pixels of a wave are re-read by neighbouring taps from L1, the weight (at most
 // 295 KB) from L2.  All loads are unconditional with clamped addresses and zeroed afterwards; rows past the last pixel are clamped on
@@ -36,41 +36,12 @@ struct ConvLnParams {
   float eps;
 };
 
-// layernorm_kernel's row arithmetic (elementwise.hip, act = GELU) with every rounding WRITTEN OUT.  That kernel's source leaves the choice
-// of which multiply meets which add in one fma to the compiler (-ffp-contract=fast); the forms below are the ones its listings show, the
-// same in every instance and in both builds, and contraction is switched off here so that this kernel cannot be given other ones (its
-// 16-bit conversions invite the vectoriser to pair the multiplies first, which had split `1 + 0.3275911 ax` into a product and a sum at
-// C = 256: one output in 230 000 an ulp off).
-//   sum and sum of squares: a lane adds its elements in order, q = d1 d1, then fma(d0, d0, q), fma(d2, d2, q), ...; lanes meet through
-//   xor-shuffles, widest first (group16_add; with fewer than 16 live lanes the wider steps of that kernel add zeros and are left out);
-//   u = fma(w, rstd (x - mean), b);  GELU (gelu_erf_as): d = fma(ax, 0.3275911, 1), Horner by fma, max(u, 0) - (|u| / 2)(poly ex) as one fma.
-template <int CPL, int LPR, int C>
-__device__ __forceinline__ void ln_row_stats(const float (&v)[CPL][4], float eps, float& mean, float& rstd) {
-#pragma clang fp contract(off)
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < CPL; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s += v[j][e];
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  mean = s / C;
-  const float d0 = v[0][0] - mean, d1 = v[0][1] - mean;
-  float q = d1 * d1;
-  q = __builtin_fmaf(d0, d0, q);
-#pragma unroll
-  for (int i = 2; i < CPL * 4; ++i) {
-    const float d = v[i >> 2][i & 3] - mean;
-    q = __builtin_fmaf(d, d, q);
-  }
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  rstd = 1.0f / sqrtf(q / C + eps);
-}
-
+// layernorm_kernel's value with act = GELU, every rounding WRITTEN OUT and contraction off, as ln_row_stats / ln_row_value (common.h)
+// state the row arithmetic and for their reason: u = ln_row_value;  GELU (gelu_erf_as): d = fma(ax, 0.3275911, 1), Horner by fma,
+// max(u, 0) - (|u| / 2)(poly ex) as one fma.
 __device__ __forceinline__ float ln_gelu_value(float x, float mean, float rstd, float w, float b) {
 #pragma clang fp contract(off)
-  const float u = __builtin_fmaf(w, rstd * (x - mean), b);
+  const float u = ln_row_value(x, mean, rstd, w, b);
   const float ab = fabsf(u);
   const float ax = ab * 0.70710678118654752440f;
   const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(ax, 0.3275911f, 1.0f));

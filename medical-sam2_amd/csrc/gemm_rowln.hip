@@ -26,8 +26,12 @@
 //     per wave, lane chunks l16 + 16 j) in two passes of 32 rows.  A lane's 12 residual chunks, gamma and beta are loaded up front, before
 //     any store (one in-order counter: a load behind a store waits for the store's round trip).  x = (acc + bias) + r is
 //     gemm_epilogue_direct's fp32 + residual association; mean, centred sum of squares, rstd and the 16-bit output are layernorm_kernel's
-//     expressions in its order (elementwise.hip), RESTATED here: layernorm_kernel is left as it is.
+//     expressions in its order (elementwise.hip) as common.h states them, every fma written out (ln_row_stats, ln_row_value);
+//     layernorm_kernel is left as it is.
 // Rows past M are clamped on load and masked on store.  Every wave runs the same number of barriers.
+// The tile's constants (RowTile<N>), the W prefetch, the k-step and the epilogue are rowtile.h's, which mlp_rowln.hip shares; so are the
+// refusals and the params fill the C entries below have in common (rowtile_check, rowtile_fill_out).  Here: the ring, `issue`, the
+// main loop, the merged-A prologue.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage): 155 VGPRs, 53 SGPRs in both builds, no scratch, one workgroup per CU by its 112 KB of LDS.
 // Measured inside the benchmark step: K = 384 18.1 us against 17.9 + 9.1 for the pair, K = 1536 43.7 against 36.0 + 9.1.
 //
@@ -38,11 +42,12 @@
 //     every thread merges the 16-byte chunks it owns with attn_merge_kernel's arithmetic (attention.hip) and stores them into K / 64
 //     RESIDENT 8 KB images in front of the ring; the ring then carries W alone (32 KB stages), so the prefetch's throw-away pieces and
 //     the next W tile never touch an image.  The epilogue tile aliases images and ring behind the barrier that ends the main loop.
-// The arithmetic the new instances restate (the merge, the LayerNorm) is compiled with contraction off and its fused multiply-adds
-// spelled as the restated kernels' listings show them; <384, 0> keeps the source form it was measured and tested with.
+// The merge is restated here, compiled with contraction off and its fused multiply-adds spelled as attn_merge_kernel's listings show
+// them; the LayerNorm of every instance is the written-out form of common.h (for <384, 0> it is what the compiler made of the source form
+// the kernel was measured and tested with: same listing).
 // Registers: <256, 0> 92, <256, 64> 91, <256, 256> 190 VGPRs (a thread's 4 x 8 partial chunks are loaded up front), 53 - 55 SGPRs, 80 / 72
 // / 96 KB of LDS, no scratch in both builds.  In the step: 34.3 -> 17.0 us (K = 256) and 32.5 -> 12.2 us (K = 64) per chain of three launches.
-#include "common.h"
+#include "rowtile.h"
 #include <stdlib.h>
 
 struct RowLnParams {
@@ -63,52 +68,18 @@ struct RowLnParams {
   int splits;            // 2 .. 8
 };
 
-// layernorm_kernel's row arithmetic with every rounding WRITTEN OUT, as conv_mfma.hip states it from that kernel's listings (the same in
-// every instance and in both builds): the instances of this file that are new state it instead of leaving the pairing of multiplies and
-// adds to -ffp-contract=fast; the N = 384 instance keeps the source form it was measured and tested with.
-template <int CH, int N>
-__device__ __forceinline__ void rowln_stats(const float (&v)[CH][4], float eps, float& mean, float& rstd) {
-#pragma clang fp contract(off)
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < CH; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s += v[j][e];
-  group16_add(s);
-  mean = s / N;
-  const float d0 = v[0][0] - mean, d1 = v[0][1] - mean;
-  float q = d1 * d1;
-  q = __builtin_fmaf(d0, d0, q);
-#pragma unroll
-  for (int i = 2; i < CH * 4; ++i) {
-    const float d = v[i >> 2][i & 3] - mean;
-    q = __builtin_fmaf(d, d, q);
-  }
-  group16_add(q);
-  rstd = 1.0f / sqrtf(q / N + eps);
-}
-__device__ __forceinline__ float rowln_value(float x, float mean, float rstd, float w, float b) {
-#pragma clang fp contract(off)
-  return __builtin_fmaf(w, rstd * (x - mean), b);
-}
-
 // MD = 0: A is a 16-bit matrix that goes through the ring with W.  MD = 64 / 256 (= K): A is built in LDS from split-KV partials.
 template <int N, int MD>
 __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Img128 Img;
   constexpr bool MERGED = MD != 0;
-  constexpr int BM = 64, BK = 64, NST = 2, KS = BK / 16;
-  constexpr int A_BYTES = BM * BK * 2;                                     // 8 KB
+  typedef RowTile<N> T;
+  constexpr int BM = T::BM, BK = T::BK, A_BYTES = T::A_BYTES, WPW = T::WPW, FN = T::FN, NST = 2;
   constexpr int RES_BYTES = MERGED ? (MD / BK) * A_BYTES : 0;              // merged: the A images of the whole K, resident in front of the ring
   constexpr int W_OFF = MERGED ? 0 : A_BYTES;                              // where W starts inside a stage
-  constexpr int STAGE_BYTES = W_OFF + N * BK * 2;                          // N = 384: 8 KB + 48 KB
-  constexpr int WPW = N / Img::PIECE_ROWS / 8;       // W pieces per wave and stage: 6
-  constexpr int FN = N / 4 / 32;                     // 32-column accumulators per wave: 3
-  constexpr int TLD = N + 4;                         // floats per row of the epilogue tile
-  constexpr int CH = N / 64;                         // 4-element chunks per lane and row: 6
-  static_assert(N % 128 == 0 && WPW * 8 * Img::PIECE_ROWS == N && BM == 8 * Img::PIECE_ROWS, "8 waves share the pieces of a stage evenly");
-  static_assert(BM * TLD * 4 <= RES_BYTES + NST * STAGE_BYTES, "the epilogue tile aliases the A images and the ring");
+  constexpr int STAGE_BYTES = W_OFF + T::W_BYTES;                          // N = 384: 8 KB + 48 KB
+  static_assert(T::TILE_BYTES <= RES_BYTES + NST * STAGE_BYTES, "the epilogue tile aliases the A images and the ring");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   unsigned char* const ring = lds + RES_BYTES;
   const int tid = threadIdx.x;
@@ -143,17 +114,8 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
     for (int i = 0; i < WPW; ++i) glds16(w_rsrc, base + W_OFF + (wave * WPW + i) * 1024, offsW[i], so);
   };
 
-  {
-    // this workgroup's share of W (rows 12 j .. 12 j + 11, j = its place among the 32 workgroups of its XCD) into the XCD's L2, through
-    // throw-away pieces into the ring's last stage: older than tile 0, so landed before the first barrier lets anybody fill that stage
-    const int j = (blockIdx.x >> 3) & 31, cpr = p.K >> 3, n = (N / 32) * cpr;
-    unsigned char* dst = ring + (NST - 1) * STAGE_BYTES + wave * 1024;
-    for (int i = wave; i * 64 < n; i += 8) {
-      const int q = min(i * 64 + lane, n - 1);
-      const int row = j * (N / 32) + q / cpr, c = q - (q / cpr) * cpr;
-      glds16(w_rsrc, dst, (unsigned)((int64_t)row * p.ldw * 2 + c * 16), 0);
-    }
-  }
+  // this workgroup's share of W (rows 12 j .. 12 j + 11 at N = 384) through the ring's last stage
+  ROWTILE_PREFETCH_W(w_rsrc, p.ldw, N / 32, p.K >> 3, (blockIdx.x >> 3) & 31, ring + (NST - 1) * STAGE_BYTES + wave * 1024);
 
   f32x16 acc[FN];
   zero_acc(acc);
@@ -240,107 +202,14 @@ __global__ __launch_bounds__(512, 1) void gemm_rowln_kernel(RowLnParams p) {
     if (kt + 1 < nk) issue(kt + 1);
     const unsigned char* sb = ring + (kt % NST) * STAGE_BYTES;
     const unsigned char* sa = MERGED ? lds + kt * A_BYTES : sb;   // merged: the resident image of this k-step
-    op16x8 af[KS], bfr[KS][FN];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 2 * ks + h;
-      af[ks] = *reinterpret_cast<const op16x8*>(sa + offA + ((c ^ swzA) << 4));
-#pragma unroll
-      for (int j = 0; j < FN; ++j) bfr[ks][j] = *reinterpret_cast<const op16x8*>(sb + offB[j] + ((c ^ swzB[j]) << 4));
-    }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[j] = MSAM2_MFMA_32x32x16(af[ks], bfr[ks][j], acc[j], 0, 0, 0);
+    op16x8 af[T::KS], bfr[T::KS][FN];
+    rowtile_read_fragments<N>(af, bfr, sa, sb, offA, swzA, offB, swzB, h);
+    ROWTILE_MFMAS(N, acc, af, bfr);
   }
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();                          // every wave is past its last fragment read: the ring is dead
 
-  // ---- epilogue.  Row side first: everything a lane will load, before any store
-  const int l16 = lane & 15;
-  int64_t grow[2];
-  f32x4 rv[2][CH], ww[CH], bb[CH];
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    grow[ps] = m0 + ps * 32 + wave * 4 + (lane >> 4);
-    const float* rr = p.R + min(grow[ps], (int64_t)p.M - 1) * p.ldr;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) rv[ps][j] = *reinterpret_cast<const f32x4*>(rr + (l16 + 16 * j) * 4);
-  }
-#pragma unroll
-  for (int j = 0; j < CH; ++j) {
-    ww[j] = *reinterpret_cast<const f32x4*>(p.ln_w + (l16 + 16 * j) * 4);
-    bb[j] = *reinterpret_cast<const f32x4*>(p.ln_b + (l16 + 16 * j) * 4);
-  }
-  // acc + bias -> the row-major tile: register e of lane (r, h) is row (e & 3) + 8 (e >> 2) + 4 h, column r of its 32 x 32 block
-  float* tile = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int j = 0; j < FN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e)
-      tile[(ws * 32 + s_frag_key(e, h)) * TLD + wq * (N / 4) + j * 32 + r] = acc[j][e] + bias_j[j];
-  __builtin_amdgcn_s_barrier();
-  // x = (acc + bias) + r for both passes, and the fp32 rows
-  float v[2][CH][4];
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    const float* trow = tile + (ps * 32 + wave * 4 + (lane >> 4)) * TLD;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(trow + (l16 + 16 * j) * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[ps][j][e] = t[e] + rv[ps][j][e];
-    }
-  }
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    if (grow[ps] < p.M) {
-      float* cr = p.C + grow[ps] * p.ldc;
-#pragma unroll
-      for (int j = 0; j < CH; ++j) *reinterpret_cast<f32x4*>(cr + (l16 + 16 * j) * 4) = f32x4{v[ps][j][0], v[ps][j][1], v[ps][j][2], v[ps][j][3]};
-    }
-  }
-  // layernorm_kernel's arithmetic on the row (C = N, every chunk inside the row)
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    float mean, rstd;
-    if constexpr (N == 384) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s += v[ps][j][e];
-      group16_add(s);
-      mean = s / N;
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = v[ps][j][e] - mean;
-          q += d * d;
-        }
-      group16_add(q);
-      rstd = 1.0f / sqrtf(q / N + p.eps);
-    } else {
-      rowln_stats<CH, N>(v[ps], p.eps, mean, rstd);
-    }
-    if (grow[ps] < p.M) {
-      op16* yr = p.Y + grow[ps] * p.ldy;
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        op16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float u;
-          if constexpr (N == 384) u = (v[ps][j][e] - mean) * rstd * ww[j][e] + bb[j][e];
-          else u = rowln_value(v[ps][j][e], mean, rstd, ww[j][e], bb[j][e]);
-          o[e] = f2out<op16>(u);
-        }
-        *reinterpret_cast<op16x4*>(yr + (l16 + 16 * j) * 4) = o;
-      }
-    }
-  }
+  ROWTILE_EPILOGUE(N, false, p, lds, m0, acc, bias_j);
 #endif
 }
 
@@ -367,18 +236,16 @@ extern "C" int msam2_gemm_residual_layernorm(const void* A, int64_t lda, const v
   MSAM2_REQUIRE(msam2_gemm_residual_layernorm_supported(N, K),
                 "gemm_residual_layernorm: N=%lld K=%lld is not built (N = 384 with K %% 64 == 0; N = 256 with K = 64, 256 or 2048)", (long long)N,
                 (long long)K);
-  MSAM2_REQUIRE(M > 0 && M < (1ll << 31) - 64, "gemm_residual_layernorm: M=%lld", (long long)M);
-  MSAM2_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "gemm_residual_layernorm: lda, ldw must be multiples of 8 (16-byte rows), >= K");
-  MSAM2_REQUIRE(ldr % 4 == 0 && ldc % 4 == 0 && ldy % 4 == 0 && ldr >= N && ldc >= N && ldy >= N,
-                "gemm_residual_layernorm: ldr, ldc, ldy must be multiples of 4, >= N");
-  MSAM2_REQUIRE(vec_ok(8, 2, A, W) && vec_ok(4, 4, (const void*)bias, (const void*)R32, (const void*)C32, (const void*)ln_w, (const void*)ln_b) &&
-                    vec_ok(4, 2, (const void*)Y16),
-                "gemm_residual_layernorm: A, W, bias, R32, C32, ln_w, ln_b must be 16-byte aligned, Y16 8-byte");
-  MSAM2_REQUIRE(M * lda * 2 < (1ll << 31) && N * ldw * 2 < (1ll << 31), "gemm_residual_layernorm: A / W beyond the 2 GB of a buffer descriptor's offsets");
+  const RowTileOut o = {R32, ldr, C32, ldc, ln_w, ln_b, eps, Y16, ldy, M};
+  const auto own = [&] {
+    MSAM2_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda >= K && ldw >= K, "gemm_residual_layernorm: lda, ldw must be multiples of 8 (16-byte rows), >= K");
+    return 0;
+  };
+  if (const int err = rowtile_check("gemm_residual_layernorm", o, N, own, {A, W}, {bias}, "A, W, bias", {{M, lda}, {N, ldw}}, "A / W")) return err;
   RowLnParams p = {};
-  p.A = (const op16*)A; p.W = (const op16*)W; p.bias = bias; p.R = R32; p.C = C32; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = (op16*)Y16;
-  p.lda = lda; p.ldw = ldw; p.ldr = ldr; p.ldc = ldc; p.ldy = ldy;
-  p.M = (int)M; p.K = (int)K; p.eps = eps;
+  p.A = (const op16*)A; p.W = (const op16*)W; p.bias = bias;
+  p.lda = lda; p.ldw = ldw; p.K = (int)K;
+  rowtile_fill_out(p, o);
   if (N == 384) return launch_rowln<384, 0>(p, stream, "gemm_residual_layernorm");
   return launch_rowln<256, 0>(p, stream, "gemm_residual_layernorm");
 }
@@ -400,20 +267,18 @@ extern "C" int msam2_gemm_merged_residual_layernorm(const void* workspace, size_
   MSAM2_REQUIRE(splits >= 2 && splits <= 8, "gemm_merged_residual_layernorm: splits=%d outside [2, 8]", splits);
   MSAM2_REQUIRE(D == 64 || D == 256, "gemm_merged_residual_layernorm: D=%lld is not built (64, 256)", (long long)D);
   MSAM2_REQUIRE(N == 256, "gemm_merged_residual_layernorm: N=%lld is not built (256)", (long long)N);
-  MSAM2_REQUIRE(M > 0 && M < (1ll << 31) - 64, "gemm_merged_residual_layernorm: M=%lld", (long long)M);
-  const size_t need = msam2_attention_workspace_bytes(1, 1, M, D, splits);
-  MSAM2_REQUIRE(workspace_bytes >= need, "gemm_merged_residual_layernorm: workspace too small (%zu of %zu bytes)", workspace_bytes, need);
-  MSAM2_REQUIRE(ldw % 8 == 0 && ldw >= D, "gemm_merged_residual_layernorm: ldw must be a multiple of 8 (16-byte rows), >= D");
-  MSAM2_REQUIRE(ldr % 4 == 0 && ldc % 4 == 0 && ldy % 4 == 0 && ldr >= N && ldc >= N && ldy >= N,
-                "gemm_merged_residual_layernorm: ldr, ldc, ldy must be multiples of 4, >= N");
-  MSAM2_REQUIRE(vec_ok(8, 2, workspace, W) && vec_ok(4, 4, (const void*)bias, (const void*)R32, (const void*)C32, (const void*)ln_w, (const void*)ln_b) &&
-                    vec_ok(4, 2, (const void*)Y16),
-                "gemm_merged_residual_layernorm: workspace, W, bias, R32, C32, ln_w, ln_b must be 16-byte aligned, Y16 8-byte");
-  MSAM2_REQUIRE(N * ldw * 2 < (1ll << 31), "gemm_merged_residual_layernorm: W beyond the 2 GB of a buffer descriptor's offsets");
+  const RowTileOut o = {R32, ldr, C32, ldc, ln_w, ln_b, eps, Y16, ldy, M};
+  const auto own = [&] {
+    const size_t need = msam2_attention_workspace_bytes(1, 1, M, D, splits);
+    MSAM2_REQUIRE(workspace_bytes >= need, "gemm_merged_residual_layernorm: workspace too small (%zu of %zu bytes)", workspace_bytes, need);
+    MSAM2_REQUIRE(ldw % 8 == 0 && ldw >= D, "gemm_merged_residual_layernorm: ldw must be a multiple of 8 (16-byte rows), >= D");
+    return 0;
+  };
+  if (const int err = rowtile_check("gemm_merged_residual_layernorm", o, N, own, {workspace, W}, {bias}, "workspace, W, bias", {{N, ldw}}, "W")) return err;
   RowLnParams p = {};
-  p.W = (const op16*)W; p.bias = bias; p.R = R32; p.C = C32; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = (op16*)Y16;
-  p.ldw = ldw; p.ldr = ldr; p.ldc = ldc; p.ldy = ldy;
-  p.M = (int)M; p.K = (int)D; p.eps = eps;
+  p.W = (const op16*)W; p.bias = bias;
+  p.ldw = ldw; p.K = (int)D;
+  rowtile_fill_out(p, o);
   p.P = (const op16*)workspace;
   p.ML = reinterpret_cast<const float*>(p.P + (size_t)splits * M * D);
   p.splits = splits;

@@ -31,8 +31,11 @@
 //   * W prefetch (gemm_rowln_kernel found it decisive): before stage 0 every workgroup sends its 1 / 32 of W1 and of W2 (j = its place
 //     among the 32 workgroups of its XCD) through throw-away pieces into the ring's second stage, so both weights are on their way into
 //     the XCD's L2 at once.  They are older than stage 0 and land before the first barrier lets anybody fill that stage;
-//   * epilogue: gemm_rowln_kernel<384, 0>'s, text for text (tile [64][N + 4] fp32 aliasing the LDS behind the last barrier; (acc + bias) +
-//     r; layernorm_kernel's expressions in its order), so that the compiler pairs its multiplies and adds as it does there.
+//   * epilogue: gemm_rowln_kernel<384, 0>'s (tile [64][N + 4] fp32 aliasing the LDS behind the last barrier; (acc + bias) + r;
+//     layernorm_kernel's expressions in its order), with a null Y ending the kernel behind the fp32 rows.
+// The tile's constants (RowTile<N>), the W prefetch, fc2's fragment reads and MFMAs and the epilogue are rowtile.h's, ONE text for this
+// kernel and gemm_rowln_kernel; so are the refusals and the params fill of the C entry (rowtile_check, rowtile_fill_out).  Here: the
+// resident A images, the hidden image, `issue`, fc1, the chunk loop.
 // Rows past M are clamped on load and masked on store.  Every wave runs the same number of barriers (4 H / 128 + 2).
 // H is a run-time multiple of 128; N = 384 is the template constant.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage): 166 VGPRs, 75 SGPRs in the fp16 build, 164 / 74 in the bf16 build, no scratch: two
@@ -42,7 +45,7 @@
 // chunk 0 -- at 49 us, the MFMAs at 3.5, the GELU at 5, the weight stream at 8: the parts ADD UP, the eight waves being in the same phase of a
 // stage at the same time.  Tried and not kept: fc1's token fragments resident in 96 registers (244 VGPRs; the skeleton fell to 40 us, the
 // kernel stayed at 60 - 64).
-#include "common.h"
+#include "rowtile.h"
 
 struct MlpRowLnParams {
   const op16* A;         // [M, N] norm2 rows
@@ -66,20 +69,16 @@ template <int N, int LAD>
 __global__ __launch_bounds__(512, 1) void mlp_rowln_kernel(MlpRowLnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Img128 Img;
-  constexpr int BM = 64, BK = 64, KS = BK / 16, HC = 128;
+  typedef RowTile<N> T;
+  constexpr int BM = T::BM, BK = T::BK, KS = T::KS, A_BYTES = T::A_BYTES, PPW = T::WPW, FN = T::FN, HC = 128;
   constexpr int KT = N / BK;                         // k images of the A rows: 6
-  constexpr int A_BYTES = BM * BK * 2;               // 8 KB
   constexpr int RES_BYTES = KT * A_BYTES;            // 48 KB
   constexpr int HID_BYTES = (HC / BK) * A_BYTES;     // 16 KB
-  constexpr int STAGE_BYTES = N * BK * 2;            // 48 KB: W2's N rows x 64 k, or W1's 128 rows x N / 2 k as KT / 2 images of 16 KB
+  constexpr int STAGE_BYTES = T::W_BYTES;            // 48 KB: W2's N rows x 64 k, or W1's 128 rows x N / 2 k as KT / 2 images of 16 KB
   constexpr int W1IMG_BYTES = HC * BK * 2;           // 16 KB
-  constexpr int PPW = STAGE_BYTES / 1024 / 8;        // pieces per wave and stage: 6
-  constexpr int FN = N / 4 / 32;                     // 32-column accumulators of C per wave: 3
-  constexpr int TLD = N + 4;
-  constexpr int CH = N / 64;
   static_assert(N == 384, "one instance: the stage of 48 KB holds W1's 128 rows x 192 k as well as W2's 384 rows x 64 k");
-  static_assert((KT / 2) * W1IMG_BYTES == STAGE_BYTES && PPW * 8 * 1024 == STAGE_BYTES && BM == 8 * Img::PIECE_ROWS, "8 waves share the pieces evenly");
-  static_assert(BM * TLD * 4 <= RES_BYTES + HID_BYTES + 2 * STAGE_BYTES, "the epilogue tile aliases the images and the ring");
+  static_assert((KT / 2) * W1IMG_BYTES == STAGE_BYTES, "a W1 stage is whole images");
+  static_assert(T::TILE_BYTES <= RES_BYTES + HID_BYTES + 2 * STAGE_BYTES, "the epilogue tile aliases the images and the ring");
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   unsigned char* const hid = lds + RES_BYTES;
   unsigned char* const ring = hid + HID_BYTES;
@@ -133,22 +132,8 @@ __global__ __launch_bounds__(512, 1) void mlp_rowln_kernel(MlpRowLnParams p) {
     // into the XCD's L2, through throw-away pieces into the ring's second buffer: older than stage 0
     const int j = (blockIdx.x >> 3) & 31;
     unsigned char* dst = ring + STAGE_BYTES + wave * 1024;
-    {
-      const int cpr = N >> 3, rows = p.H >> 5, n = rows * cpr;
-      for (int i = wave; i * 64 < n; i += 8) {
-        const int q = min(i * 64 + lane, n - 1);
-        const int row = j * rows + q / cpr, c = q - (q / cpr) * cpr;
-        glds16(w1_rsrc, dst, (unsigned)((int64_t)row * p.ldw1 * 2 + c * 16), 0);
-      }
-    }
-    {
-      const int cpr = p.H >> 3, n = (N / 32) * cpr;
-      for (int i = wave; i * 64 < n; i += 8) {
-        const int q = min(i * 64 + lane, n - 1);
-        const int row = j * (N / 32) + q / cpr, c = q - (q / cpr) * cpr;
-        glds16(w2_rsrc, dst, (unsigned)((int64_t)row * p.ldw2 * 2 + c * 16), 0);
-      }
-    }
+    ROWTILE_PREFETCH_W(w1_rsrc, p.ldw1, p.H >> 5, N >> 3, j, dst);
+    ROWTILE_PREFETCH_W(w2_rsrc, p.ldw2, N / 32, p.H >> 3, j, dst);
   }
 
   f32x16 acc[FN];
@@ -198,20 +183,15 @@ __global__ __launch_bounds__(512, 1) void mlp_rowln_kernel(MlpRowLnParams p) {
     const unsigned char* sb = ring + u * STAGE_BYTES;
     const unsigned char* sa = hid + u * A_BYTES;
     op16x8 af[KS], bfr[KS][FN];
+    rowtile_read_fragments<N>(af, bfr, sa, sb, offA, swzA, offB, swzB, h);
+    if constexpr (LAD & 4) {
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 2 * ks + h;
-      af[ks] = *reinterpret_cast<const op16x8*>(sa + offA + ((c ^ swzA) << 4));
+      for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) bfr[ks][j] = *reinterpret_cast<const op16x8*>(sb + offB[j] + ((c ^ swzB[j]) << 4));
+        for (int j = 0; j < FN; ++j) acc[j][ks] += op2f(af[ks][0]) + op2f(bfr[ks][j][0]);   // keeps the fragment reads alive
+    } else {
+      ROWTILE_MFMAS(N, acc, af, bfr);
     }
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        if constexpr (LAD & 4) acc[j][ks] += op2f(af[ks][0]) + op2f(bfr[ks][j][0]);   // keeps the fragment reads alive
-        else acc[j] = MSAM2_MFMA_32x32x16(af[ks], bfr[ks][j], acc[j], 0, 0, 0);
-      }
   };
 
   const int nc = p.H / HC;
@@ -261,85 +241,7 @@ __global__ __launch_bounds__(512, 1) void mlp_rowln_kernel(MlpRowLnParams p) {
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();                          // every wave is past its last fragment read: images and ring are dead
 
-  // ---- epilogue: gemm_rowln_kernel<384, 0>'s.  Row side first: everything a lane will load, before any store
-  const int l16 = lane & 15;
-  int64_t grow[2];
-  f32x4 rv[2][CH], ww[CH], bb[CH];
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    grow[ps] = m0 + ps * 32 + wave * 4 + (lane >> 4);
-    const float* rr = p.R + min(grow[ps], (int64_t)p.M - 1) * p.ldr;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) rv[ps][j] = *reinterpret_cast<const f32x4*>(rr + (l16 + 16 * j) * 4);
-  }
-#pragma unroll
-  for (int j = 0; j < CH; ++j) {
-    ww[j] = *reinterpret_cast<const f32x4*>(p.ln_w + (l16 + 16 * j) * 4);
-    bb[j] = *reinterpret_cast<const f32x4*>(p.ln_b + (l16 + 16 * j) * 4);
-  }
-  // acc + bias -> the row-major tile: register e of lane (r, h) is row (e & 3) + 8 (e >> 2) + 4 h, column r of its 32 x 32 block
-  float* tile = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int j = 0; j < FN; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e)
-      tile[(ws * 32 + s_frag_key(e, h)) * TLD + wq * (N / 4) + j * 32 + r] = acc[j][e] + bias_j[j];
-  __builtin_amdgcn_s_barrier();
-  // x = (acc + bias) + r for both passes, and the fp32 rows
-  float v[2][CH][4];
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    const float* trow = tile + (ps * 32 + wave * 4 + (lane >> 4)) * TLD;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(trow + (l16 + 16 * j) * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[ps][j][e] = t[e] + rv[ps][j][e];
-    }
-  }
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    if (grow[ps] < p.M) {
-      float* cr = p.C + grow[ps] * p.ldc;
-#pragma unroll
-      for (int j = 0; j < CH; ++j) *reinterpret_cast<f32x4*>(cr + (l16 + 16 * j) * 4) = f32x4{v[ps][j][0], v[ps][j][1], v[ps][j][2], v[ps][j][3]};
-    }
-  }
-  if (!p.Y) return;                                      // no LayerNorm rows asked for (uniform; no barrier follows)
-  // layernorm_kernel's arithmetic on the row (C = N, every chunk inside the row)
-#pragma unroll
-  for (int ps = 0; ps < 2; ++ps) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) s += v[ps][j][e];
-    group16_add(s);
-    const float mean = s / N;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < CH; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[ps][j][e] - mean;
-        q += d * d;
-      }
-    group16_add(q);
-    const float rstd = 1.0f / sqrtf(q / N + p.eps);
-    if (grow[ps] < p.M) {
-      op16* yr = p.Y + grow[ps] * p.ldy;
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        op16x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float u = (v[ps][j][e] - mean) * rstd * ww[j][e] + bb[j][e];
-          o[e] = f2out<op16>(u);
-        }
-        *reinterpret_cast<op16x4*>(yr + (l16 + 16 * j) * 4) = o;
-      }
-    }
-  }
+  ROWTILE_EPILOGUE(N, true, p, lds, m0, acc, bias_j);
 #endif
 }
 
@@ -362,23 +264,19 @@ extern "C" int msam2_mlp_residual_layernorm_fwd(const void* A, int64_t lda, cons
   MSAM2_REQUIRE(!Y16 || (ln_w && ln_b), "mlp_residual_layernorm: LayerNorm rows asked for without ln_w, ln_b");
   MSAM2_REQUIRE(msam2_mlp_residual_layernorm_supported(N, H), "mlp_residual_layernorm: N=%lld H=%lld is not built (N = 384 with H %% 128 == 0)",
                 (long long)N, (long long)H);
-  MSAM2_REQUIRE(M > 0 && M < (1ll << 31) - 64, "mlp_residual_layernorm: M=%lld", (long long)M);
-  MSAM2_REQUIRE(lda % 8 == 0 && ldw1 % 8 == 0 && ldw2 % 8 == 0 && lda >= N && ldw1 >= N && ldw2 >= H,
-                "mlp_residual_layernorm: lda, ldw1, ldw2 must be multiples of 8 (16-byte rows), lda, ldw1 >= N, ldw2 >= H");
-  MSAM2_REQUIRE(ldr % 4 == 0 && ldc % 4 == 0 && ldr >= N && ldc >= N && (!Y16 || (ldy % 4 == 0 && ldy >= N)),
-                "mlp_residual_layernorm: ldr, ldc, ldy must be multiples of 4, >= N");
-  MSAM2_REQUIRE(vec_ok(8, 2, A, W1, W2) &&
-                    vec_ok(4, 4, (const void*)b1, (const void*)b2, (const void*)R32, (const void*)C32, (const void*)ln_w, (const void*)ln_b) &&
-                    vec_ok(4, 2, (const void*)Y16),
-                "mlp_residual_layernorm: A, W1, W2, b1, b2, R32, C32, ln_w, ln_b must be 16-byte aligned, Y16 8-byte");
-  MSAM2_REQUIRE(M * lda * 2 < (1ll << 31) && H * ldw1 * 2 < (1ll << 31) && N * ldw2 * 2 < (1ll << 31),
-                "mlp_residual_layernorm: A / W1 / W2 beyond the 2 GB of a buffer descriptor's offsets");
+  const RowTileOut o = {R32, ldr, C32, ldc, ln_w, ln_b, eps, Y16, ldy, M};
+  const auto own = [&] {
+    MSAM2_REQUIRE(lda % 8 == 0 && ldw1 % 8 == 0 && ldw2 % 8 == 0 && lda >= N && ldw1 >= N && ldw2 >= H,
+                  "mlp_residual_layernorm: lda, ldw1, ldw2 must be multiples of 8 (16-byte rows), lda, ldw1 >= N, ldw2 >= H");
+    return 0;
+  };
+  if (const int err = rowtile_check("mlp_residual_layernorm", o, N, own, {A, W1, W2}, {b1, b2}, "A, W1, W2, b1, b2",
+                                    {{M, lda}, {H, ldw1}, {N, ldw2}}, "A / W1 / W2"))
+    return err;
   MlpRowLnParams p = {};
-  p.A = (const op16*)A; p.W1 = (const op16*)W1; p.W2 = (const op16*)W2; p.b1 = b1; p.b2 = b2; p.R = R32; p.C = C32;
-  p.ln_w = Y16 ? ln_w : (const float*)R32; p.ln_b = Y16 ? ln_b : (const float*)R32;   // null Y: the up-front loads read N valid floats nobody uses
-  p.Y = (op16*)Y16;
-  p.lda = lda; p.ldw1 = ldw1; p.ldw2 = ldw2; p.ldr = ldr; p.ldc = ldc; p.ldy = ldy;
-  p.M = (int)M; p.H = (int)H; p.eps = eps;
+  p.A = (const op16*)A; p.W1 = (const op16*)W1; p.W2 = (const op16*)W2; p.b1 = b1; p.b2 = b2;
+  p.lda = lda; p.ldw1 = ldw1; p.ldw2 = ldw2; p.H = (int)H;
+  rowtile_fill_out(p, o);
   return launch_mlp_rowln<0>(p, stream);
 }
 
@@ -390,9 +288,9 @@ int msam2_mlp_rowln_ladder(int lad, const void* A, const void* W1, const void* W
                                       const float* ln_b, void* Y16, int64_t M, int64_t H, void* stream) {
   MSAM2_REQUIRE(A && W1 && W2 && R32 && C32 && ln_w && ln_b && Y16 && M > 0 && H > 0 && H % 128 == 0, "mlp_rowln_ladder: operands");
   MlpRowLnParams p = {};
-  p.A = (const op16*)A; p.W1 = (const op16*)W1; p.W2 = (const op16*)W2; p.R = R32; p.C = C32; p.ln_w = ln_w; p.ln_b = ln_b; p.Y = (op16*)Y16;
-  p.lda = 384; p.ldw1 = 384; p.ldw2 = H; p.ldr = 384; p.ldc = 384; p.ldy = 384;
-  p.M = (int)M; p.H = (int)H; p.eps = 1e-6f;
+  p.A = (const op16*)A; p.W1 = (const op16*)W1; p.W2 = (const op16*)W2;
+  p.lda = 384; p.ldw1 = 384; p.ldw2 = H; p.H = (int)H;
+  rowtile_fill_out(p, RowTileOut{R32, 384, C32, 384, ln_w, ln_b, 1e-6f, Y16, 384, M});
   switch (lad) {
     case 0: return launch_mlp_rowln<0>(p, stream);
     case 1: return launch_mlp_rowln<1>(p, stream);

@@ -260,6 +260,26 @@ def layernorm_dual(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, ep
     return y.reshape(x.shape), y16.reshape(x.shape)
 
 
+def _rowln_outputs(name: str, residual: torch.Tensor, M: Optional[int], N: int, ln_w: torch.Tensor, ln_b: torch.Tensor, biases, vectors_text: str,
+                   out: Optional[torch.Tensor], out16: Optional[torch.Tensor], device):
+    """The output side of the three full-row wrappers, checked in their order: residual fp32 [M, N] (M None: the residual's rows give M);
+    ln_w, ln_b fp32 [N] and every (bias or None, length) of `biases` fp32 contiguous, named by `vectors_text`; out / out16 allocated on
+    `device` where None, then validated.  Returns (M, out, out16)."""
+    _req(residual.dim() == 2 and residual.dtype == F32 and residual.shape == (residual.shape[0] if M is None else M, N) and residual.stride(1) == 1,
+         f"{name}: residual must be fp32 [M, N]")
+    M = residual.shape[0]
+    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
+         and all(b is None or (b.dtype == F32 and b.numel() == n and b.is_contiguous()) for b, n in biases),
+         f"{name}: {vectors_text}")
+    if out is None:
+        out = torch.empty(M, N, dtype=F32, device=device)
+    if out16 is None:
+        out16 = torch.empty(M, N, dtype=OP16, device=device)
+    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
+         f"{name}: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    return M, out, out16
+
+
 def gemm_residual_layernorm_supported(N: int, K: int) -> bool:
     """True when `gemm_residual_layernorm` is built for this output width and reduction length (per-slice quantities only)."""
     return bool(lib().msam2_gemm_residual_layernorm_supported(N, K))
@@ -276,16 +296,8 @@ def gemm_residual_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[tor
     N = w.shape[0]
     _req(gemm_residual_layernorm_supported(N, K),
          f"gemm_residual_layernorm: N = {N}, K = {K} is not built (N = 384 with K % 64 == 0; N = 256 with K = 64, 256 or 2048)")
-    _req(residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1, "gemm_residual_layernorm: residual must be fp32 [M, N]")
-    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
-         and (bias is None or (bias.dtype == F32 and bias.numel() == N and bias.is_contiguous())),
-         "gemm_residual_layernorm: bias, ln_w, ln_b are fp32 [N]")
-    if out is None:
-        out = torch.empty(M, N, dtype=F32, device=a.device)
-    if out16 is None:
-        out16 = torch.empty(M, N, dtype=OP16, device=a.device)
-    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
-         "gemm_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    M, out, out16 = _rowln_outputs("gemm_residual_layernorm", residual, M, N, ln_w, ln_b, ((bias, N),), "bias, ln_w, ln_b are fp32 [N]", out, out16,
+                                   a.device)
     check(lib().msam2_gemm_residual_layernorm(_p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(residual), residual.stride(0), _p(out),
                                               out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16), out16.stride(0), M, N, K, _stream()))
     return out, out16
@@ -310,17 +322,8 @@ def mlp_residual_layernorm(a: torch.Tensor, w1: torch.Tensor, b1: Optional[torch
     M, N = a.shape
     H = w1.shape[0]
     _req(mlp_residual_layernorm_supported(N, H), f"mlp_residual_layernorm: N = {N}, H = {H} is not built (N = 384 with H % 128 == 0)")
-    _req(residual.dtype == F32 and residual.shape == (M, N) and residual.stride(1) == 1, "mlp_residual_layernorm: residual must be fp32 [M, N]")
-    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
-         and (b1 is None or (b1.dtype == F32 and b1.numel() == H and b1.is_contiguous()))
-         and (b2 is None or (b2.dtype == F32 and b2.numel() == N and b2.is_contiguous())),
-         "mlp_residual_layernorm: b1 is fp32 [H]; b2, ln_w, ln_b are fp32 [N]")
-    if out is None:
-        out = torch.empty(M, N, dtype=F32, device=a.device)
-    if out16 is None:
-        out16 = torch.empty(M, N, dtype=OP16, device=a.device)
-    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
-         "mlp_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    M, out, out16 = _rowln_outputs("mlp_residual_layernorm", residual, M, N, ln_w, ln_b, ((b1, H), (b2, N)),
+                                   "b1 is fp32 [H]; b2, ln_w, ln_b are fp32 [N]", out, out16, a.device)
     check(lib().msam2_mlp_residual_layernorm_fwd(_p(a), a.stride(0), _p(w1), w1.stride(0), _p(b1), _p(w2), w2.stride(0), _p(b2), _p(residual),
                                                  residual.stride(0), _p(out), out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16),
                                                  out16.stride(0), M, N, H, _stream()))
@@ -341,18 +344,8 @@ def gemm_merged_residual_layernorm(workspace: torch.Tensor, splits: int, D: int,
     _req(w.dim() == 2 and w.dtype == OP16 and w.stride(1) == 1 and w.shape[1] == D, f"gemm_merged_residual_layernorm: w is 16-bit [N, {D}], K-contiguous")
     _req(workspace.dtype == torch.uint8 and workspace.is_contiguous(), "gemm_merged_residual_layernorm: workspace is a contiguous uint8 buffer")
     N = w.shape[0]
-    _req(residual.dim() == 2 and residual.dtype == F32 and residual.shape[1] == N and residual.stride(1) == 1,
-         "gemm_merged_residual_layernorm: residual must be fp32 [M, N]")
-    M = residual.shape[0]
-    _req(ln_w.dtype == F32 and ln_b.dtype == F32 and ln_w.numel() == N and ln_b.numel() == N and ln_w.is_contiguous() and ln_b.is_contiguous()
-         and (bias is None or (bias.dtype == F32 and bias.numel() == N and bias.is_contiguous())),
-         "gemm_merged_residual_layernorm: bias, ln_w, ln_b are fp32 [N]")
-    if out is None:
-        out = torch.empty(M, N, dtype=F32, device=w.device)
-    if out16 is None:
-        out16 = torch.empty(M, N, dtype=OP16, device=w.device)
-    _req(out.dtype == F32 and out.shape == (M, N) and out.stride(1) == 1 and out16.dtype == OP16 and out16.shape == (M, N) and out16.stride(1) == 1,
-         "gemm_merged_residual_layernorm: out is fp32 [M, N], out16 16-bit [M, N], rows contiguous")
+    M, out, out16 = _rowln_outputs("gemm_merged_residual_layernorm", residual, None, N, ln_w, ln_b, ((bias, N),), "bias, ln_w, ln_b are fp32 [N]",
+                                   out, out16, w.device)
     check(lib().msam2_gemm_merged_residual_layernorm(_p(workspace), workspace.numel(), int(splits), int(D), _p(w), w.stride(0), _p(bias), _p(residual),
                                                      residual.stride(0), _p(out), out.stride(0), _p(ln_w), _p(ln_b), float(eps), _p(out16),
                                                      out16.stride(0), M, N, _stream()))
