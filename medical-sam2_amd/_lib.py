@@ -138,6 +138,7 @@ SIGNATURES = {
     "msam2_bank_decide": (c_i, [c_p, c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_p]),
     "msam2_bank_commit": (c_i, [c_p, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p]),
     "msam2_label_slices": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_p, c_i, c_p, c_p, c_p]),
+    "msam2_label_confidence": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_l, c_f, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p]),
     "msam2_label_stats": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p]),
     "msam2_label_pick": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
     "msam2_label_components_workspace_bytes": (c_z, [c_l, c_l, c_l]),

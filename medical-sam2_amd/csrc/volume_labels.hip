@@ -237,3 +237,213 @@ extern "C" int msam2_label_slices(const float* logits, const uint8_t* ids, int64
   }
   return msam2_check_launch("label_slices");
 }
+
+// ---- how far every decision was from going the other way: msam2_label_confidence ---------------------------------------------------------
+// label_slices_kernel evaluates v_o for every object at every voxel, keeps the arg-max and drops the rest.  This kernel keeps, in the
+// same single pass over the objects, the top value tv with its object to and the second value sv (strict comparisons: ties to the lower
+// index, a tied value becomes sv, NaN never enters), and from them
+//   labelled (tv > label_thr):            m = m_in  = tv - fmaxf(label_thr, sv)      how far the label is from changing
+//   background with a finite tv:          m = m_out = label_thr - tv                 how far the nearest object `to` is from claiming it
+// (one fp32 subtraction each, >= 0).  margins[0 .. K) ascending cut m into bands; `select` picks the band of the core / envelope volumes.
+// Same shape as label_slices_kernel: blockIdx.y = slice, object loop innermost with the voxel's values in registers, VPT = 4 with one
+// 4-byte store per requested volume, dead lanes recompute the last group, integer counters in LDS and one global atomicAdd per workgroup
+// and non-zero counter.
+//
+// Counters, per (slice, object): col 0 voxels labelled o; col 1 voxels with v_o > label_thr that another object took (the workgroup
+// accumulates #{v_o > label_thr} there, one ballot per object and voxel of a lane inside the object loop, and subtracts col 0 when it
+// flushes); cols 2 .. 2 + K labelled o with m_in < margins[k]; cols 2 + K .. 2 + 2K background nearest o with m_out < margins[k].
+// CHOSEN for cols 0 and 2 ..: a voxel belongs to ONE object there (to), so the wave walks the distinct `to` values it holds -- first pending
+// lane's object broadcast, that object's lanes retired, (1 + 2K) ballots per voxel of a lane for it, lane 0 adds the non-zero popcounts to
+// LDS.  A wave of 64 x VPT neighbouring voxels holds a handful of objects on an organ map, so this costs (distinct objects) x (1 + 2K) x VPT
+// ballots where tally_object's form (every object asks every lane) would cost n x (1 + 2K) x VPT.  The alternative has not been built;
+// tools/confidence_bench.py times the entry with and without counts, which bounds what the walk costs.
+namespace {
+
+constexpr int CONF_MAX_BANDS = 8;
+constexpr int CONF_MAX_COLS = 2 + 2 * CONF_MAX_BANDS;
+struct ConfMargins {           // by value in the kernel arguments: the launch reads no host memory later, so it can be captured
+  float m[CONF_MAX_BANDS];     // [K ..) = +inf, never looked at
+};
+
+template <int VPT, bool COUNT>
+__global__ __launch_bounds__(LBL_THREADS) void label_confidence_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ ids, int n,
+                                                                       int lh, int lw, int H, int W, float label_thr, ConfMargins mg, int K,
+                                                                       int select, uint8_t* __restrict__ labels, uint8_t* __restrict__ core,
+                                                                       uint8_t* __restrict__ envelope, uint8_t* __restrict__ conf,
+                                                                       int* __restrict__ counts) {
+  const int t = blockIdx.y;
+  const int plane = lh * lw;
+  const float* base = logits + (int64_t)t * n * plane;
+  const float sy = (float)lh / H, sx = (float)lw / W;
+  const int Wg = W / VPT, groups = H * Wg;                  // H * W < 2^31 (host)
+  const int64_t slice = (int64_t)t * H * W;
+  const bool lane0 = (threadIdx.x & 63) == 0;
+  const int cols = 2 + 2 * K;
+  __shared__ int cnt[COUNT ? LABEL_MAX_OBJ * CONF_MAX_COLS : 1];
+  if (COUNT) {
+    for (int i = threadIdx.x; i < n * cols; i += LBL_THREADS) cnt[i] = 0;
+    __syncthreads();
+  }
+  const float m_sel = mg.m[select];
+#pragma unroll 1
+  for (int it = 0; it < LBL_ITER; ++it) {
+    const int64_t gi = ((int64_t)blockIdx.x * LBL_ITER + it) * LBL_THREADS + threadIdx.x;
+    const bool live = gi < groups;
+    const int g = live ? (int)gi : groups - 1;               // dead lanes recompute the last group (no divergent loads), masked below
+    const int Y = g / Wg, X0 = (g - Y * Wg) * VPT;
+    float tv[VPT], sv[VPT];
+    int to[VPT];
+    ResizeTaps taps[VPT];
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+      tv[e] = sv[e] = -INFINITY;
+      to[e] = -1;
+      taps[e] = resize_taps(lh, lw, sy, sx, Y, X0 + e);
+    }
+    const bool vec4_form = VPT == 4 || (W & 3) == 0;
+    for (int o = 0; o < n; ++o) {
+      const float* p = base + (int64_t)o * plane;
+      int above = 0;
+#pragma unroll
+      for (int e = 0; e < VPT; ++e) {
+        const float v = resize_value(p, taps[e], vec4_form, VPT == 4 ? (e & 1) != 0 : (X0 & 1) != 0);
+        if (v > tv[e]) {                                      // strict: ties to the lower index, the tied value becomes sv; NaN never enters
+          sv[e] = tv[e];
+          tv[e] = v;
+          to[e] = o;
+        } else if (v > sv[e]) {
+          sv[e] = v;
+        }
+        if (COUNT) above += __popcll(__ballot(live && v > label_thr));
+      }
+      if (COUNT && lane0 && above) atomicAdd(cnt + o * cols + 1, above);
+    }
+    bool lab[VPT];
+    unsigned below[VPT];                                      // bit k: m < margins[k]
+    unsigned lb = 0, cb = 0, eb = 0, fb = 0;                   // the four output bytes of each voxel, packed
+#pragma unroll
+    for (int e = 0; e < VPT; ++e) {
+      lab[e] = tv[e] > label_thr;
+      const bool near = !lab[e] && tv[e] > -INFINITY && tv[e] < INFINITY;   // background with a finite top value: `to` is its nearest object
+      const float m = lab[e] ? tv[e] - fmaxf(label_thr, sv[e]) : label_thr - tv[e];
+      unsigned lt = 0, ge = 0;
+#pragma unroll
+      for (int k = 0; k < CONF_MAX_BANDS; ++k) {
+        if (k >= K) break;
+        lt |= (unsigned)(m < mg.m[k]) << k;
+        ge += m >= mg.m[k];
+      }
+      const bool owned = lab[e] || near;
+      below[e] = owned ? lt : 0u;
+      if (!(live && owned)) to[e] = -1;                       // from here on: the object whose band columns this voxel counts in, or none
+      const unsigned id = owned ? ids[to[e] < 0 ? 0 : to[e]] : 0u;
+      const unsigned idl = lab[e] ? id : 0u;
+      lb |= idl << (8 * e);
+      cb |= (lab[e] && m >= m_sel ? id : 0u) << (8 * e);
+      eb |= (lab[e] || (near && m < m_sel) ? id : 0u) << (8 * e);
+      fb |= (owned ? ge : (unsigned)K) << (8 * e);
+    }
+    if (live) {
+      const int64_t at = slice + (int64_t)g * VPT;
+      if (VPT == 4) {
+        if (labels) *reinterpret_cast<unsigned*>(labels + at) = lb;
+        if (core) *reinterpret_cast<unsigned*>(core + at) = cb;
+        if (envelope) *reinterpret_cast<unsigned*>(envelope + at) = eb;
+        if (conf) *reinterpret_cast<unsigned*>(conf + at) = fb;
+      } else {
+        if (labels) labels[at] = (uint8_t)lb;
+        if (core) core[at] = (uint8_t)cb;
+        if (envelope) envelope[at] = (uint8_t)eb;
+        if (conf) conf[at] = (uint8_t)fb;
+      }
+    }
+    if (COUNT) {
+      for (;;) {                                              // the distinct objects this wave holds, one per turn (wave-uniform trip count)
+        int cand = -1;
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) cand = to[e] >= 0 ? to[e] : cand;
+        const unsigned long long any = __ballot(cand >= 0);
+        if (!any) break;
+        const int o = __shfl(cand, __ffsll((long long)any) - 1);
+        bool in[VPT], out[VPT];
+        int c0 = 0;
+#pragma unroll
+        for (int e = 0; e < VPT; ++e) {
+          const bool mine = to[e] == o;
+          in[e] = mine && lab[e];
+          out[e] = mine && !lab[e];
+          if (mine) to[e] = -1;                               // retired
+          c0 += __popcll(__ballot(in[e]));
+        }
+        int* c = cnt + o * cols;
+        if (lane0 && c0) atomicAdd(c, c0);
+#pragma unroll
+        for (int k = 0; k < CONF_MAX_BANDS; ++k) {
+          if (k >= K) break;
+          int ci = 0, co = 0;
+#pragma unroll
+          for (int e = 0; e < VPT; ++e) {
+            const bool b = (below[e] >> k) & 1u;
+            ci += __popcll(__ballot(in[e] && b));
+            co += __popcll(__ballot(out[e] && b));
+          }
+          if (lane0 && ci) atomicAdd(c + 2 + k, ci);
+          if (lane0 && co) atomicAdd(c + 2 + K + k, co);
+        }
+      }
+    }
+  }
+  if (COUNT) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < n * cols; i += LBL_THREADS) {
+      const int col = i % cols;
+      const int c = col == 1 ? cnt[i] - cnt[i - 1] : cnt[i];   // #{v_o > label_thr} minus the voxels o labelled: what another object took
+      if (c) atomicAdd(counts + (int64_t)t * n * cols + i, c);
+    }
+  }
+}
+
+template <int VPT, bool COUNT>
+void launch_label_confidence(hipStream_t s, const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H,
+                             int64_t W, float label_thr, const ConfMargins& mg, int64_t K, int64_t select, uint8_t* labels, uint8_t* core,
+                             uint8_t* envelope, uint8_t* conf, int* counts) {
+  const int64_t groups = H * (W / VPT), per = (int64_t)LBL_THREADS * LBL_ITER;
+  hipLaunchKernelGGL((label_confidence_kernel<VPT, COUNT>), dim3(cdiv(groups, per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits, ids, (int)n,
+                     (int)lh, (int)lw, (int)H, (int)W, label_thr, mg, (int)K, (int)select, labels, core, envelope, conf, counts);
+}
+
+}  // namespace
+
+extern "C" int msam2_label_confidence(const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H, int64_t W,
+                                      float label_thr, const float* margins, int64_t K, int64_t select, uint8_t* labels, uint8_t* core,
+                                      uint8_t* envelope, uint8_t* conf, int* counts, void* stream) {
+  MSAM2_REQUIRE(logits && ids && margins, "label_confidence: null logits / ids / margins");
+  LABEL_REQUIRE_OBJECTS("label_confidence", n);
+  MSAM2_REQUIRE(K >= 1 && K <= CONF_MAX_BANDS, "label_confidence: K = %lld margins (1 .. %d per call)", (long long)K, CONF_MAX_BANDS);
+  MSAM2_REQUIRE(T >= 1 && T <= LABEL_MAX_SLICES && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
+                "label_confidence: bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)T, (long long)lh, (long long)lw,
+                (long long)H, (long long)W);
+  ConfMargins mg;
+  for (int k = 0; k < CONF_MAX_BANDS; ++k) {
+    mg.m[k] = INFINITY;
+    if (k >= K) continue;
+    const float m = margins[k];                              // a HOST pointer: read here, passed on by value
+    MSAM2_REQUIRE(std::isfinite(m) && m > 0.f && (k == 0 || m > mg.m[k - 1]),
+                  "label_confidence: margins[%d] = %g (finite, positive and strictly ascending)", k, (double)m);
+    mg.m[k] = m;
+  }
+  MSAM2_REQUIRE(select >= 0 && select < K, "label_confidence: select = %lld (0 .. %lld)", (long long)select, (long long)(K - 1));
+  MSAM2_REQUIRE(labels || core || envelope || conf || counts, "label_confidence: no output requested (labels, core, envelope, conf, counts)");
+  hipStream_t s = (hipStream_t)stream;
+  if (counts && hipMemsetAsync(counts, 0, (size_t)(T * n * (2 + 2 * K)) * sizeof(int), s) != hipSuccess)
+    return msam2_check_launch("label_confidence (memset)");
+  const bool vec4 = W % 4 == 0 && (((uintptr_t)labels | (uintptr_t)core | (uintptr_t)envelope | (uintptr_t)conf) & 3) == 0;
+  if (vec4) {
+    if (counts) launch_label_confidence<4, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
+    else launch_label_confidence<4, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
+  } else {
+    if (counts) launch_label_confidence<1, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
+    else launch_label_confidence<1, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
+  }
+  return msam2_check_launch("label_confidence");
+}

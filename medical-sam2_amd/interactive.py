@@ -8,6 +8,10 @@ device: `volume_labels.label_volume` turns the stored low-res logits into a labe
 (csrc/clicks.hip) finds the click of every (slice, object) and `prompts.worst_slices` the slices to correct.  Per round one small table
 crosses to the host: the overlap counts and the chosen click rows, in one copy.
 
+Without a ground truth `review_queue` takes the place of `refine_volume`'s scoring half: `volume_labels.volume_confidence` turns the same stored
+logits into the label volume, a confident core and a generous envelope, `prompts.review_slices` names each object's most uncertain slices and
+`corrective_clicks(core, envelope)` the centre of the largest uncertain part of each -- where a reader should look first; one copy to the host.
+
 Not built: clicks merged into `segment_volume`'s or `train_step_3d`'s prompt dictionaries, and the image predictor's loop."""
 from __future__ import annotations
 
@@ -16,8 +20,9 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-from .prompts import corrective_clicks, worst_slices
-from .volume_labels import label_volume, volume_scores
+from .prompts import corrective_clicks, review_slices, worst_slices
+from .volume_labels import (DEFAULT_PROBABILITIES, confidence_report, label_volume, margins_from_probabilities, slice_consistency,
+                            volume_confidence, volume_scores)
 
 
 def _propagate(predictor, state) -> None:
@@ -90,3 +95,43 @@ def refine_volume(predictor, state, gt: torch.Tensor, obj_ids: Sequence[int], ro
         for o, t, x, y, label in record["clicks"]:
             predictor.add_new_points(state, t, o, [[float(x), float(y)]], [label], clear_old_points=False)
     return records
+
+
+@torch.no_grad()
+def review_queue(state, obj_ids: Sequence[int], probabilities=DEFAULT_PROBABILITIES, select: int = 1, per_object: int = 1,
+                 label_thr: float = 0.0):
+    """state: a propagated inference state (only its stored low-res logits are read: no predictor, no ground truth); obj_ids: the label values
+    of its objects, in the state's order.  `volume_confidence` at video resolution with the margins of `probabilities` gives labels, core and
+    envelope of band `select`; per object its `per_object` slices with the most uncertain voxels of that band (`review_slices`) and on each the
+    point `corrective_clicks(core, envelope, mode="center")` gives: the voxels of the envelope that the core misses ARE the uncertain band, so
+    it is the voxel deepest inside its largest part.  Returns (report, queue): report = `confidence_report` (with "slice_dice" when the volume has
+    two slices or more, plus "margins"), queue = [(obj_id, slice, x, y, uncertain_voxels)], objects in order, most uncertain slice first; an object
+    with fewer uncertain slices has fewer rows.  One device-to-host copy."""
+    obj_ids = [int(o) for o in obj_ids]
+    T, H, W = state["num_frames"], state["video_height"], state["video_width"]
+    n, per = len(obj_ids), int(per_object)
+    margins = margins_from_probabilities(probabilities)
+    conf = volume_confidence(_stored_logits(state), H, W, obj_ids, margins=margins, select=select, label_thr=label_thr,
+                             maps=("labels", "core", "envelope"))
+    counts = conf["counts"]
+    dev, K = counts.device, len(margins)
+    parts = [counts]
+    if T > 1:
+        parts.append(slice_consistency(conf["labels"], obj_ids))
+    points, _, _ = corrective_clicks(conf["core"], conf["envelope"], obj_ids, "center")
+    where = review_slices(counts, select, per)                                          # [n, per], -1 = no such slice
+    at = where.clamp(min=0)
+    obj = torch.arange(n, device=dev)[:, None]
+    xy = points[at, obj, 0].to(torch.int64)                                             # [n, per, 2]
+    uncertain = (counts[..., 2 + select] + counts[..., 2 + K + select]).to(torch.int64)[at, obj]
+    parts.append(torch.cat([where[..., None], xy, uncertain[..., None]], dim=-1))
+    host = torch.cat([p.reshape(-1).to(torch.int64) for p in parts]).cpu().numpy()      # the call's one device-to-host copy
+    sizes = [p.numel() for p in parts]
+    k = host[: sizes[0]].reshape(tuple(counts.shape))
+    c = host[sizes[0]: sizes[0] + sizes[1]].reshape(T - 1, n, 3) if T > 1 else None
+    report = confidence_report(k, c)
+    report["margins"] = margins
+    queue = []
+    for j, rows in enumerate(host[len(host) - sizes[-1]:].reshape(n, per, 4).tolist()):
+        queue.extend((obj_ids[j], t, x, y, u) for t, x, y, u in rows if t >= 0)
+    return report, queue

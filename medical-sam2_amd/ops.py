@@ -1175,6 +1175,50 @@ def label_slices(logits: torch.Tensor, ids, H: int, W: int, label_thr: float = 0
     return out, counts
 
 
+CONFIDENCE_OUTPUTS = ("labels", "core", "envelope", "conf")
+
+
+def label_confidence(logits: torch.Tensor, ids, H: int, W: int, margins, select: int = 0, label_thr: float = 0.0, labels=True, core=True,
+                     envelope=True, conf=True, counts=True):
+    """fp32 [T, n, lh, lw] low-res logits -> (labels, core, envelope, conf: uint8 [T, H, W] | None each, counts int32 [T, n, 2 + 2K] | None) of
+    their (H, W) bilinear resize, which is never written -- label_slices' pass, keeping the second-best value as well.  Per voxel tv = the top
+    value with its object `to`, sv = the second (ties to the lower index, the tied value is sv).  Labelled (tv > label_thr): margin
+    m = tv - max(label_thr, sv); background with a finite tv: nearest object `to`, m = label_thr - tv.  margins: K host floats (1 .. 8,
+    finite, > 0, strictly ascending, rounded to fp32), in logit units.
+    labels = label_slices' bytes; core = ids[to] where labelled and m >= margins[select], else 0; envelope = the label, and on background
+    ids[to] where m < margins[select]; conf = #{k: m >= margins[k]} (K where no object is nearest: 0 = least certain).  counts columns:
+    0 voxels labelled o, 1 voxels with v_o > label_thr that another object took, 2 .. 2 + K labelled o with m < margins[k],
+    2 + K .. 2 + 2K background nearest o with m < margins[k].
+    Every output: True = allocated here, False = skipped, or (volumes) a uint8 contiguous [T, H, W] tensor / (counts) an int32 contiguous
+    [T, n, 2 + 2K] tensor filled in place.  ids: as label_slices takes them.  Nothing is copied to the host."""
+    _req(logits.dtype == F32 and logits.is_contiguous() and logits.dim() == 4, "label_confidence: fp32 contiguous [T, n, lh, lw]")
+    T, n, lh, lw = logits.shape
+    dev = logits.device
+    on_dev = isinstance(ids, torch.Tensor) and ids.device == dev and dev.type != "cpu"
+    ids_d = ids.contiguous() if on_dev else label_ids(ids, dev)
+    _req(ids_d.dtype == torch.uint8 and ids_d.numel() == n, f"label_confidence: {n} objects need {n} uint8 ids")
+    H, W = int(H), int(W)
+    _req(not isinstance(margins, torch.Tensor) or margins.device.type == "cpu", "label_confidence: margins are host numbers (the call reads them)")
+    m = [float(v) for v in (margins.tolist() if isinstance(margins, torch.Tensor) else margins)]
+    K = len(m)
+    m_host = (ctypes.c_float * max(K, 1))(*m)
+    vols = []
+    for name, want in zip(CONFIDENCE_OUTPUTS, (labels, core, envelope, conf)):
+        if isinstance(want, torch.Tensor):
+            _device_table(f"label_confidence: {name}", want, torch.uint8, (T, H, W), dev, "logits'")
+            vols.append(want)
+        else:
+            vols.append(torch.empty(T, H, W, dtype=torch.uint8, device=dev) if want else None)
+    if isinstance(counts, torch.Tensor):
+        _device_table("label_confidence: counts", counts, torch.int32, (T, n, 2 + 2 * K), dev, "logits'")
+        cnt = counts
+    else:
+        cnt = torch.empty(T, n, 2 + 2 * K, dtype=torch.int32, device=dev) if counts else None
+    check(lib().msam2_label_confidence(_p(logits), _p(ids_d), T, n, lh, lw, H, W, _f32(label_thr), m_host, K, int(select), _p(vols[0]), _p(vols[1]),
+                                       _p(vols[2]), _p(vols[3]), _p(cnt), _stream()))
+    return vols[0], vols[1], vols[2], vols[3], cnt
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # start of the 3-D path: box and click prompts from a label volume (csrc/prompts.hip)
 def _label_volume_args(what: str, labels: torch.Tensor, ids, min_side: int = 1, max_voxels: bool = False):

@@ -13,6 +13,8 @@ caller wants host dictionaries.
 * `segment_prompts`: the `{slice: {...}}` prompts of `segment_volume` / `train_step_3d`; `targets_from_labels`: the latter's targets.
 * `corrective_clicks`: the next click per (slice, object) from the error regions of a prediction against the ground truth
   (`ops.label_error_clicks`, csrc/clicks.hip); `worst_slices`: where an object's error is largest.  `interactive.refine_volume` drives them.
+* `review_slices`: `worst_slices` on the uncertain-voxel columns of `volume_labels.volume_confidence` -- no ground truth
+  (`interactive.review_queue`).
 
 Not reproduced: what `random_click` does with an empty mask (label 0 at a random background pixel: the dataset never calls it for an
 absent object, and `present` tells the caller), and overlapping object masks (a label volume has one value per voxel;
@@ -143,6 +145,16 @@ def worst_slices(errors: torch.Tensor, per_object: int = 1) -> torch.Tensor:
     out = torch.full((per_object, n), -1, dtype=torch.int64, device=errors.device)
     out[: top.shape[0]] = torch.where(top >= D, D - 1 - top % D, torch.full_like(top, -1))   # total >= 1 iff key >= D
     return out.t().contiguous()
+
+
+def review_slices(counts: torch.Tensor, band: int, per_object: int = 1) -> torch.Tensor:
+    """`worst_slices` without a ground truth: counts int [D, n, 2 + 2K] of `volume_labels.volume_confidence` -> int64 [n, per_object]: per
+    object the slices with the most uncertain voxels of band `band` (labelled it with a margin below margins[band], plus background that
+    nears it within margins[band]), most first, ties to the lower slice, -1 where fewer slices have one: `worst_slices` on those two columns."""
+    assert counts.dim() == 3 and counts.shape[-1] >= 4 and counts.shape[-1] % 2 == 0 and not counts.is_floating_point(), "counts: int [D, n, 2 + 2K]"
+    K, band = (counts.shape[-1] - 2) // 2, int(band)
+    assert 0 <= band < K, f"band {band} of 0 .. {K - 1}"
+    return worst_slices(torch.stack([counts[..., 2 + band], counts[..., 2 + K + band]], dim=-1), per_object)
 
 
 def _jitter(r0, r1, c0, c1, variation: float, seed: Optional[int]) -> np.ndarray:

@@ -19,7 +19,13 @@ dilates, opens or closes every organ with a ball of a radius in millimetres (csr
 Where no ground truth exists the organs are measured: `organ_measurements` (csrc/measure.hip: one pass over the label volume and the
 image, five small integer tables) gives volume, extent, centroid, covariance and principal axes, the voxel-face surface area and the
 intensity statistics inside every organ (mean, spread, range, percentiles, histogram); `measurements_from_tables` is its host half,
-`measurement_errors` compares two such reports (relative volume difference, centroid distance)."""
+`measurement_errors` compares two such reports (relative volume difference, centroid distance).
+
+How far to trust them, still without a ground truth: `volume_confidence` (`ops.label_confidence`, csrc/volume_labels.hip) repeats
+`label_volume`'s pass and keeps what the arg-max drops -- per voxel the margin by which the decision held, against bands given in logit units
+(`margins_from_probabilities`) -- as a confidence map, a confident core volume, a generous envelope volume and integer tables per (slice, organ);
+`slice_consistency` counts the overlap of adjacent slices; `confidence_report` is the host half: volume intervals in mL, uncertain fractions,
+adjacent-slice Dice.  Core and envelope are label volumes, so every entry above (measurements, surface distances, clicks) applies to them."""
 from __future__ import annotations
 
 import math
@@ -35,6 +41,17 @@ from .metrics import scores_from_counts
 
 F32 = torch.float32
 REFERENCE_THRESHOLDS = (0.1, 0.3, 0.5, 0.7, 0.9)
+
+
+def _masks_layout(masks):
+    """the two forms of `masks` -> (slice keys in ascending order | None for a tensor, T, n, device)"""
+    if isinstance(masks, torch.Tensor):
+        assert masks.dim() == 4, "masks: [T, n, h, w]"
+        return None, masks.shape[0], masks.shape[1], masks.device
+    order = sorted(masks)
+    first = masks[order[0]]
+    assert first.dim() == 4 and first.shape[1] == 1, "masks: {slice: [n, 1, h, w]}"
+    return order, len(order), first.shape[0], first.device
 
 
 def _chunk(masks, order, i: int, j: int) -> torch.Tensor:
@@ -53,14 +70,7 @@ def label_volume(masks: Union[Dict[int, torch.Tensor], torch.Tensor], H: int, W:
     gt (uint8 [T, H, W] label volume, e.g. `labels_from_pack`) returns (labels, counts): counts int32 [K, T, n, 3] on the device =
     (|P & G|, |P|, |G|) per threshold, slice and object (see `ops.label_slices`), for `volume_scores`.  The slices go through
     `slices_per_call` at a time, so no copy of the logits is larger than one chunk; nothing is copied to the host."""
-    if isinstance(masks, torch.Tensor):
-        assert masks.dim() == 4, "masks: [T, n, h, w]"
-        order, T, n, dev = None, masks.shape[0], masks.shape[1], masks.device
-    else:
-        order = sorted(masks)
-        first = masks[order[0]]
-        assert first.dim() == 4 and first.shape[1] == 1, "masks: {slice: [n, 1, h, w]}"
-        T, n, dev = len(order), first.shape[0], first.device
+    order, T, n, dev = _masks_layout(masks)
     H, W = int(H), int(W)
     ids = ops.label_ids(list(range(1, n + 1)) if obj_ids is None else obj_ids, dev)
     assert ids.numel() == n, f"{n} objects need {n} ids"
@@ -450,3 +460,104 @@ def measurement_errors(pred_m: dict, gt_m: dict) -> dict:
         rel = np.where(vg > 0.0, (vp - vg) / vg, np.nan)
     d = np.asarray(pred_m["centroid_mm"], dtype=np.float64) - np.asarray(gt_m["centroid_mm"], dtype=np.float64)
     return {"volume_rel_diff": rel, "centroid_distance_mm": np.sqrt((d * d).sum(axis=1))}
+
+
+# ---- confidence without a ground truth: margins, core / envelope volumes, per-slice tables -----------------------------------
+DEFAULT_PROBABILITIES = (0.6, 0.75, 0.9)
+CONFIDENCE_MAPS = ops.CONFIDENCE_OUTPUTS
+
+
+def margins_from_probabilities(ps) -> tuple:
+    """Winning probabilities in (0.5, 1) -> margins in logit units, log(p / (1 - p)) rounded to fp32 (as the device compares with them): at
+    label_thr = 0 the band "margin < logit(p)" holds the voxels whose decision had a sigmoid probability below p."""
+    out = []
+    for p in ps:
+        p = float(p)
+        if not 0.5 < p < 1.0:
+            raise ValueError(f"margins_from_probabilities: p = {p} (a winning probability: 0.5 < p < 1)")
+        out.append(float(np.float32(math.log(p / (1.0 - p)))))
+    return tuple(out)
+
+
+@torch.no_grad()
+def volume_confidence(masks: Union[Dict[int, torch.Tensor], torch.Tensor], H: int, W: int, obj_ids: Optional[Sequence[int]] = None,
+                      probabilities=DEFAULT_PROBABILITIES, margins=None, select: int = 1, label_thr: float = 0.0, slices_per_call: int = 8,
+                      maps=CONFIDENCE_MAPS) -> dict:
+    """`label_volume` without a ground truth: masks and obj_ids as it takes them.  margins: K <= 8 ascending positive logit distances (default:
+    `margins_from_probabilities(probabilities)`); select: the band of the core / envelope volumes.  Returns {"labels", "core", "envelope",
+    "conf": uint8 [T, H, W] for each name in `maps`; "counts": int32 [T, n, 2 + 2K]; "margins": the K floats} with every tensor on the device
+    (`ops.label_confidence` documents volumes and columns).  The slices go through `slices_per_call` at a time; nothing is copied to the host."""
+    order, T, n, dev = _masks_layout(masks)
+    H, W = int(H), int(W)
+    ids = ops.label_ids(list(range(1, n + 1)) if obj_ids is None else obj_ids, dev)
+    assert ids.numel() == n, f"{n} objects need {n} ids"
+    m = margins_from_probabilities(probabilities) if margins is None else tuple(float(np.float32(v)) for v in margins)
+    maps = tuple(maps)
+    assert all(name in CONFIDENCE_MAPS for name in maps), f"maps: any of {CONFIDENCE_MAPS}"
+    out = {name: torch.empty(T, H, W, dtype=torch.uint8, device=dev) for name in CONFIDENCE_MAPS if name in maps}
+    out["counts"] = torch.empty(T, n, 2 + 2 * len(m), dtype=torch.int32, device=dev)
+    step = max(1, int(slices_per_call))
+    for i in range(0, T, step):
+        j = min(T, i + step)
+        ops.label_confidence(_chunk(masks, order, i, j), ids, H, W, m, select, label_thr, counts=out["counts"][i:j],
+                             **{name: out[name][i:j] if name in out else False for name in CONFIDENCE_MAPS})
+    out["margins"] = m
+    return out
+
+
+@torch.no_grad()
+def slice_consistency(labels: torch.Tensor, obj_ids) -> torch.Tensor:
+    """int32 [D - 1, n, 3] on the device = (|A & B|, |A|, |B|) per object between every slice A of the uint8 [D, H, W] label volume and the next
+    slice B: `ops.label_overlap` on the volume without its last and without its first slice (both contiguous views; D >= 2)."""
+    assert labels.dim() == 3 and labels.shape[0] >= 2, "slice_consistency: a label volume of at least two slices"
+    return ops.label_overlap(labels[:-1], labels[1:], obj_ids)
+
+
+def _host_int64(*tables):
+    """tensors (one concatenated device-to-host copy) or arrays -> int64 numpy arrays of the same shapes"""
+    if any(isinstance(t, torch.Tensor) for t in tables):
+        assert all(isinstance(t, torch.Tensor) for t in tables), "tensors or arrays, not both"
+        flat = torch.cat([t.reshape(-1).to(torch.int64) for t in tables]).cpu().numpy()
+        out, at = [], 0
+        for t in tables:
+            out.append(flat[at: at + t.numel()].reshape(tuple(t.shape)))
+            at += t.numel()
+        return out
+    return [np.asarray(t).astype(np.int64) for t in tables]
+
+
+def _confidence_figures(k: np.ndarray, K: int, ml_per_voxel: float) -> dict:
+    """k int64 [..., n, 2 + 2K] -> the figures of `confidence_report` with the same leading axes"""
+    label, inside, outside = k[..., 0], k[..., 2: 2 + K], k[..., 2 + K: 2 + 2 * K]
+    core, env = label[..., None] - inside, label[..., None] + outside
+    uncertain = inside + outside
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fraction = np.where(env > 0, uncertain.astype(np.float64) / env.astype(np.float64), np.nan)
+    return {"voxels": label, "volume_ml": label * ml_per_voxel, "core_voxels": core, "core_ml": core * ml_per_voxel, "envelope_voxels": env,
+            "envelope_ml": env * ml_per_voxel, "uncertain_voxels": uncertain, "uncertain_fraction": fraction, "overlap_voxels": k[..., 1]}
+
+
+def confidence_report(counts, consistency=None, spacing=(1.0, 1.0, 1.0)) -> dict:
+    """The host half of `volume_confidence`: counts [T, n, 2 + 2K] and, optionally, `slice_consistency`'s table [T - 1, n, 3] (device tensors:
+    the call's one device-to-host copy; or numpy arrays), spacing (sz, sy, sx) in millimetres.  Per organ o and band k, from int64 sums over the
+    slices: "voxels", "volume_ml" [n] of the label; "core_voxels", "core_ml" [n, K] (label minus the labelled voxels with a margin below
+    margins[k]); "envelope_voxels", "envelope_ml" [n, K] (label plus the background voxels that near to o) -- the volume interval of band k;
+    "uncertain_voxels" [n, K] and "uncertain_fraction" = uncertain / envelope (NaN where the envelope is empty); "overlap_voxels" [n]: above the
+    label threshold but labelled another organ.  "per_slice": the same keys with a leading slice axis.  With consistency: "slice_dice"
+    float64 [T - 1, n] = 2 |A & B| / (|A| + |B|) of adjacent slices, NaN where both are empty.  Integers up to the final division."""
+    tables = _host_int64(counts) if consistency is None else _host_int64(counts, consistency)
+    k = tables[0]
+    assert k.ndim == 3 and k.shape[-1] >= 4 and k.shape[-1] % 2 == 0, "counts: [T, n, 2 + 2K]"
+    K = (k.shape[-1] - 2) // 2
+    sp = tuple(float(s) for s in spacing)
+    assert len(sp) == 3 and all(s > 0.0 for s in sp), "spacing: three positive values (sz, sy, sx)"
+    ml = sp[0] * sp[1] * sp[2] / 1000.0
+    out = _confidence_figures(k.sum(axis=0), K, ml)
+    out["per_slice"] = _confidence_figures(k, K, ml)
+    if consistency is not None:
+        c = tables[1]
+        assert c.ndim == 3 and c.shape[-1] == 3 and c.shape[1] == k.shape[1], "consistency: [T - 1, n, 3]"
+        den = c[..., 1] + c[..., 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["slice_dice"] = np.where(den > 0, 2.0 * c[..., 0].astype(np.float64) / den.astype(np.float64), np.nan)
+    return out
