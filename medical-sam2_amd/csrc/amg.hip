@@ -340,8 +340,8 @@ extern "C" int msam2_mask_stats(const float* logits, int64_t M, int64_t lh, int6
   MSAM2_REQUIRE(((uintptr_t)boxes & 15) == 0, "mask_stats: boxes must be 16-byte aligned");
   MSAM2_REQUIRE(workspace_bytes >= msam2_mask_stats_workspace_bytes(M), "mask_stats: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(counts, 0, (size_t)M * 3 * sizeof(int), s) != hipSuccess || hipMemsetAsync(workspace, 0, (size_t)M * 4 * sizeof(int), s) != hipSuccess)
-    return msam2_check_launch("mask_stats (memset)");
+  fill_on(s, counts, M * 3, 0);
+  fill_on(s, (int*)workspace, M * 4, 0);
   const int64_t per = STATS_THREADS * STATS_PPT;
   hipLaunchKernelGGL(mask_stats_kernel, dim3(cdiv(h * w, per), (unsigned)M), dim3(STATS_THREADS), 0, s, logits, (int)lh,
                      (int)lw, (int)h, (int)w, thr, thr_hi, thr_lo, counts, (int*)workspace);
@@ -367,7 +367,7 @@ extern "C" int msam2_mask_rle_runs(const float* logits, int64_t M, int64_t lh, i
   if (M == 0) return MSAM2_OK;
   MSAM2_REQUIRE(logits && runs, "mask_rle_runs: null tensor");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(runs, 0, (size_t)M * sizeof(int), s) != hipSuccess) return msam2_check_launch("mask_rle_runs (memset)");
+  fill_on(s, runs, M, 0);
   const int64_t total = H * W, per = RUNS_THREADS * RUNS_PPT;
   hipLaunchKernelGGL(rle_runs_kernel, dim3(cdiv(total, per), (unsigned)M), dim3(RUNS_THREADS), 0, s, logits, (int)lh, (int)lw,
                      (int)h, (int)w, (int)x0, (int)y0, (int)H, total, thr, runs);
@@ -398,8 +398,8 @@ extern "C" int msam2_box_nms(const float* boxes, const float* scores, int64_t K,
   MSAM2_REQUIRE(n_keep, "box_nms: null n_keep");
   hipStream_t s = (hipStream_t)stream;
   if (K == 0) {
-    if (hipMemsetAsync(n_keep, 0, sizeof(int), s) != hipSuccess) return msam2_check_launch("box_nms (memset)");
-    return MSAM2_OK;
+    fill_on(s, n_keep, 1, 0);
+    return msam2_check_launch("box_nms");
   }
   MSAM2_REQUIRE(boxes && scores && keep && workspace, "box_nms: null tensor");
   MSAM2_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "box_nms: boxes and workspace must be 16-byte aligned");

@@ -83,7 +83,8 @@ __global__ void cc_area_kernel(const int* __restrict__ labels_all, const int* __
   counts_all[off + i] = y > 0 ? hist_all[off + y - 1] : 0;
 }
 
-// hole filling helpers (utils/misc.py:247-258)
+// hole filling helpers (utils/misc.py:247-258).  This fill_kernel writes `value` into the small components only: an overload beside common.h's
+// flat fill_kernel<T>, which its name predates and its symbol keeps.
 __global__ void threshold_kernel(const float* __restrict__ m, uint8_t* __restrict__ out, int64_t n, float thr, int above) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = above ? (m[i] > thr) : (m[i] <= thr);
@@ -92,11 +93,6 @@ __global__ void fill_kernel(float* __restrict__ m, const int* __restrict__ label
                             int64_t n, float value) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     if (labels[i] > 0 && counts[i] <= max_area) m[i] = value;
-}
-
-// (a kernel, not hipMemsetAsync: memset nodes of a captured graph did not order reliably against neighbouring kernel nodes)
-__global__ void cc_zero_kernel(int* __restrict__ x, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] = 0;
 }
 
 }  // namespace
@@ -114,7 +110,7 @@ extern "C" int msam2_cc_label(const uint8_t* img, int32_t* labels, int32_t* coun
   hipStream_t s = (hipStream_t)stream;
   int* parent = (int*)workspace;
   int* hist = parent + N * H * W;
-  hipLaunchKernelGGL(cc_zero_kernel, dim3(grid1d(N * H * W, 2048)), dim3(256), 0, s, hist, N * H * W);
+  fill_on(s, hist, N * H * W, 0);                           // (common.h: why a kernel)
   dim3 blk(32, 8), grid(cdiv(W / 2, 32), cdiv(H / 2, 8), (unsigned)N);
   hipLaunchKernelGGL(cc_init_kernel, grid, blk, 0, s, parent, (int)W, (int)H);
   hipLaunchKernelGGL(cc_merge_kernel, grid, blk, 0, s, img, parent, (int)W, (int)H);

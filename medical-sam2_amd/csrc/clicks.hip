@@ -24,7 +24,7 @@
 //   * counts (uniform): one wave per row, per-wave LDS counters; rows int32 [D, n, H] = |FN_j| + |FP_j| per row, every element written.
 //   * table: one wave per (slice, object); in mode 1 a prefix scan over the row counts finds the row of voxel k, a ballot scan of that row of
 //     the two volumes the column (msam2_label_pick's two steps).
-// clicks and the keys are cleared by memsets on the caller's stream.  No thread waits for another beyond workgroup barriers: no spin, no grid
+// clicks and the keys are cleared by fill_kernel (common.h) on the caller's stream.  No thread waits for another beyond workgroup barriers: no spin, no grid
 // barrier, no cooperative launch.
 #include "common.h"
 
@@ -300,14 +300,13 @@ extern "C" int msam2_label_error_clicks(const uint8_t* pred, const uint8_t* gt, 
   MSAM2_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)clicks & 3) == 0,
                 "label_error_clicks: the workspace must be 8-byte aligned, clicks 4-byte");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(clicks, 0, (size_t)(D * n * CLK_FIELDS) * sizeof(int), s) != hipSuccess)
-    return msam2_check_launch("label_error_clicks (memset)");
+  fill_on(s, clicks, D * n * CLK_FIELDS, 0);
   const int64_t rows = D * H, vox = D * H * W;
   unsigned long long* keys = mode == CLK_CENTER ? (unsigned long long*)workspace : nullptr;
   int* row_counts = mode == CLK_UNIFORM ? (int*)workspace : nullptr;
   if (mode == CLK_CENTER) {
     uint16_t* g = (uint16_t*)((char*)workspace + clk_key_bytes(D, n));
-    if (hipMemsetAsync(keys, 0, clk_key_bytes(D, n), s) != hipSuccess) return msam2_check_launch("label_error_clicks (memset)");
+    fill_on(s, (int*)keys, D * n * 2 * 2, 0);                // 64-bit words, 8-byte aligned: two ints each
     hipLaunchKernelGGL(clk_row_kernel, dim3(cdiv(rows, CLK_WAVES), 2), dim3(CLK_THREADS), 0, s, pred, gt, rows, (int)W, g);
     hipLaunchKernelGGL(clk_col_kernel, dim3(cdiv(vox, CLK_THREADS)), dim3(CLK_THREADS), 0, s, pred, gt, ids, (int)n, (int)H, (int)W, vox, g, keys,
                        clicks);

@@ -475,6 +475,22 @@ static inline void with_type(int is_16bit, F&& f) {
 // here, so a total beyond 2^39 elements -- more than the device's memory holds -- would not be clamped)
 static inline unsigned grid1d(int64_t total, int64_t cap, int64_t threads = 256) { return (unsigned)min(cap, (total + threads - 1) / threads); }
 
+// The one flat pre-set of a table or workspace on the caller's stream: x[0 .. n) = value.  A kernel, never hipMemsetAsync / hipMemcpyAsync:
+// issued inside a stream capture those became memset nodes that did not order reliably against the neighbouring kernel nodes (replays of a
+// captured training step accumulated into stale data, NaNs from the third replay on, while eager launches were correct), so
+// every in-library fill is a kernel and tests/test_fill_rule_cpu.py keeps it so.  A template in an unnamed namespace: emitted only in the
+// code objects that instantiate it, with internal linkage per source.  Every table here is int32, or 64-bit words cleared to zero: <int>.
+// Not flat fills, so kernels of their own: gemm_zero_kernel (strided 2-D view), gemm_tt_zero_kernel (strided, plus a column sum), zero2_kernel
+// (two arrays in one launch), srf_zero_kernel (per-job tables), measure_init_kernel (five tables with three neutral elements).
+namespace {
+template <typename T> __global__ void fill_kernel(T* __restrict__ x, int64_t n, T value) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] = value;
+}
+template <typename T> static inline void fill_on(hipStream_t s, T* x, int64_t n, T value) {
+  if (n > 0) hipLaunchKernelGGL(fill_kernel<T>, dim3(grid1d(n, 2048)), dim3(256), 0, s, x, n, value);
+}
+}  // namespace
+
 // Can every one of `a` take an access of N elements of S bytes?  A pointer: its address is a multiple of N S bytes (null passes: an
 // optional tensor that is absent).  A stride in elements: every row it leads to keeps that alignment, i.e. it is a multiple of N.
 static inline bool vec_ok1(const void* p, int64_t n, int64_t s) { return (uintptr_t)p % (uintptr_t)(n * s) == 0; }

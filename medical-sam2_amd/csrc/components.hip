@@ -169,11 +169,6 @@ __device__ __forceinline__ unsigned long long clean_key(int size, int index) {
   return ((unsigned long long)(unsigned)size << 32) | (unsigned)(0x7fffffff - index);
 }
 
-// (a kernel, not hipMemsetAsync: cc.hip found memset nodes of a captured graph unreliable against neighbouring kernel nodes)
-__global__ void cmp_zero_kernel(int* __restrict__ x, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) x[i] = 0;
-}
-
 __global__ __launch_bounds__(CMP_THREADS) void clean_find_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ size,
                                                                  const uint8_t* __restrict__ ids, int n, CleanTables* __restrict__ t,
                                                                  int64_t N) {
@@ -327,7 +322,7 @@ extern "C" int msam2_label_clean(const uint8_t* labels, const int32_t* comp, con
   hipStream_t s = (hipStream_t)stream;
   const int64_t N = D * H * W;
   CleanTables* t = (CleanTables*)workspace;
-  hipLaunchKernelGGL(cmp_zero_kernel, dim3(1), dim3(CMP_THREADS), 0, s, (int*)workspace, (int64_t)(sizeof(CleanTables) / sizeof(int)));
+  fill_on(s, (int*)workspace, (int64_t)(sizeof(CleanTables) / sizeof(int)), 0);   // (common.h: why a kernel)
   const dim3 grid(cdiv(N, CMP_THREADS * CMP_ITER)), blk(CMP_THREADS);
   hipLaunchKernelGGL(clean_find_kernel, grid, blk, 0, s, labels, size, ids, (int)n, t, N);
   hipLaunchKernelGGL(clean_apply_kernel, grid, blk, 0, s, labels, comp, size, ids, (int)n, min_voxels, (unsigned)largest_mask, out, t, N);
@@ -341,8 +336,7 @@ extern "C" int msam2_label_overlap(const uint8_t* pred, const uint8_t* gt, const
   LABEL_REQUIRE_OBJECTS("label_overlap", n);
   LABEL_REQUIRE_SIZES("label_overlap", D, H, W, 1, LABEL_MAX_VOXELS, LABEL_AT_MOST_2G_VOXELS);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t total = D * n * 3;
-  hipLaunchKernelGGL(cmp_zero_kernel, dim3(grid1d(total, 1024, CMP_THREADS)), dim3(CMP_THREADS), 0, s, counts, total);
+  fill_on(s, counts, D * n * 3, 0);
   hipLaunchKernelGGL(overlap_kernel, dim3(cdiv(H * W, CMP_THREADS * CMP_ITER), (unsigned)D), dim3(CMP_THREADS), 0, s, pred, gt, ids, (int)n, (int)(H * W), counts);
   return msam2_check_launch("label_overlap");
 }

@@ -53,7 +53,7 @@ static inline size_t label_round16(size_t b) { return (b + 15) & ~(size_t)15; }
 // For the sources that define LABEL_BOXES_OUT before the include (holes.hip, morph.hip): a __global__ function goes into the code object of
 // every source that sees it, called or not.
 #ifdef LABEL_BOXES_OUT
-// (kernels, not hipMemcpyAsync / hipMemsetAsync: cc.hip found memset nodes of a captured graph unreliable against neighbouring kernel nodes)
+// (a kernel, not hipMemcpyAsync: see fill_kernel in common.h)
 __global__ void label_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int64_t n, int vec) {
   const int64_t step = (int64_t)gridDim.x * blockDim.x, t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (vec) {                                                // both 16-byte aligned: the tail by bytes
@@ -63,9 +63,6 @@ __global__ void label_copy_kernel(const uint8_t* __restrict__ src, uint8_t* __re
   } else {
     for (int64_t i = t; i < n; i += step) dst[i] = src[i];
   }
-}
-__global__ void label_zero_kernel(int* __restrict__ x, int n) {
-  if ((int)threadIdx.x < n) x[threadIdx.x] = 0;
 }
 
 // The workspace of such an entry: LABEL_WS_HEAD_BYTES (it is never empty), the snapshot of the input when the call is in place, then
@@ -80,7 +77,7 @@ static inline const uint8_t* label_begin_out(const uint8_t* labels, uint8_t* out
   uint8_t* copy_to = in_place ? (uint8_t*)(ws + LABEL_WS_HEAD_BYTES) : out;
   hipLaunchKernelGGL(label_copy_kernel, dim3(grid1d(N, 4096, 256 * 16)), dim3(256), 0, s, labels, copy_to, N,
                      (int)((((uintptr_t)labels | (uintptr_t)copy_to) & 15) == 0));
-  hipLaunchKernelGGL(label_zero_kernel, dim3(1), dim3(LABEL_MAX_OBJ * 4), 0, s, info, (int)n * 4);
+  fill_on(s, info, n * 4, 0);
   return in_place ? copy_to : labels;
 }
 #endif

@@ -15,7 +15,7 @@
 //     segment's length, and only the head touches LDS (one add to the row count, one min and one max on the column extent).  A wave of
 //     background costs one ballot and no LDS access.
 //   * the band's row counts leave with plain stores (each row of the table has exactly one owner), and (count, r0, r1, c0, c1) of the
-//     objects the band contains with one atomic each.  stats is pre-set to -1 by a memset on the caller's stream: r0 / c0 are minimised
+//     objects the band contains with one atomic each.  stats is pre-set to -1 by fill_kernel on the caller's stream: r0 / c0 are minimised
 //     as UNSIGNED numbers (0xffffffff is the neutral element and reads back as -1 when the object is absent), r1 / c1 maximised as signed
 //     ones, and the first band of every slice adds 1 to every count, so an absent object ends at (0, -1, -1, -1, -1).
 // msam2_label_pick: one workgroup per (slice, object): a prefix scan over the object's row counts (rows r0 .. r1, 256 at a time) finds
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(STAT_THREADS) void label_stats_kernel(const uint8_t
   __syncthreads();
   if (tid < n) {
     int* st = stats + ((int64_t)d * n + tid) * 5;
-    const int c = t.cnt[tid] + (blockIdx.x == 0 ? 1 : 0);  // the memset left -1 in the count
+    const int c = t.cnt[tid] + (blockIdx.x == 0 ? 1 : 0);  // the pre-set left -1 in the count
     if (c) atomicAdd(st, c);
     if (t.cnt[tid] > 0) {
       atomicMin(reinterpret_cast<unsigned*>(st + 1), (unsigned)t.r0[tid]);
@@ -245,7 +245,7 @@ extern "C" int msam2_label_stats(const uint8_t* labels, const uint8_t* ids, int6
   LABEL_REQUIRE_OBJECTS("label_stats", n);
   LABEL_REQUIRE_SIZES("label_stats", D, H, W, 1, LABEL_NO_VOXEL_CAP, "");
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(stats, 0xff, (size_t)(D * n * 5) * sizeof(int), s) != hipSuccess) return msam2_check_launch("label_stats (memset)");
+  fill_on(s, stats, D * n * 5, -1);                         // (common.h: why a kernel)
   int64_t band = cdiv(STAT_BAND_BYTES, W);
   band = band < STAT_ROWS ? band : STAT_ROWS;
   band = band < H ? band : H;

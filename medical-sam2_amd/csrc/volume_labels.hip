@@ -68,6 +68,22 @@ __device__ __forceinline__ float resize_value(const float* __restrict__ p, const
 constexpr int LBL_THREADS = 256, LBL_ITER = 4;          // voxel groups per thread: a workgroup owns 1024 groups of VPT voxels of one slice
 constexpr int LBL_MAX_THR = 8;
 
+// Host side of both entries.  The refusal of their sizes (entry: a string literal):
+#define LBL_REQUIRE_SIZES(entry, T, lh, lw, H, W)                                                                                        \
+  MSAM2_REQUIRE((T) >= 1 && (T) <= LABEL_MAX_SLICES && (lh) > 0 && (lw) > 0 && (H) > 0 && (W) > 0 && (lh) * (lw) < (1ll << 31) &&       \
+                    (H) * (W) < (1ll << 31),                                                                                             \
+                entry ": bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)(T), (long long)(lh), (long long)(lw),   \
+                (long long)(H), (long long)(W))
+// The VPT x COUNT ladder and the grid: launch(VPT and COUNT as std::integral_constant values, grid) for the instance that applies
+template <typename F>
+static inline void lbl_dispatch(bool vec4, bool count, int64_t T, int64_t H, int64_t W, F&& launch) {
+  auto go = [&](auto vpt, auto cnt) { launch(vpt, cnt, dim3(cdiv(H * (W / decltype(vpt)::value), (int64_t)LBL_THREADS * LBL_ITER), (unsigned)T)); };
+  const std::integral_constant<int, 4> four;
+  const std::integral_constant<int, 1> one;
+  if (vec4) count ? go(four, std::true_type{}) : go(four, std::false_type{});
+  else count ? go(one, std::true_type{}) : go(one, std::false_type{});
+}
+
 // Counts of one object over the VPT voxels of each lane of this wave, added to the workgroup's LDS counters c[k * kstride + (0, 1, 2)] =
 // (|P & G|, |P|, |G|) of threshold k.  P = in && v > th[k]; the ballots are wave-uniform, so are the branches around the LDS atomics.
 template <int VPT>
@@ -92,6 +108,26 @@ __device__ __forceinline__ void tally_object(int* c, int kstride, const float (&
     }
     if (lane0) LABEL_OVERLAP_ADD(c + k * kstride, ci, cp, cg);
   }
+}
+
+// The group of VPT voxels a thread has in iteration `it` of its workgroup: g of `groups` (Wg per row), first voxel (Y, X0).  Dead lanes
+// recompute the last group (no divergent loads) and are masked by `live`.
+template <int VPT>
+struct VoxelGroup {
+  bool live;
+  int g, Y, X0;
+  __device__ __forceinline__ VoxelGroup(int it, int groups, int Wg) {
+    const int64_t gi = ((int64_t)blockIdx.x * LBL_ITER + it) * LBL_THREADS + threadIdx.x;
+    live = gi < groups;
+    g = live ? (int)gi : groups - 1;
+    Y = g / Wg, X0 = (g - Y * Wg) * VPT;
+  }
+};
+// a group's output bytes, packed one per voxel from bit 0: one 4-byte store (VPT = 4, `at` a multiple of 4 in an aligned volume) or one byte
+template <int VPT>
+__device__ __forceinline__ void store_group(uint8_t* __restrict__ vol, int64_t at, unsigned bytes) {
+  if (VPT == 4) *reinterpret_cast<unsigned*>(vol + at) = bytes;
+  else vol[at] = (uint8_t)bytes;
 }
 
 // One thread: VPT consecutive X of one row (VPT = 4 needs W % 4 == 0 and 4-byte aligned labels / gt: one 4-byte load and store), the
@@ -121,10 +157,9 @@ __global__ __launch_bounds__(LBL_THREADS) void label_slices_kernel(const float* 
   }
 #pragma unroll 1
   for (int it = 0; it < LBL_ITER; ++it) {
-    const int64_t gi = ((int64_t)blockIdx.x * LBL_ITER + it) * LBL_THREADS + threadIdx.x;
-    const bool live = gi < groups;
-    const int g = live ? (int)gi : groups - 1;               // dead lanes recompute the last group (no divergent loads), masked below
-    const int Y = g / Wg, X0 = (g - Y * Wg) * VPT;
+    const VoxelGroup<VPT> vg(it, groups, Wg);
+    const bool live = vg.live;
+    const int g = vg.g, Y = vg.Y, X0 = vg.X0;
     uint8_t gb[VPT];
 #pragma unroll
     for (int e = 0; e < VPT; ++e) gb[e] = 0;
@@ -180,14 +215,10 @@ __global__ __launch_bounds__(LBL_THREADS) void label_slices_kernel(const float* 
       }
     }
     if (labels != nullptr && live) {
-      if (VPT == 4) {
-        unsigned u = 0;
+      unsigned u = 0;
 #pragma unroll
-        for (int e = 0; e < VPT; ++e) u |= (unsigned)(bo[e] >= 0 ? ids[bo[e]] : (uint8_t)0) << (8 * e);
-        *reinterpret_cast<unsigned*>(labels + slice + (int64_t)g * 4) = u;
-      } else {
-        labels[slice + g] = bo[0] >= 0 ? ids[bo[0]] : (uint8_t)0;
-      }
+      for (int e = 0; e < VPT; ++e) u |= (unsigned)(bo[e] >= 0 ? ids[bo[e]] : (uint8_t)0) << (8 * e);
+      store_group<VPT>(labels, slice + (int64_t)g * VPT, u);
     }
   }
   if (COUNT) {
@@ -201,15 +232,6 @@ __global__ __launch_bounds__(LBL_THREADS) void label_slices_kernel(const float* 
   }
 }
 
-template <int VPT, bool COUNT>
-void launch_label_slices(hipStream_t s, const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H,
-                         int64_t W, float label_thr, const float* thr, int64_t K, const uint8_t* gt, int exclusive, uint8_t* labels,
-                         int* counts) {
-  const int64_t groups = H * (W / VPT), per = (int64_t)LBL_THREADS * LBL_ITER;
-  hipLaunchKernelGGL((label_slices_kernel<VPT, COUNT>), dim3(cdiv(groups, per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits,
-                     ids, (int)n, (int)lh, (int)lw, (int)H, (int)W, label_thr, thr, (int)K, gt, exclusive, labels, counts, (int)T);
-}
-
 }  // namespace
 
 extern "C" int msam2_label_slices(const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H, int64_t W,
@@ -218,23 +240,17 @@ extern "C" int msam2_label_slices(const float* logits, const uint8_t* ids, int64
   MSAM2_REQUIRE(logits && ids, "label_slices: null logits / ids");
   LABEL_REQUIRE_OBJECTS("label_slices", n);
   MSAM2_REQUIRE(K >= 0 && K <= LBL_MAX_THR, "label_slices: K = %lld thresholds (at most %d per call)", (long long)K, LBL_MAX_THR);
-  MSAM2_REQUIRE(T >= 1 && T <= LABEL_MAX_SLICES && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
-                "label_slices: bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)T, (long long)lh, (long long)lw, (long long)H,
-                (long long)W);
+  LBL_REQUIRE_SIZES("label_slices", T, lh, lw, H, W);
   MSAM2_REQUIRE(labels || counts, "label_slices: neither labels nor counts requested");
   MSAM2_REQUIRE(!counts || (K >= 1 && thresholds), "label_slices: counts need 1 .. %d thresholds", LBL_MAX_THR);
   hipStream_t s = (hipStream_t)stream;
-  if (counts && hipMemsetAsync(counts, 0, (size_t)(K * T * n * 3) * sizeof(int), s) != hipSuccess)
-    return msam2_check_launch("label_slices (memset)");
+  if (counts) fill_on(s, counts, K * T * n * 3, 0);         // (common.h: why a kernel)
   const uint8_t* g = counts ? gt : nullptr;
   const bool vec4 = W % 4 == 0 && (((uintptr_t)labels | (uintptr_t)g) & 3) == 0;
-  if (vec4) {
-    if (counts) launch_label_slices<4, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
-    else launch_label_slices<4, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
-  } else {
-    if (counts) launch_label_slices<1, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
-    else launch_label_slices<1, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, thresholds, K, g, exclusive, labels, counts);
-  }
+  lbl_dispatch(vec4, counts != nullptr, T, H, W, [&](auto vpt, auto cnt, dim3 grid) {
+    hipLaunchKernelGGL((label_slices_kernel<decltype(vpt)::value, decltype(cnt)::value>), grid, dim3(LBL_THREADS), 0, s, logits, ids, (int)n, (int)lh, (int)lw, (int)H,
+                       (int)W, label_thr, thresholds, (int)K, g, exclusive, labels, counts, (int)T);
+  });
   return msam2_check_launch("label_slices");
 }
 
@@ -287,10 +303,9 @@ __global__ __launch_bounds__(LBL_THREADS) void label_confidence_kernel(const flo
   const float m_sel = mg.m[select];
 #pragma unroll 1
   for (int it = 0; it < LBL_ITER; ++it) {
-    const int64_t gi = ((int64_t)blockIdx.x * LBL_ITER + it) * LBL_THREADS + threadIdx.x;
-    const bool live = gi < groups;
-    const int g = live ? (int)gi : groups - 1;               // dead lanes recompute the last group (no divergent loads), masked below
-    const int Y = g / Wg, X0 = (g - Y * Wg) * VPT;
+    const VoxelGroup<VPT> vg(it, groups, Wg);
+    const bool live = vg.live;
+    const int g = vg.g, Y = vg.Y, X0 = vg.X0;
     float tv[VPT], sv[VPT];
     int to[VPT];
     ResizeTaps taps[VPT];
@@ -345,17 +360,10 @@ __global__ __launch_bounds__(LBL_THREADS) void label_confidence_kernel(const flo
     }
     if (live) {
       const int64_t at = slice + (int64_t)g * VPT;
-      if (VPT == 4) {
-        if (labels) *reinterpret_cast<unsigned*>(labels + at) = lb;
-        if (core) *reinterpret_cast<unsigned*>(core + at) = cb;
-        if (envelope) *reinterpret_cast<unsigned*>(envelope + at) = eb;
-        if (conf) *reinterpret_cast<unsigned*>(conf + at) = fb;
-      } else {
-        if (labels) labels[at] = (uint8_t)lb;
-        if (core) core[at] = (uint8_t)cb;
-        if (envelope) envelope[at] = (uint8_t)eb;
-        if (conf) conf[at] = (uint8_t)fb;
-      }
+      if (labels) store_group<VPT>(labels, at, lb);
+      if (core) store_group<VPT>(core, at, cb);
+      if (envelope) store_group<VPT>(envelope, at, eb);
+      if (conf) store_group<VPT>(conf, at, fb);
     }
     if (COUNT) {
       for (;;) {                                              // the distinct objects this wave holds, one per turn (wave-uniform trip count)
@@ -403,15 +411,6 @@ __global__ __launch_bounds__(LBL_THREADS) void label_confidence_kernel(const flo
   }
 }
 
-template <int VPT, bool COUNT>
-void launch_label_confidence(hipStream_t s, const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H,
-                             int64_t W, float label_thr, const ConfMargins& mg, int64_t K, int64_t select, uint8_t* labels, uint8_t* core,
-                             uint8_t* envelope, uint8_t* conf, int* counts) {
-  const int64_t groups = H * (W / VPT), per = (int64_t)LBL_THREADS * LBL_ITER;
-  hipLaunchKernelGGL((label_confidence_kernel<VPT, COUNT>), dim3(cdiv(groups, per), (unsigned)T), dim3(LBL_THREADS), 0, s, logits, ids, (int)n,
-                     (int)lh, (int)lw, (int)H, (int)W, label_thr, mg, (int)K, (int)select, labels, core, envelope, conf, counts);
-}
-
 }  // namespace
 
 extern "C" int msam2_label_confidence(const float* logits, const uint8_t* ids, int64_t T, int64_t n, int64_t lh, int64_t lw, int64_t H, int64_t W,
@@ -420,9 +419,7 @@ extern "C" int msam2_label_confidence(const float* logits, const uint8_t* ids, i
   MSAM2_REQUIRE(logits && ids && margins, "label_confidence: null logits / ids / margins");
   LABEL_REQUIRE_OBJECTS("label_confidence", n);
   MSAM2_REQUIRE(K >= 1 && K <= CONF_MAX_BANDS, "label_confidence: K = %lld margins (1 .. %d per call)", (long long)K, CONF_MAX_BANDS);
-  MSAM2_REQUIRE(T >= 1 && T <= LABEL_MAX_SLICES && lh > 0 && lw > 0 && H > 0 && W > 0 && lh * lw < (1ll << 31) && H * W < (1ll << 31),
-                "label_confidence: bad sizes (T %lld, low-res %lldx%lld, output %lldx%lld)", (long long)T, (long long)lh, (long long)lw,
-                (long long)H, (long long)W);
+  LBL_REQUIRE_SIZES("label_confidence", T, lh, lw, H, W);
   ConfMargins mg;
   for (int k = 0; k < CONF_MAX_BANDS; ++k) {
     mg.m[k] = INFINITY;
@@ -435,15 +432,11 @@ extern "C" int msam2_label_confidence(const float* logits, const uint8_t* ids, i
   MSAM2_REQUIRE(select >= 0 && select < K, "label_confidence: select = %lld (0 .. %lld)", (long long)select, (long long)(K - 1));
   MSAM2_REQUIRE(labels || core || envelope || conf || counts, "label_confidence: no output requested (labels, core, envelope, conf, counts)");
   hipStream_t s = (hipStream_t)stream;
-  if (counts && hipMemsetAsync(counts, 0, (size_t)(T * n * (2 + 2 * K)) * sizeof(int), s) != hipSuccess)
-    return msam2_check_launch("label_confidence (memset)");
+  if (counts) fill_on(s, counts, T * n * (2 + 2 * K), 0);
   const bool vec4 = W % 4 == 0 && (((uintptr_t)labels | (uintptr_t)core | (uintptr_t)envelope | (uintptr_t)conf) & 3) == 0;
-  if (vec4) {
-    if (counts) launch_label_confidence<4, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
-    else launch_label_confidence<4, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
-  } else {
-    if (counts) launch_label_confidence<1, true>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
-    else launch_label_confidence<1, false>(s, logits, ids, T, n, lh, lw, H, W, label_thr, mg, K, select, labels, core, envelope, conf, counts);
-  }
+  lbl_dispatch(vec4, counts != nullptr, T, H, W, [&](auto vpt, auto cnt, dim3 grid) {
+    hipLaunchKernelGGL((label_confidence_kernel<decltype(vpt)::value, decltype(cnt)::value>), grid, dim3(LBL_THREADS), 0, s, logits, ids, (int)n,
+                       (int)lh, (int)lw, (int)H, (int)W, label_thr, mg, (int)K, (int)select, labels, core, envelope, conf, counts);
+  });
   return msam2_check_launch("label_confidence");
 }

@@ -219,6 +219,41 @@ def test_mask_kernels_exact(crop, frame):
     assert torch.equal(boxes2.cpu().long(), R.boxes_of(up > 0.5))
 
 
+def test_mask_stats_graph_capture_and_replay():
+    """Four replays over two logit sets into caller-owned counts, boxes and workspace, poisoned before every replay: the pre-sets of counts and
+    of the workspace are nodes of the graph."""
+    import medical_sam2_amd.ops as ops
+    from medical_sam2_amd import _lib
+    M, (lh, lw), (h, w), thr, off = 3, (8, 8), (32, 32), 0.0, 1.0
+    sets = [torch.randn(M, lh, lw, generator=torch.Generator().manual_seed(seed)) * 4 for seed in (5, 6)]
+    x = sets[0].to(DEV)
+    counts = torch.empty(M, 3, dtype=torch.int32, device=DEV)
+    boxes = torch.empty(M, 4, dtype=torch.int32, device=DEV)
+    nb = _lib.lib().msam2_mask_stats_workspace_bytes(M)
+    ws = torch.empty(nb // 4, dtype=torch.int32, device=DEV)
+
+    def call():
+        rc = _lib.lib().msam2_mask_stats(ops._p(x), M, lh, lw, h, w, thr, thr + off, thr - off, ops._p(counts), ops._p(boxes), ops._p(ws), nb,
+                                         ops._stream())
+        assert rc == 0, _lib.lib().msam2_last_error().decode()
+    call()                                                          # eager first: nothing is set up inside the capture
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        call()
+    for logits in (sets[1], sets[0], sets[1], sets[0]):            # the replay reads what the buffer holds now
+        x.copy_(logits.to(DEV))
+        counts.fill_(-7), boxes.fill_(-7), ws.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        eager_counts, eager_boxes = ops.mask_stats(x, h, w, thr, off)
+        assert torch.equal(counts, eager_counts) and torch.equal(boxes, eager_boxes)
+        up = ops.bilinear_upsample(x, h, w)
+        ref_counts = torch.stack([(up > thr + off).sum((1, 2)), (up > thr - off).sum((1, 2)), (up > thr).sum((1, 2))], 1).to(torch.int32)
+        assert torch.equal(counts.cpu(), ref_counts.cpu()) and torch.equal(boxes.cpu().long(), R.boxes_of(up > thr))
+        assert 0 < int(ref_counts[:, 2].min()) and int(ref_counts[:, 2].max()) < h * w          # not vacuous
+
+
 @pytest.mark.parametrize("K", [0, 1, 7, 64, 1000, 5000, 16384])
 def test_box_nms_exact(K):
     import medical_sam2_amd.ops as ops

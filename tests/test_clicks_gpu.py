@@ -187,9 +187,9 @@ def test_graph_capture_and_replay():
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         out = ops.label_error_clicks(p, g, ids_d, workspace=ws)
-    for v in (other, pred):                                                            # the replay reads what the buffers hold now
+    for v in (other, pred, other, pred):                                               # the replay reads what the buffers hold now
         p.copy_(torch.from_numpy(v).to(DEV))
-        out.fill_(-7)
+        out.fill_(-7), ws.fill_(-7)
         graph.replay()
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), R.table(v, gt, ids))

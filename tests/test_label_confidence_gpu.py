@@ -212,7 +212,7 @@ def test_graph_capture_and_replay_with_caller_owned_outputs():
     with torch.cuda.graph(g):
         again = ops.label_confidence(x, ids_d, H, W, margins, 2, 0.0, *out)
     assert all(a is b for a, b in zip(again, out))
-    for logits in (second, first):                                                          # the replay reads what the buffer holds now
+    for logits in (second, first, second, first):                                           # the replay reads what the buffer holds now
         x.copy_(logits.to(DEV))
         for t in out:
             t.fill_(77)

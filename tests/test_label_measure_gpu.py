@@ -210,7 +210,7 @@ def test_graph_capture_and_replay_with_caller_owned_tables():
     with torch.cuda.graph(g):
         same = ops.label_measure(labels, ids_d, img, lo, bins, out=out)
     assert all(a is b for a, b in zip(same, out))
-    for v, im in ((other, other_image), (vol, image)):                    # the replay reads what the buffers hold now
+    for v, im in ((other, other_image), (vol, image)) * 2:                # the replay reads what the buffers hold now; four replays
         labels.copy_(torch.from_numpy(np.ascontiguousarray(v)).to(DEV))
         img.copy_(torch.from_numpy(im).to(DEV))
         for t in out:

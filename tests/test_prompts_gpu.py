@@ -167,7 +167,7 @@ def test_graph_capture_and_replay():
     with torch.cuda.graph(g):
         stats, rows = ops.label_stats(labels, ids_d)
         xy = ops.label_pick(labels, ids_d, stats, rows, u=u)
-    for v in (other, vol):                                                             # the replay reads what the buffers hold now
+    for v in (other, vol, other, vol):                                                 # the replay reads what the buffers hold now
         labels.copy_(torch.from_numpy(v).to(DEV))
         stats.fill_(-7), rows.fill_(-7), xy.fill_(-7)
         g.replay()

@@ -148,6 +148,44 @@ def test_random_fields_against_float64(shape, seed):
         assert np.array_equal(counts[..., 2], ref_counts[..., 2])                          # |G| does not depend on the logits
 
 
+@pytest.mark.parametrize("out", [(32, 32), (30, 30)], ids=["4_voxel_path", "scalar_path"])
+def test_graph_capture_and_replay(out):
+    """Four replays over two logit sets into caller-owned labels and counts, poisoned before every replay: the pre-set of counts is a node of
+    the graph, and a replay that did not run it in order would add to the poison or to the replay before."""
+    import medical_sam2_amd.ops as ops
+    from medical_sam2_amd import _lib
+    T, n, (lh, lw), (H, W) = 2, 3, (8, 8), out
+    ids = R.random_ids(n, 11)
+    thresholds = R.REFERENCE_THRESHOLDS[1:3]
+    gt = R.random_gt(T, H, W, ids, 11)
+    sets = [R.random_logits(T, n, lh, lw, seed) for seed in (11, 12)]
+    x, gt_d = sets[0].to(DEV), gt.to(DEV)
+    ids_d = torch.tensor(ids, dtype=torch.uint8, device=DEV)
+    thr_d = torch.tensor(R.f32_thresholds(thresholds), dtype=torch.float32, device=DEV)
+    labels = torch.empty(T, H, W, dtype=torch.uint8, device=DEV)
+    counts = torch.empty(len(thresholds), T, n, 3, dtype=torch.int32, device=DEV)
+
+    def call():
+        rc = _lib.lib().msam2_label_slices(ops._p(x), ops._p(ids_d), T, n, lh, lw, H, W, 0.0, ops._p(thr_d), len(thresholds), ops._p(gt_d), 0,
+                                           ops._p(labels), ops._p(counts), ops._stream())
+        assert rc == 0, _lib.lib().msam2_last_error().decode()
+    call()                                                                                  # eager first: nothing is set up inside the capture
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        call()
+    for logits in (sets[1], sets[0], sets[1], sets[0]):                                    # the replay reads what the buffer holds now
+        x.copy_(logits.to(DEV))
+        labels.fill_(0xAB), counts.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        up = ops.bilinear_upsample(x.view(T * n, lh, lw), H, W).view(T, n, H, W).cpu().numpy()
+        ref_labels, ref_counts, _ = R.apply_rule(up, ids, 0.0, thresholds, gt.numpy(), False)
+        assert np.array_equal(labels.cpu().numpy(), ref_labels)
+        assert np.array_equal(counts.cpu().numpy().astype(np.int64), ref_counts)
+        assert ref_counts[..., 0].sum() > 0 and len(np.unique(ref_labels)) > 2             # not vacuous
+
+
 def test_argument_errors_cross_the_abi_as_codes():
     import medical_sam2_amd.ops as ops
     from medical_sam2_amd import _lib

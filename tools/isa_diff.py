@@ -2,11 +2,13 @@
 `-S --cuda-device-only`, normalises the listings (comments, .file / .loc / .ident, debug sections and the per-translation-unit
 __hip_cuid_<hash> symbol dropped) and compares them line for line: every instruction, every .amdhsa_ field, the set of kernel symbols.
 A listing is kept beside its source (isa/ or isa_bf16/, ignored by git) and reused while no source or header is newer.
-Four verdicts per source file: `identical`; `operand order only` (same line counts, and the listings become equal once the two source
+Five verdicts per source file: `identical`; `kernels in common identical` (the kernel sets differ only by symbols of FLAT_FILL_ADDED /
+FLAT_FILL_REMOVED, and every kernel both trees have is equal: body, .amdhsa_ fields, metadata -- function numbers dropped as below); `operand order only` (same line counts, and the listings become equal once the two source
 operands of every instruction in COMMUTATIVE are put in one order -- the kernels it concerns are named); `instance order only` (the
 sources in INSTANCE_ORDER: the compiler emitted the same kernels in another order -- every kernel body is equal once the function number
 in its .LBB<n>_<m> labels is dropped, and so is the text outside the bodies when it is compared per kernel symbol and not by position);
-DIFFERS with the first differing kernel.  Exit status 0 iff no file DIFFERS.
+DIFFERS with the first differing kernel, or `kernel symbols differ` for any other change of the kernel set.  Exit status 0 iff no file
+DIFFERS or has such a change.
 usage: python tools/isa_diff.py <parent-tree> <new-tree> [--bf16]"""
 import os
 import re
@@ -26,7 +28,13 @@ COMMUTATIVE = ("s_add_i32", "s_mul_i32", "v_mul_f32_e32")
 # if / else ladders did.  The order shows in two places only: the function number <n> of the local labels, and the position of a kernel's
 # sections, .set lines and metadata entry in the file.  Extend only with sources where that is the cause.
 INSTANCE_ORDER = ("backward.hip", "conv.hip", "elementwise.hip")
-FUNC_NUMBER_RE = re.compile(r"\.(LBB|Lfunc_end)\d+")
+# The one change of the kernel SET that is accepted: the flat zero fills that three sources spelled out gave way to common.h's fill_kernel<int>
+# (the symbols in full: (anonymous namespace)::fill_kernel<int>(int*, long, int), cc_zero_kernel(int*, long), cmp_zero_kernel(int*, long),
+# label_zero_kernel(int*, int)).  Every kernel the two trees share must still be equal, body and per-symbol blocks.  Extend only with symbols
+# whose coming or going is the whole point of a change.
+FLAT_FILL_ADDED = ("_ZN12_GLOBAL__N_111fill_kernelIiEEvPT_lS1_",)
+FLAT_FILL_REMOVED = ("_ZN12_GLOBAL__N_114cc_zero_kernelEPil", "_ZN12_GLOBAL__N_115cmp_zero_kernelEPil", "_ZN12_GLOBAL__N_117label_zero_kernelEPii")
+FUNC_NUMBER_RE =re.compile(r"\.(LBB|Lfunc_end)\d+")
 COMMUTATIVE_RE = re.compile(r"^(\s*(?:%s)\s+[^,]+),\s*([^,]+),\s*([^,]+)$" % "|".join(COMMUTATIVE))
 
 
@@ -97,7 +105,16 @@ def compare(a, b, src=""):
         return "identical (%d lines)" % a.count("\n")
     ka, kb = (dict(kernels(re.sub(r"^(_Z\w+):$", r"\1: ", t, flags=re.M))) for t in (a, b))
     if set(ka) != set(kb):
-        return "kernel symbols differ: only in parent %s, only in new %s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))
+        removed, added = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
+        (ba, oa), (bb, ob) = by_symbol(a), by_symbol(b)
+        for d in (ba, oa, bb, ob):
+            for sym in removed + added:
+                d.pop(sym, None)
+        for d in (oa, ob):                                      # a kernel leaves one .section line behind that names nobody (its body: comments)
+            d[None] = [blk for blk in d.get(None, []) if not (len(blk) == 1 and blk[0].startswith("\t.section"))]
+        if set(removed) <= set(FLAT_FILL_REMOVED) and set(added) <= set(FLAT_FILL_ADDED) and (ba, oa) == (bb, ob):
+            return "kernels in common identical (%d: bodies, .amdhsa_ fields and metadata); added %s; removed %s" % (len(ba), added, removed)
+        return "kernel symbols differ: only in parent %s, only in new %s" % (removed, added)
     if src in INSTANCE_ORDER and by_symbol(a) == by_symbol(b):
         moved = sum(x != y for x, y in zip(ka, kb))
         return "instance order only (one of %s): %d of %d kernels emitted at another position, every body and every per-symbol block equal" % (
