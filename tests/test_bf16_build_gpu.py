@@ -22,13 +22,15 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "medical-sam2_amd", "libmsam2_hip_bf16.so")
 LOG = os.path.join(ROOT, "gpurun_out", "bf16_suite.log")
-# What the bf16 library re-runs: every single-process parity file -- kernels, the GEMM, attention, pointwise and backward variant matrices, modules (incl. the tighter
+# What the bf16 library re-runs: every single-process parity file -- kernels, the GEMM, attention, pointwise, backward and fused-kernel variant matrices (with the
+# feature tests of the stage 1-2 fused kernels), modules (incl. the tighter
 # operand-rounding comparison), end to end (incl. the 28-slice bank chain and the 64-slice volume at size), the unit-round-off scaling test,
 # properties, graphs, backward, gradient goldens, BPTT, the autograd bridge, the captured training step.  Left to the fp16 run only: the
 # 512-slice volume (half a minute of CPU oracle that would compete with the fp16 session's own) and the multi-process files, which spawn
 # their own children.
 FILES = ["tests/test_kernels_gpu.py", "tests/test_gemm_variants_gpu.py", "tests/test_attention_variants_gpu.py", "tests/test_pointwise_variants_gpu.py",
-         "tests/test_backward_variants_gpu.py", "tests/test_attention_bwd_variants_gpu.py",
+         "tests/test_backward_variants_gpu.py", "tests/test_attention_bwd_variants_gpu.py", "tests/test_fused_variants_gpu.py",
+         "tests/test_window_qkv_attention_gpu.py", "tests/test_proj_mlp_fused_gpu.py",
          "tests/test_modules_gpu.py",
          "tests/test_e2e_gpu.py", "tests/test_operand_rounding_gpu.py", "tests/test_properties_gpu.py", "tests/test_graphs_gpu.py", "tests/test_eval_seg.py",
          "tests/test_backward_gpu.py", "tests/test_backward_encoder_gpu.py", "tests/test_grads_golden.py", "tests/test_bptt_gpu.py",

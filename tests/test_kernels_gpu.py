@@ -786,7 +786,9 @@ def test_hip_graph_replay(ops):
 @pytest.mark.parametrize("dim,T", [(96, 512), (96, 4096 + 77), (192, 256), (192, 3000), (384, 64), (384, 4096 + 37)])
 def test_ln_mlp_residual_fused(ops, dim, T):
     """msam2_ln_mlp_residual_fwd (LayerNorm + fc1 + exact-erf GELU + fc2 + residual in one kernel, hieradet.py:166-167) against the
-    oracle's norm2 / MLP on the same 16-bit weights: ragged token counts (partial passes, clamped rows), several passes per workgroup."""
+    oracle's norm2 / MLP on the same 16-bit weights: ragged token counts (partial passes, clamped rows).  Every workgroup runs ONE pass here
+    (the launch is min(256, passes) workgroups; 4173 tokens are 9 passes at dim 96, 12 at dim 192): the grid wrap -- a workgroup's second
+    pass, the ring refill across passes -- is tests/test_fused_variants_gpu.py's."""
     x = rnd(T, dim, seed=1, scale=1.5) + 0.3
     P = {"n.weight": 1 + 0.1 * rnd(dim, seed=2), "n.bias": 0.1 * rnd(dim, seed=3),
          "m.layers.0.weight": bf(rnd(4 * dim, dim, seed=4) / dim ** 0.5).float(), "m.layers.0.bias": 0.1 * rnd(4 * dim, seed=5),
