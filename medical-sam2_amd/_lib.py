@@ -161,6 +161,13 @@ SIGNATURES = {
                                 ctypes.POINTER(c_f), c_p, c_p, c_p, c_z, c_p]),
     "msam2_label_resize": (c_i, [c_p, c_i, c_l, c_l, c_l, c_l, c_p, c_p, ctypes.POINTER(ctypes.c_uint32), c_p, c_p]),
     "msam2_label_measure": (c_i, [c_p, c_p, c_p, c_i, c_l, c_l, c_l, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "msam2_instance_remap_workspace_bytes": (c_z, [c_l]),
+    "msam2_instance_remap": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_z, c_p]),
+    "msam2_instance_apply": (c_i, [c_p, c_p, c_l, c_l, c_p, c_p]),
+    "msam2_instance_pairs_workspace_bytes": (c_z, [c_l, c_l]),
+    "msam2_instance_pairs": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_z, c_p]),
+    "msam2_instance_paint_workspace_bytes": (c_z, [c_l]),
+    "msam2_instance_paint": (c_i, [c_p, c_l, c_l, c_l, c_p, c_p, c_i, c_p, c_p, c_z, c_p]),
     "msam2_decoder_tokens_supported": (c_i, [c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_l, c_l]),
     "msam2_decoder_tokens_self": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_decoder_tokens_workspace_bytes": (c_z, [c_l, c_l]),

@@ -1526,6 +1526,123 @@ def label_measure(labels: torch.Tensor, ids, image: Optional[torch.Tensor] = Non
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# instances: contiguous ids, pair tables and painted maps behind PQ / AJI / lesion-wise F1 (csrc/instances.hip)
+INSTANCE_MAX_PAIRS = 1 << 26      # csrc/instances.hip INS_MAX_CAP
+INSTANCE_MAX_MASKS = 65535        # csrc/instances.hip INS_MAX_MASKS
+
+
+def _instance_map(what: str, m, dev=None, shape=None):
+    """an instance map: int32 contiguous [H, W] or [D, H, W] on the GPU -> (D, H, W)"""
+    _req(isinstance(m, torch.Tensor) and m.dtype == torch.int32 and m.dim() in (2, 3) and m.is_contiguous() and m.is_cuda,
+         f"{what} must be an int32 contiguous [H, W] or [D, H, W] instance map on the GPU")
+    _req(dev is None or m.device == dev, f"{what} must be on the device of the first map")
+    _req(shape is None or tuple(m.shape) == tuple(shape), f"{what} must have the shape {list(shape or ())} of the first map")
+    D, H, W = (1, *m.shape) if m.dim() == 2 else m.shape
+    _req(1 <= D <= LABEL_MAX_SLICES and 1 <= H <= LABEL_MAX_SIDE and 1 <= W <= LABEL_MAX_SIDE and D * H * W <= LABEL_MAX_VOXELS,
+         f"{what}: sizes {D} x {H} x {W} (1 .. {LABEL_MAX_SLICES} slices of 1 .. {LABEL_MAX_SIDE} rows and columns, at most 2^31 - 2 voxels)")
+    return D, H, W
+
+
+def instance_remap(map: torch.Tensor, id_bound: int, cap: int, labels: Optional[torch.Tensor] = None, out=None):
+    """Instance map with arbitrary ids in 0 .. id_bound - 1 (0 = background) -> (out, orig, size, cls, info): out = the map with contiguous ids
+    1 .. n in ascending order of the original id (remap_label(by_size=False)); orig / size / cls int32 [cap] = original id, voxel count and the
+    largest value of the uint8 volume `labels` over the instance (0 without labels); info int32 [4] = (instances found, voxels with an id
+    outside [0, id_bound): they become 0, 1 if found > cap, 0).  found > cap: out is complete, the tables hold the first cap instances.
+    out: the five tensors of an earlier call, filled in place (its map may be `map` itself).  Nothing is copied to the host."""
+    D, H, W = _instance_map("instance_remap: map", map)
+    dev = map.device
+    id_bound, cap = int(id_bound), int(cap)
+    _req(1 <= id_bound < 2 ** 31, f"instance_remap: id_bound = {id_bound} (1 .. 2^31 - 1)")
+    _req(1 <= cap < 2 ** 31, f"instance_remap: cap = {cap} table rows (1 .. 2^31 - 1)")
+    if labels is not None:
+        _device_table("instance_remap: labels", labels, torch.uint8, map.shape, dev, "map's")
+    if out is None:
+        out = (torch.empty_like(map), *(torch.empty(cap, dtype=torch.int32, device=dev) for _ in range(3)), torch.empty(4, dtype=torch.int32, device=dev))
+    _req(isinstance(out, (tuple, list)) and len(out) == 5, "instance_remap: out must be the five tensors (out, orig, size, cls, info)")
+    for name, t, shape in zip(("map", "orig", "size", "cls", "info"), out, (map.shape, (cap,), (cap,), (cap,), (4,))):
+        _device_table(f"instance_remap: out's {name}", t, torch.int32, shape, dev, "map's")
+    o, orig, size, cls, info = out
+    nb = lib().msam2_instance_remap_workspace_bytes(id_bound)
+    ws = torch.empty(nb // 4, dtype=torch.int32, device=dev)
+    check(lib().msam2_instance_remap(_p(map), _p(labels), D, H, W, id_bound, _p(o), _p(orig), _p(size), _p(cls), cap, _p(info), _p(ws), nb, _stream()))
+    return o, orig, size, cls, info
+
+
+def instance_apply(map: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = table[map[i]] for a device int32 [n + 1] table with table[0] == 0 (the caller's contract); an id outside [0, n] gives 0.
+    out: None (a new map), or an int32 map of that shape to fill -- `map` itself for in place.  Nothing is copied to the host."""
+    _instance_map("instance_apply: map", map)
+    _req(isinstance(table, torch.Tensor) and table.dim() == 1 and table.numel() >= 1, "instance_apply: table must be int32 [n + 1]")
+    _device_table("instance_apply: table", table, torch.int32, table.shape, map.device, "map's")
+    if out is None:
+        out = torch.empty_like(map)
+    _device_table("instance_apply: out", out, torch.int32, map.shape, map.device, "map's")
+    check(lib().msam2_instance_apply(_p(map), _p(table), table.numel() - 1, map.numel(), _p(out), _stream()))
+    return out
+
+
+def instance_pairs_workspace(na: int, cap: int, dev) -> torch.Tensor:
+    """the workspace instance_pairs needs for na instances in `a` and cap pair rows"""
+    nb = lib().msam2_instance_pairs_workspace_bytes(int(na), int(cap))
+    _req(nb > 0, f"instance_pairs: na = {na} instances (1 .. 2^31 - 2) or cap = {cap} pair rows (1 .. {INSTANCE_MAX_PAIRS})")
+    return _workspace8(nb, dev)
+
+
+def instance_pairs(a: torch.Tensor, b: torch.Tensor, na: int, nb: int, cap: int, out=None, workspace: Optional[torch.Tensor] = None):
+    """Two instance maps of one shape with contiguous ids (a: 1 .. na, b: 1 .. nb, 0 = background) -> (pairs int32 [cap, 3], area_a int32 [na],
+    area_b int32 [nb], info int32 [4]): pairs = rows (i, j, |a == i and b == j|) of every non-empty pair sorted by (i, j), rows beyond
+    info[0] are 0; info = (rows written, 1 if the distinct pairs exceeded cap: no row is written then, voxels of a with an id outside
+    [0, na]: background, the same for b).  out: the four tables of an earlier call, workspace: instance_pairs_workspace(na, cap, device) --
+    with both the call allocates nothing and can be captured.  Nothing is copied to the host: the caller checks info[1]."""
+    D, H, W = _instance_map("instance_pairs: a", a)
+    dev = a.device
+    _instance_map("instance_pairs: b", b, dev, a.shape)
+    na, nb, cap = int(na), int(nb), int(cap)
+    _req(1 <= na <= LABEL_MAX_VOXELS and 1 <= nb <= LABEL_MAX_VOXELS, f"instance_pairs: na = {na}, nb = {nb} instances (1 .. 2^31 - 2)")
+    _req(1 <= cap <= INSTANCE_MAX_PAIRS, f"instance_pairs: cap = {cap} pair rows (1 .. {INSTANCE_MAX_PAIRS})")
+    shapes = ((cap, 3), (na,), (nb,), (4,))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int32, device=dev) for s in shapes)
+    _req(isinstance(out, (tuple, list)) and len(out) == 4, "instance_pairs: out must be the four tables (pairs, area_a, area_b, info)")
+    for name, t, s in zip(("pairs", "area_a", "area_b", "info"), out, shapes):
+        _device_table(f"instance_pairs: out's {name}", t, torch.int32, s, dev, "a's")
+    need = lib().msam2_instance_pairs_workspace_bytes(na, cap)
+    if workspace is None:
+        workspace = _workspace8(need, dev)
+    _req(isinstance(workspace, torch.Tensor) and workspace.dtype == torch.int64 and workspace.is_contiguous() and workspace.device == dev and
+         workspace.numel() * 8 >= need, f"instance_pairs: workspace must be int64 contiguous with at least {need} bytes on a's device")
+    pairs, area_a, area_b, info = out
+    check(lib().msam2_instance_pairs(_p(a), _p(b), D, H, W, na, nb, _p(pairs), cap, _p(area_a), _p(area_b), _p(info), _p(workspace),
+                                     workspace.numel() * 8, _stream()))
+    return pairs, area_a, area_b, info
+
+
+def instance_paint(masks: torch.Tensor, order: Optional[torch.Tensor] = None, boxes: Optional[torch.Tensor] = None, skip_covered: bool = True,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """masks uint8 [N, H, W] (non-zero = inside) -> instance map int32 [H, W] painted in the order of `order` (int32 [N] mask indices on the
+    device; None = 0 .. N - 1) by the rule of func_2d/function.py:621-624: at position k the mask is skipped if none of its pixels is still 0
+    in the map, else all its pixels become k + 1.  skip_covered=False paints every mask.  boxes int32 [N, 4] (per mask: x0, y0, x1, y1
+    inclusive): pixels outside the box count as outside the mask.  Nothing is copied to the host."""
+    _req(isinstance(masks, torch.Tensor) and masks.dtype == torch.uint8 and masks.dim() == 3 and masks.is_contiguous() and masks.is_cuda,
+         "instance_paint: masks must be a uint8 contiguous [N, H, W] tensor on the GPU")
+    N, H, W = masks.shape
+    dev = masks.device
+    _req(1 <= N <= INSTANCE_MAX_MASKS, f"instance_paint: {N} masks (1 .. {INSTANCE_MAX_MASKS})")
+    _req(1 <= H <= LABEL_MAX_SIDE and 1 <= W <= LABEL_MAX_SIDE, f"instance_paint: H x W = {H} x {W} (1 .. {LABEL_MAX_SIDE} rows and columns)")
+    if order is not None:
+        _device_table("instance_paint: order", order, torch.int32, (N,), dev, "masks'")
+    if boxes is not None:
+        _device_table("instance_paint: boxes", boxes, torch.int32, (N, 4), dev, "masks'")
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.int32, device=dev)
+    _device_table("instance_paint: out", out, torch.int32, (H, W), dev, "masks'")
+    nb = lib().msam2_instance_paint_workspace_bytes(N)
+    ws = torch.empty(nb // 4, dtype=torch.int32, device=dev)
+    check(lib().msam2_instance_paint(_p(masks), N, H, W, _p(order), _p(boxes), 1 if skip_covered else 0, _p(out), _p(ws), nb, _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # after the overlap scores: exact distance transforms and surface distances of label volumes (csrc/surface.hip)
 EDT_FEATURES = {"surface": 0, "outside": 1}
 SURFACE_WORKSPACE_BYTES = 512 << 20    # an interface default, not a measured optimum
