@@ -168,6 +168,9 @@ SIGNATURES = {
     "msam2_instance_pairs": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_l, c_p, c_l, c_p, c_p, c_p, c_p, c_z, c_p]),
     "msam2_instance_paint_workspace_bytes": (c_z, [c_l]),
     "msam2_instance_paint": (c_i, [c_p, c_l, c_l, c_l, c_p, c_p, c_i, c_p, c_p, c_z, c_p]),
+    "msam2_label_mesh_count": (c_i, [c_p, c_p, c_l, c_l, c_l, c_l, c_p, c_p]),
+    "msam2_label_mesh_workspace_bytes": (c_z, [c_p, c_i]),
+    "msam2_label_mesh": (c_i, [c_p, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_z, c_p]),
     "msam2_decoder_tokens_supported": (c_i, [c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_l, c_l]),
     "msam2_decoder_tokens_self": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_l, c_p]),
     "msam2_decoder_tokens_workspace_bytes": (c_z, [c_l, c_l]),

@@ -1697,18 +1697,21 @@ def _organ_extents(stats: "torch.Tensor"):
     return out
 
 
-def _organ_boxes(what: str, volumes, ids_d: torch.Tensor, distinct: bool = True):
+def _organ_boxes(what: str, volumes, ids_d: torch.Tensor, distinct: bool = True, extra: Optional[torch.Tensor] = None):
     """The preparation of the entries that work per organ inside a box -> (values, per volume: `_organ_extents`' list).  One `label_stats`
     call per volume (z extent: the slices with count > 0; rows and columns: the stats' min / max), then ONE device-to-host copy of those
     small tables with the ids: the only synchronisation on the way in.  distinct: ids taken from the device as they are must still be
-    distinct values in 1 .. 255."""
+    distinct values in 1 .. 255.  extra: an integer device table that rides in the same copy; it comes back flat, as a third result."""
     D, n = volumes[0].shape[0], ids_d.numel()
-    tables = [label_stats(v, ids_d)[0].reshape(-1) for v in volumes]
-    host = torch.cat(tables + [ids_d.to(torch.int32)]).cpu().numpy().astype("int64")                       # the one copy
+    tables = [label_stats(v, ids_d)[0].reshape(-1) for v in volumes] + [ids_d.to(torch.int32)]
+    if extra is not None:
+        tables = [t.to(torch.int64) for t in tables] + [extra.reshape(-1).to(torch.int64)]
+    host = torch.cat(tables).cpu().numpy().astype("int64")                                                 # the one copy
     m = D * n * 5
-    values = host[len(volumes) * m:].tolist()
+    values = host[len(volumes) * m: len(volumes) * m + n].tolist()
     _req(not distinct or (len(set(values)) == n and all(1 <= v <= 255 for v in values)), f"{what}: ids must be distinct values in 1 .. 255")
-    return values, [_organ_extents(host[k * m: (k + 1) * m].reshape(D, n, 5)) for k in range(len(volumes))]
+    extents = [_organ_extents(host[k * m: (k + 1) * m].reshape(D, n, 5)) for k in range(len(volumes))]
+    return (values, extents) if extra is None else (values, extents, host[len(volumes) * m + n:])
 
 
 def _boxes_or_empty(extents):
@@ -1838,6 +1841,79 @@ def label_fill_holes(labels: torch.Tensor, ids, connectivity: int = 6, max_voxel
     check(L.msam2_label_fill_holes(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), flat, n, c, _p(mv), HOLE_CLAIMS[claim], _p(out), _p(info),
                                    _p(ws), nb, _stream()))
     return out, info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# out of the label volume: closed surface meshes per organ, surface nets or voxel faces (csrc/mesh.hip)
+MESH_PLACEMENTS = {"corner": 0, "nets": 1}
+MESH_MAX_RELAX = 64                    # csrc/mesh.hip MESH_MAX_RELAX
+MESH_MAX_LATTICE = 1 << 29             # csrc/mesh.hip MESH_MAX_LATTICE
+MESH_WORKSPACE_BYTES = 2 << 30         # an interface default, not a measured optimum
+
+
+def label_mesh_sizes(labels: torch.Tensor, ids) -> torch.Tensor:
+    """uint8 [D, H, W] label volume -> int64 [n, 2] on the device: (vertices, quads) of the surface mesh of every listed organ -- lattice
+    points whose eight voxels are not all equal in labels == ids[j] (voxels outside the volume are not the organ), and voxel faces between
+    the organ and anything else, the volume's frame included (the row sums of label_measure's faces).  One pass, integer adds.
+    ids: host integers (checked: distinct, 1 .. 255), or the device tensor of label_ids() taken as is.  Nothing is copied to the host."""
+    ids_d, D, H, W, n = _label_volume_args("label_mesh_sizes", labels, ids, max_voxels=True)
+    counts = torch.empty(n, 2, dtype=torch.int64, device=labels.device)
+    check(lib().msam2_label_mesh_count(_p(labels), _p(ids_d), D, H, W, n, _p(counts), _stream()))
+    return counts
+
+
+def label_mesh(labels: torch.Tensor, ids, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), placement: str = "nets", relax: int = 0,
+               workspace_bytes: int = MESH_WORKSPACE_BYTES):
+    """`label_mesh_with_values` without its last result: (vertices, quads, v_offsets, q_offsets, counts)."""
+    return label_mesh_with_values(labels, ids, spacing, origin, placement, relax, workspace_bytes)[:5]
+
+
+def label_mesh_with_values(labels: torch.Tensor, ids, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), placement: str = "nets", relax: int = 0,
+                           workspace_bytes: int = MESH_WORKSPACE_BYTES):
+    """Closed, consistently oriented surface meshes of the organs of a uint8 [D, H, W] label volume on the device -> (vertices float32
+    [nv, 3] (rows (z, y, x), physical units), quads int32 [nq, 4], v_offsets [n + 1] and q_offsets [n + 1] (host lists: organ j owns
+    vertices[v_offsets[j]: v_offsets[j + 1]] and quads[q_offsets[j]: q_offsets[j + 1]], whose entries are its own vertex numbers from 0),
+    counts int32 [n, 2] (device): the (vertices, quads) the library found, equal to the segments' lengths, values: the label values as
+    host integers -- they came with the one copy, so a caller that gave ids as a device tensor need not read them back).
+    A vertex per lattice point (corner of eight voxels) whose voxels are not all inside or all outside the organ, in ascending lattice
+    order; a quad per voxel face between organ and not-organ (voxels beyond the volume are not the organ: an organ cut by the field of view
+    is closed), wound so that its normal looks out, ordered by (lowest lattice corner, axis z / y / x).  placement="corner": vertices at the
+    voxel corners (the voxel-face surface); "nets": at the mean of the midpoints of the cell's crossed edges (surface nets).  relax: 0 .. 64
+    Jacobi sweeps towards the mean of the linked vertices, every vertex kept inside its own cell.  A voxel centre (z, y, x) sits at
+    origin + (z sz, y sy, x sx).  DESIGN 7.22 has the exact arithmetic; the tables are equal to its restatement bit for bit.
+
+    The sizes (`label_mesh_sizes`) ride in the one device-to-host copy of `_organ_boxes`: the only synchronisation on the way in, nothing
+    else is copied to the host.  Organs go through in groups whose workspace (about 1.25 bytes per lattice point of the organ's box, 48
+    more with relax > 0) stays below `workspace_bytes`; an organ whose box alone needs more raises with the needed size in the message."""
+    ids_d, D, H, W, n = _label_volume_args("label_mesh", labels, ids, max_voxels=True)
+    _req(placement in MESH_PLACEMENTS, f"label_mesh: placement {placement!r} (one of {tuple(MESH_PLACEMENTS)})")
+    relax = int(relax)
+    _req(0 <= relax <= MESH_MAX_RELAX, f"label_mesh: relax = {relax} sweeps (0 .. {MESH_MAX_RELAX})")
+    sp = _spacing("label_mesh", spacing)
+    og = tuple(float(o) for o in origin)
+    _req(len(og) == 3 and all(o - o == 0.0 for o in og), f"label_mesh: origin must be three finite values (oz, oy, ox), got {og}")
+    dev = labels.device
+    values, (extents,), sizes = _organ_boxes("label_mesh", (labels,), ids_d, extra=label_mesh_sizes(labels, ids_d))
+    boxes = _boxes_or_empty(extents)
+    sizes = sizes.reshape(n, 2)
+    for v, b in zip(values, boxes):
+        lattice = (b[1] - b[0] + 2) * (b[3] - b[2] + 2) * (b[5] - b[4] + 2)
+        _req(lattice <= MESH_MAX_LATTICE, f"label_mesh: the box of id {v} has {lattice} lattice points (at most 2^29 per organ)")
+    v_offs = [0] + [int(x) for x in sizes[:, 0].cumsum()]
+    q_offs = [0] + [int(x) for x in sizes[:, 1].cumsum()]
+    # (an empty tensor's data_ptr() is 0 and the entry refuses NULL tables: keep one row when every organ is absent, slice afterwards)
+    vertices = torch.empty(max(v_offs[-1], 1), 3, dtype=torch.float32, device=dev)
+    quads = torch.empty(max(q_offs[-1], 1), 4, dtype=torch.int32, device=dev)
+    counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    L = lib()
+    need = [L.msam2_label_mesh_workspace_bytes((ctypes.c_int32 * 6)(*b), relax) for b in boxes]
+    ws, nb = _box_workspace("label_mesh", values, need, sum(need), workspace_bytes, dev)
+    i64 = lambda rows: (ctypes.c_int64 * n)(*[int(r) for r in rows])                                       # noqa: E731
+    check(L.msam2_label_mesh(_p(labels), D, H, W, (ctypes.c_uint8 * n)(*values), (ctypes.c_int32 * (6 * n))(*[v for b in boxes for v in b]),
+                             i64(v_offs[:-1]), i64(sizes[:, 0]), i64(q_offs[:-1]), i64(sizes[:, 1]), n, MESH_PLACEMENTS[placement], relax,
+                             (ctypes.c_double * 3)(*sp), (ctypes.c_double * 3)(*og), vertices.data_ptr(), quads.data_ptr(), _p(counts), _p(ws), nb,
+                             _stream()))
+    return vertices[:v_offs[-1]], quads[:q_offs[-1]], v_offs, q_offs, counts, values
 
 
 # ---------------------------------------------------------------------------------------------------------------------

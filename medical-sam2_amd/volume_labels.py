@@ -19,7 +19,9 @@ dilates, opens or closes every organ with a ball of a radius in millimetres (csr
 Where no ground truth exists the organs are measured: `organ_measurements` (csrc/measure.hip: one pass over the label volume and the
 image, five small integer tables) gives volume, extent, centroid, covariance and principal axes, the voxel-face surface area and the
 intensity statistics inside every organ (mean, spread, range, percentiles, histogram); `measurements_from_tables` is its host half,
-`measurement_errors` compares two such reports (relative volume difference, centroid distance).
+`measurement_errors` compares two such reports (relative volume difference, centroid distance).  `organ_meshes` (csrc/mesh.hip) gives the
+surface of every organ as a closed quad mesh on the device -- surface nets or the voxel faces -- for a viewer, a printer or a planning
+tool (`meshes.OrganMesh`: area, enclosed volume, STL / OBJ / PLY); `mesh_measurements` reports its area and volume.
 
 How far to trust them, still without a ground truth: `volume_confidence` (`ops.label_confidence`, csrc/volume_labels.hip) repeats
 `label_volume`'s pass and keeps what the arg-max drops -- per voxel the margin by which the decision held, against bands given in logit units
@@ -482,6 +484,33 @@ def organ_measurements(labels: torch.Tensor, image: Optional[torch.Tensor] = Non
     if image is None:
         return measurements_from_tables(m, e, None, f, None, 0, spacing, percentiles)
     return measurements_from_tables(m, e, v, f, h.reshape(k, bins), lo, spacing, percentiles)
+
+
+@torch.no_grad()
+def organ_meshes(labels: torch.Tensor, obj_ids: Optional[Sequence[int]] = None, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0),
+                 placement: str = "nets", relax: int = 0, n: Optional[int] = None, workspace_bytes: int = ops.MESH_WORKSPACE_BYTES) -> dict:
+    """The surface of every organ of the uint8 [T, H, W] label volume as a closed quad mesh on the device (`ops.label_mesh`,
+    csrc/mesh.hip) -> {obj_id: `meshes.OrganMesh`}: views of one vertex and one quad table, nothing copied to the host beyond the boxes and
+    sizes on the way in.  spacing = (sz, sy, sx) and origin = (oz, oy, ox) in millimetres: voxel centre (z, y, x) sits at origin + (z sz,
+    y sy, x sx).  placement="nets": surface nets, whose area is close to that of the smooth surface; "corner": the voxel faces themselves
+    (the area `organ_measurements` reports, and exactly the organ's voxel volume).  relax: Jacobi sweeps that smooth the net while every
+    vertex stays inside its cell (0 .. 64).  An organ without a voxel gives an empty mesh.  obj_ids / n: as `clean_labels` takes them."""
+    from .meshes import OrganMesh
+    ids = _resolve_ids("organ_meshes", labels, obj_ids, n)
+    vertices, quads, v_offs, q_offs, _, values = ops.label_mesh_with_values(labels, ids, spacing, origin, placement, relax, workspace_bytes)
+    return {v: OrganMesh(vertices[v_offs[j]: v_offs[j + 1]], quads[q_offs[j]: q_offs[j + 1]]) for j, v in enumerate(values)}
+
+
+def mesh_measurements(meshes: dict) -> dict:
+    """{obj_id: OrganMesh} of `organ_meshes` (spacing in millimetres) -> "ids", "area_mm2", "volume_mm3", "volume_ml" (float64 arrays in the
+    dict's order), "vertices" and "quads" (counts): the surface area and the enclosed volume of the mesh, beside `organ_measurements`'
+    voxel-face area and voxel volume (which stay as they are).  One scalar per figure and organ crosses to the host."""
+    ids = list(meshes)
+    area = np.array([meshes[v].area() for v in ids], dtype=np.float64)
+    vol = np.array([meshes[v].volume() for v in ids], dtype=np.float64)
+    return {"ids": ids, "area_mm2": area, "volume_mm3": vol, "volume_ml": vol / 1000.0,
+            "vertices": np.array([meshes[v].vertices.shape[0] for v in ids], dtype=np.int64),
+            "quads": np.array([meshes[v].quads.shape[0] for v in ids], dtype=np.int64)}
 
 
 def measurement_errors(pred_m: dict, gt_m: dict) -> dict:
